@@ -22,6 +22,11 @@ reference path is single-threaded by construction) timed on a bounded sample of 
 cores.  Before anything is timed the result of the SAME kernels (time-tiled kernel + record permutation passes, forced)
 is compared with the oracle's on every row of the forcing; a mismatch refuses to report.
 
+The result line is the last line of the output.  `--secondary` adds the other BASELINE configurations, each a JSON line of its
+own printed before it.  `--dump-outputs DIR` writes what the last timed step returned (final state and discharge rows; a seeded
+sample of their columns where they exceed 64 MB) as DIR/<name>.npy: the inputs are the same from run to run, so two builds can be
+compared output for output.
+
 N > 1 (one rank per GPU, torch.distributed.run): BASELINE config 5 -- ONE network of 1.25M reaches per GPU (10M at
 N = 8) graph-partitioned over the GPUs, boundary discharge exchanged over RCCL (river_route_amd/multi_gpu.py).
 """
@@ -71,12 +76,20 @@ def parse_args():
     ap.add_argument('--sequential-parts', type=int, default=0,
                     help='one GPU: the network of `--gpus P` (P x --reaches reaches, BASELINE config 5 at P = 8) cut into P parts that are routed '
                          'one after another on this card, boundary series handed from part to part (multi_gpu.run_sequential); per-part times in the line')
-    ap.add_argument('--no-secondary', action='store_true',
-                    help="N = 1: skip the `secondary` entries (BASELINE configs 2 and 4 behind their own oracle gates)")
+    ap.add_argument('--secondary', action=argparse.BooleanOptionalAction, default=False,
+                    help="N = 1: also the `secondary` entries (BASELINE configs 2 and 4 and variants, each behind its own oracle gate; "
+                         "`--workload unit`: the year of ten calls), each printed as a JSON line of its own before the result line")
     ap.add_argument('--cpu-replicas', type=int, default=-1,
                     help="also time N independent oracle replicas on N cores (the only parallelism the reference endorses, "
                          "docs/references/parallelism.md:67-114); 0 = off, -1 = a sweep over 16 / 64 / 256 / all cores")
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the timed path returned in its last step as DIR/<name>.npy '
+                         '(at most 64 MB: larger arrays as a fixed, seeded sample of their columns)')
     a = ap.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        ap.error('--steps must be at least 1 and --warmup at least 0')
+    if a.dump_outputs and (a.gpus > 1 or a.sequential_parts > 1 or a.workload == 'dropin'):
+        ap.error('--dump-outputs: one GPU, --workload rapid / unit / rapid_f32')
     if a.reaches is None:
         a.reaches = 1_000_000 if a.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and a.sequential_parts < 2 else 1_250_000
     return a
@@ -93,6 +106,26 @@ def muskingum_coefficients(k, x, dt):
     r = dt / k
     den = r + 2.0 * (1.0 - x)
     return (r - 2.0 * x) / den, (r + 2.0 * x) / den, (2.0 * (1.0 - x) - r) / den
+
+
+DUMP_BYTES = 60_000_000         # --dump-outputs: array bytes of one dump (under 64 MB with the .npy headers)
+
+
+def dump_outputs(out_dir, arrays):
+    """--dump-outputs: what the timed path handed back after its last step, as out_dir/<name>.npy in its own dtype.  `arrays` is
+    [(name, device array of shape (n,) or (rows, n), order of its rows or None)].  Each array keeps all its rows and the same share
+    of its columns: all of them when everything fits in DUMP_BYTES, otherwise a sorted sample drawn with seed 0.  The sample depends
+    only on the shapes and dtypes, so two runs with the same arguments dump the same cells."""
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    share = min(1.0, DUMP_BYTES / sum(a.numel() * a.element_size() for _, a, _ in arrays))
+    for name, a, order in arrays:
+        n = a.shape[-1]
+        if share < 1.0:
+            cols = np.sort(np.random.default_rng(0).choice(n, int(n * share), replace=False))
+            a = a.index_select(a.dim() - 1, torch.from_numpy(cols).to(a.device))
+        h = a.cpu().numpy()
+        np.save(os.path.join(out_dir, f'{name}.npy'), h if order is None else h[order])
 
 
 def host_cpu_model():
@@ -244,6 +277,8 @@ def bench_unit(args, device_index):
         one_pass()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [('q_channel', q_ch, None), ('q_full', q_full, None), ('uh_state', state, None), ('discharge', out, None)])
     from river_route_amd.engine import copy_bandwidth
     from river_route_amd.measure import roofline_from_profile
     prof = plan.profile()
@@ -251,7 +286,7 @@ def bench_unit(args, device_index):
     # a year as the reference runs it: ten files of T steps, one call each, the discharge and the convolution's tail carried from
     # call to call (UnitMuskingum.py's loop over runoff files); the same depth block stands for each file
     year = None
-    if T * 10 == 35_040 and not args.no_secondary:      # (--no-secondary: the counter passes sum every dispatch of the process)
+    if T * 10 == 35_040 and args.secondary:      # (not by default: the counter passes sum every dispatch of the process)
         def year_pass():
             state.zero_(); q_ch.zero_(); q_full.zero_()
             for _ in range(10):
@@ -415,8 +450,10 @@ def main():
             print(json.dumps(entry))
         return
     line = bench_rapid(args, device_index, net, indptr, indices, c1, c2, c3, base)
-    if not args.no_secondary and n == 1_000_000 and T == 35_040 and nsub == 1:
-        line['secondary'] = secondary_lines(args, device_index)
+    if args.secondary and n == 1_000_000 and T == 35_040 and nsub == 1:
+        # lines of their own, the result line last: all of them in one line would be too long for a reader of the output's tail
+        for entry in secondary_lines(argparse.Namespace(**{**vars(args), 'dump_outputs': None}), device_index):
+            print(json.dumps(entry))
     print(json.dumps(line))
 
 
@@ -818,6 +855,8 @@ def bench_rapid_f32(args, device_index, factor: int = 4):
         one_pass()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, [('final_state', q_t, None), ('discharge32', out32, None)])
     traffic = pmc_traffic(args.order, n, T, 1, key='f32') if factor == 4 else None
     roofline = roofline_from_profile(plan.profile(), 1, HBM_PEAK_GBS, traffic=traffic)
     whole_path(roofline, plan.profile(), plan.profile_aux(), plan.last_kernel(), float(n) * T * args.steps / elapsed, traffic)
@@ -884,6 +923,8 @@ def bench_rapid(args, local_rank, net, indptr, indices, c1, c2, c3, base):
         one_pass()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
+    if args.dump_outputs:      # step t went to sink row t % sink_rows: the sink's rows in step order are the last sink_rows steps of the year
+        dump_outputs(args.dump_outputs, [('final_state', q_t, None), ('discharge', out, (T - sink_rows + np.arange(sink_rows)) % sink_rows)])
 
     prof, aux, kern = plan.profile(), plan.profile_aux(), plan.last_kernel()      # HIP events of the last timed pass, on the engine's stream
     if base is not None and chk_name != kern:
