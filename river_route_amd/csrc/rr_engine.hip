@@ -243,7 +243,7 @@ int rr_plan_direct_layout(const rr_plan *P, int32_t *tile_c0, int32_t *tile_nc, 
 int rr_plan_last_kernel(const rr_plan *P)
 {
     if (!P) return -1;
-    return P->ses.rows_direct ? RR_KERNEL_DIRECT : (P->ses.wave ? RR_KERNEL_TILE : RR_KERNEL_TICK);
+    return (int)P->ses.kernel;
 }
 
 int rr_plan_set_options(rr_plan *P, int64_t rows_per_chunk, int64_t sample_every)
@@ -353,20 +353,23 @@ int rr_plan_reserve(rr_plan *P, int mode, int64_t T, int64_t nsub, int host_rows
     if (!P->coeffs_set) return fail(RR_E_STATE, "rr_plan_reserve before rr_plan_set_coeffs (per-edge weights decide which kernel routes)");
     if (P->ses.open) return fail(RR_E_STATE, "rr_plan_reserve: a routing call is open");
     const Mode m = mode == RR_MODE_RAPID ? Mode::Rapid : (mode == RR_MODE_MUSKINGUM ? Mode::Muskingum : Mode::Unit);
+    CallShape shape;      // (the other place a CallShape is built: call_shape)
+    shape.mode = m; shape.T = T; shape.nsub = nsub;
+    shape.host = (host_rows & 1) != 0;
+    shape.dev_rows = !shape.host && (host_rows & RR_ROWS_NOT_PLAIN) == 0;      // device rows the direct row path reads as they are
+    shape.out32 = (host_rows & RR_ROWS_F32_OUT) != 0;
+    shape.uh = (host_rows & RR_ROWS_UH) != 0;
     Schedule sch;
-    // host rows reach the time-tiled kernel through the PCIe pipeline's device rings; where it does not apply they stream
-    const bool host = (host_rows & 1) != 0, plain = !host && (host_rows & RR_ROWS_NOT_PLAIN) == 0;      // rows in device arrays (float64 or float32): the direct row path applies
-    rc = reserve_core(P, m, T, nsub, false, false, &sch, plain, (host_rows & RR_ROWS_F32_OUT) != 0, (host_rows & RR_ROWS_UH) != 0);
-    if (rc == RR_OK && host && !sch.tiled) rc = reserve_core(P, m, T, nsub, true, true, &sch);
-    if (rc == RR_OK && host && sch.tiled) rc = host_pipe_prepare(P);
+    rc = reserve_core(P, shape, &sch);
     if (rc) return rc;
     if (info) {
-        info[0] = sch.direct ? 2 : (sch.tiled ? 1 : 0); info[1] = (sch.tiled || sch.direct) ? sch.KC * kRec : 1; info[2] = sch.chunks;
+        const bool piped = shape.host && sch.kernel == Kernel::Tile;
+        const int64_t levels = sch.kernel == Kernel::Direct ? P->dp.skel.n_levels : (sch.kernel == Kernel::Tile ? P->tp.n_levels : 0);
+        info[0] = (int)sch.kernel; info[1] = sch.kernel != Kernel::Tick ? sch.KC * kRec : 1; info[2] = sch.chunks;
         info[3] = (P->ring_cap + P->mrows_cap + P->stage_cap) * (int64_t)sizeof(double);
-        info[4] = host && sch.tiled ? 2 * P->pipe.dev_cap * (int64_t)sizeof(double) : 0;
-        info[5] = host && sch.tiled ? 2 * HostPipe::kPinned * P->pipe.pin_cap * (int64_t)sizeof(double) : 0;
-        info[6] = sch.direct ? P->h.depth - 1 + (int64_t)P->dp.skel.n_levels * sch.KC * kRec
-                             : (sch.tiled ? P->h.depth - 1 + (int64_t)P->tp.n_levels * sch.KC * kRec : P->h.depth - 1);      // pipeline depth in ticks
+        info[4] = piped ? 2 * P->pipe.dev_cap * (int64_t)sizeof(double) : 0;
+        info[5] = piped ? 2 * HostPipe::kPinned * P->pipe.pin_cap * (int64_t)sizeof(double) : 0;
+        info[6] = P->h.depth - 1 + levels * sch.KC * kRec;      // pipeline depth in ticks
         info[7] = sch.ring * (int64_t)sizeof(double);
     }
     return RR_OK;
@@ -378,7 +381,7 @@ int rr_plan_profile(rr_plan *P, double prof[10])
     for (int k = 0; k < 10; ++k) prof[k] = 0.0;
     prof[0] = (double)P->prof_launches;
     prof[8] = (double)P->prof_brackets;
-    prof[9] = (P->ses.wave || P->ses.rows_direct) ? (double)(P->ses.KC * kRec) : 1.0;
+    prof[9] = P->ses.kernel != Kernel::Tick ? (double)(P->ses.KC * kRec) : 1.0;
     prof[7] = (double)P->prof_reach_steps;
     if (P->device < 0 || !P->ev_first || P->prof_launches == 0) return RR_OK;
     HIPCHK(hipSetDevice(P->device));
@@ -514,10 +517,10 @@ int rr_stream_begin(rr_plan *P, int has_lateral, const double *q_t, const double
     Rows io; io.dev_in = has_lateral ? lateral : nullptr; io.rows_in = lat_rows; io.dev_out = discharge; io.rows_out = out_rows;
     const Mode mode = has_lateral ? Mode::Rapid : Mode::Muskingum;
     if (P->ses.open) return fail(RR_E_STATE, "a routing call is already open on this plan (rr_stream_end it first)");
-    rc = prepare_call(P, mode, T, nsub, false, false, true, true, has_lateral ? lat_rows : 0, out_rows);
+    rc = prepare_call(P, call_shape(mode, T, nsub, io, true), "rr_stream_begin");
     if (rc) return rc;
     if (P->h.n > 0 && T > 0) {
-        rc = launch_state_in(P, mode, q_t, (hipStream_t)stream);
+        rc = launch_state_in(P, q_t, (hipStream_t)stream);
         if (rc) return rc;
     }
     return session_begin(P, mode, T, nsub, io, (hipStream_t)stream, ghost_series, export_series);
@@ -535,7 +538,7 @@ int rr_stream_begin_unit(rr_plan *P, const double *q_ch, const double *q_full, c
     Rows io; io.dev_in = lateral; io.rows_in = lat_rows; io.dev_out = discharge; io.rows_out = out_rows;
     if (P->ses.open) return fail(RR_E_STATE, "a routing call is already open on this plan (rr_stream_end_unit it first)");
     if (P->unit_general) return fail(RR_E_UNSUPPORTED, "rr_stream_begin_unit: general edge data (rr_plan_set_unit_weights) on a partitioned network is not supported");
-    rc = prepare_call(P, Mode::Unit, T, nsub, false, false, true);
+    rc = prepare_call(P, call_shape(Mode::Unit, T, nsub, io, true), "rr_stream_begin_unit");
     if (rc) return rc;
     if (P->h.n > 0 && T > 0) {
         rc = unit_state_in(P, q_ch, q_full, (hipStream_t)stream);
@@ -572,7 +575,7 @@ int rr_stream_end(rr_plan *P, double *q_t)
     hipStream_t stream = P->ses.stream;
     rc = session_end(P);
     if (rc) return rc;
-    if (P->h.n > 0 && total > 0 && q_t) launch_state_out(P, P->ses.mode, q_t, total, stream);
+    if (P->h.n > 0 && total > 0 && q_t) launch_state_out(P, q_t, total, stream);
     return RR_OK;
 }
 
@@ -601,15 +604,25 @@ int rr_postorder(int64_t n, const int64_t *down_index, int64_t *order)
 
 // ---- device-pointer entry points ----
 
+// The output of a *_dev route call: float64 rows (out_rows of them) or float32 rows, each the mean of `factor` routed rows (prepare_call
+// checks factor).  False unless exactly one of the two arrays is given, and float64 rows have rows.
+static bool dev_output(Rows &io, double *discharge, int64_t out_rows, float *discharge32, int64_t factor, int64_t T)
+{
+    if (discharge32) { io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = factor >= 1 ? T / factor : 0; }
+    else { io.dev_out = discharge; io.rows_out = out_rows; }
+    return (discharge != nullptr) != (discharge32 != nullptr) && (discharge32 || out_rows >= 1);
+}
+
 int rr_rapid_route_dev(rr_plan *P, double *q_t, const double *qlateral, int64_t ql_rows, double *discharge,
                        int64_t out_rows, int64_t T, int64_t nsub, void *stream)
 {
     int rc = check_route_args(P, true, T, nsub);
     if (rc) return rc;
-    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral || !discharge || ql_rows < 1 || out_rows < 1))
+    Rows io; io.dev_in = qlateral; io.rows_in = ql_rows;
+    const bool out = dev_output(io, discharge, out_rows, nullptr, 1, T);
+    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral || ql_rows < 1 || !out))
         return fail(RR_E_INVALID, "rr_rapid_route_dev: null array or empty row count");
-    Rows io; io.dev_in = qlateral; io.rows_in = ql_rows; io.dev_out = discharge; io.rows_out = out_rows;
-    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false);
+    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false, "rr_rapid_route_dev");
 }
 
 int rr_muskingum_route_dev(rr_plan *P, double *q_t, double *discharge, int64_t out_rows, int64_t n_out,
@@ -617,10 +630,11 @@ int rr_muskingum_route_dev(rr_plan *P, double *q_t, double *discharge, int64_t o
 {
     int rc = check_route_args(P, false, n_out, n_per_out);
     if (rc) return rc;
-    if (P->h.n > 0 && n_out > 0 && (!q_t || !discharge || out_rows < 1))
+    Rows io;
+    const bool out = dev_output(io, discharge, out_rows, nullptr, 1, n_out);
+    if (P->h.n > 0 && n_out > 0 && (!q_t || !out))
         return fail(RR_E_INVALID, "rr_muskingum_route_dev: null array or empty row count");
-    Rows io; io.dev_out = discharge; io.rows_out = out_rows;
-    return rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, (hipStream_t)stream, false);
+    return rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, (hipStream_t)stream, false, "rr_muskingum_route_dev");
 }
 
 int rr_unit_route_dev(rr_plan *P, double *q_ch, double *q_full, const double *conv, int64_t conv_rows,
@@ -628,36 +642,26 @@ int rr_unit_route_dev(rr_plan *P, double *q_ch, double *q_full, const double *co
 {
     int rc = check_route_args(P, false, T, nsub);
     if (rc) return rc;
-    if (P->h.n > 0 && T > 0 && (!conv || !discharge || conv_rows < 1 || out_rows < 1 ||
-                                (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
+    Rows io; io.dev_in = conv; io.rows_in = conv_rows;
+    const bool out = dev_output(io, discharge, out_rows, nullptr, 1, T);
+    if (P->h.n > 0 && T > 0 && (!conv || conv_rows < 1 || !out || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
         return fail(RR_E_INVALID, "rr_unit_route_dev: null array or empty row count");
-    Rows io; io.dev_in = conv; io.rows_in = conv_rows; io.dev_out = discharge; io.rows_out = out_rows;
-    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false);
+    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, "rr_unit_route_dev");
 }
 
-// float32 output fused into the record pass (k_rec_out): applies when the call is time-tiled and factor x sub-steps divides
-// the tick-rows of a batch (128); otherwise RR_E_UNSUPPORTED and the caller uses the float64 form + rr_resample_cast_dev.
-static int f32_output_applies(rr_plan *P, Mode mode, int64_t T, int64_t nsub, int64_t factor, bool plain = false, bool uh = false)
-{
-    if (factor < 1 || T % factor != 0) return fail(RR_E_INVALID, "float32 output: the number of rows must be a multiple of factor >= 1");
-    if (kRecRows % (factor * nsub) != 0) return fail(RR_E_UNSUPPORTED, "float32 output: factor x sub-steps must divide the rows of a record batch (128)");
-    const Schedule sch = choose_schedule(P, mode, T, nsub, false, false, plain, 0, 0, true, uh);
-    if (!sch.tiled && !sch.direct) return fail(RR_E_UNSUPPORTED, "float32 output needs the time-tiled kernel or the direct row path, which this call does not get");
-    return RR_OK;
-}
-
+// float32 output fused into the out-pass (k_rec_out, or the direct row path's lanes): applies when the call gets the time-tiled kernel or the
+// direct row path and factor x sub-steps divides the tick-rows of a batch (128); otherwise RR_E_UNSUPPORTED (prepare_call) and the caller
+// uses the float64 form + rr_resample_cast_dev.
 int rr_rapid_route_f32_dev(rr_plan *P, double *q_t, const double *qlateral, int64_t ql_rows, float *discharge32, int64_t T,
                            int64_t nsub, int64_t factor, void *stream)
 {
     int rc = check_route_args(P, true, T, nsub);
     if (rc) return rc;
-    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral || !discharge32 || ql_rows < 1))
+    Rows io; io.dev_in = qlateral; io.rows_in = ql_rows;
+    const bool out = dev_output(io, nullptr, 0, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral || !out || ql_rows < 1))
         return fail(RR_E_INVALID, "rr_rapid_route_f32_dev: null array or empty row count");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    rc = f32_output_applies(P, Mode::Rapid, T, nsub, factor, true);
-    if (rc) return rc;
-    Rows io; io.dev_in = qlateral; io.rows_in = ql_rows; io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor;
-    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false);
+    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false, "rr_rapid_route_f32_dev");
 }
 
 int rr_rapid_route_f32in_dev(rr_plan *P, double *q_t, const float *qlateral32, int64_t ql_rows, double *discharge, int64_t out_rows,
@@ -665,28 +669,21 @@ int rr_rapid_route_f32in_dev(rr_plan *P, double *q_t, const float *qlateral32, i
 {
     int rc = check_route_args(P, true, T, nsub);
     if (rc) return rc;
-    const bool f32 = discharge32 != nullptr;
-    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral32 || ql_rows < 1 || (!discharge && !discharge32) || (discharge && discharge32) || (discharge && out_rows < 1)))
+    Rows io; io.dev_in32 = qlateral32; io.rows_in = ql_rows;
+    const bool out = dev_output(io, discharge, out_rows, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!q_t || !qlateral32 || ql_rows < 1 || !out))
         return fail(RR_E_INVALID, "rr_rapid_route_f32in_dev: null array, empty row count, or both or neither output");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    if (f32) { rc = f32_output_applies(P, Mode::Rapid, T, nsub, factor, true); if (rc) return rc; }
-    else { const Schedule sch = choose_schedule(P, Mode::Rapid, T, nsub, false, false, true); if (!sch.tiled && !sch.direct) return fail(RR_E_UNSUPPORTED, "rr_rapid_route_f32in_dev needs the time-tiled kernel or the direct row path, which this call does not get"); }
-    Rows io; io.dev_in32 = qlateral32; io.dev_in = P->d_c4_params; io.rows_in = ql_rows;      // (dev_in only has to be non-NULL for the executor)
-    if (f32) { io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor; }
-    else { io.dev_out = discharge; io.rows_out = out_rows; }
-    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false);
+    return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false, "rr_rapid_route_f32in_dev");
 }
 
 int rr_muskingum_route_f32_dev(rr_plan *P, double *q_t, float *discharge32, int64_t n_out, int64_t n_per_out, void *stream)
 {
     int rc = check_route_args(P, false, n_out, n_per_out);
     if (rc) return rc;
-    if (P->h.n > 0 && n_out > 0 && (!q_t || !discharge32)) return fail(RR_E_INVALID, "rr_muskingum_route_f32_dev: null array");
-    if (P->h.n == 0 || n_out == 0) return RR_OK;
-    rc = f32_output_applies(P, Mode::Muskingum, n_out, n_per_out, 1, true);
-    if (rc) return rc;
-    Rows io; io.dev_out32 = discharge32; io.out_factor = 1; io.rows_out = n_out;
-    return rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, (hipStream_t)stream, false);
+    Rows io;
+    const bool out = dev_output(io, nullptr, 0, discharge32, 1, n_out);
+    if (P->h.n > 0 && n_out > 0 && (!q_t || !out)) return fail(RR_E_INVALID, "rr_muskingum_route_f32_dev: null array");
+    return rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, (hipStream_t)stream, false, "rr_muskingum_route_f32_dev");
 }
 
 int rr_unit_route_f32_dev(rr_plan *P, double *q_ch, double *q_full, const double *conv, int64_t conv_rows, float *discharge32,
@@ -694,13 +691,11 @@ int rr_unit_route_f32_dev(rr_plan *P, double *q_ch, double *q_full, const double
 {
     int rc = check_route_args(P, false, T, nsub);
     if (rc) return rc;
-    if (P->h.n > 0 && T > 0 && (!conv || !discharge32 || conv_rows < 1 || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
+    Rows io; io.dev_in = conv; io.rows_in = conv_rows;
+    const bool out = dev_output(io, nullptr, 0, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!conv || !out || conv_rows < 1 || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
         return fail(RR_E_INVALID, "rr_unit_route_f32_dev: null array or empty row count");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    rc = f32_output_applies(P, Mode::Unit, T, nsub, factor, true);
-    if (rc) return rc;
-    Rows io; io.dev_in = conv; io.rows_in = conv_rows; io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor;
-    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false);
+    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, "rr_unit_route_f32_dev");
 }
 
 int rr_rapid_route_runoff_dev(rr_plan *P, double *q_t, int64_t n_points, const int32_t *indptr, const int32_t *indices,
@@ -710,19 +705,13 @@ int rr_rapid_route_runoff_dev(rr_plan *P, double *q_t, int64_t n_points, const i
 {
     int rc = check_route_args(P, true, T, 1);
     if (rc) return rc;
-    const bool f32 = discharge32 != nullptr;
-    if (P->h.n > 0 && T > 0 && (!q_t || !indptr || !indices || !weights || !runoff || (!discharge && !discharge32) || (discharge && discharge32)))
+    const RunoffArgs ga{indptr, indices, weights, area, runoff, stride_t, stride_p, (int32_t)flags, runoff_is_f32 ? 1 : 0};
+    Rows io; io.runoff = &ga;      // no lateral rows: the in-pass makes them
+    const bool out = dev_output(io, discharge, T, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!q_t || !indptr || !indices || !weights || !runoff || !out))
         return fail(RR_E_INVALID, "rr_rapid_route_runoff_dev: null array, or both or neither output");
     if (n_points < 0 || stride_t < 0 || stride_p < 0) return fail(RR_E_INVALID, "rr_rapid_route_runoff_dev: negative size or stride");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    if (f32) { rc = f32_output_applies(P, Mode::Rapid, T, 1, factor); if (rc) return rc; }
-    else if (!choose_schedule(P, Mode::Rapid, T, 1, false, false).tiled) return fail(RR_E_UNSUPPORTED, "rr_rapid_route_runoff_dev needs the time-tiled kernel, which this call does not get");
-    RunoffArgs ga{indptr, indices, weights, area, runoff, stride_t, stride_p, (int32_t)flags, runoff_is_f32 ? 1 : 0};
-    Rows io; io.dev_in = P->d_c4_params; io.rows_in = 1;      // (no lateral rows: dev_in only has to be non-NULL for the executor)
-    if (f32) { io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor; }
-    else { io.dev_out = discharge; io.rows_out = T; }
-    io.runoff = &ga;
-    return rapid_like(P, Mode::Rapid, q_t, io, T, 1, (hipStream_t)stream, false);
+    return rapid_like(P, Mode::Rapid, q_t, io, T, 1, (hipStream_t)stream, false, "rr_rapid_route_runoff_dev");
 }
 
 int rr_unit_route_uh_dev(rr_plan *P, double *q_ch, double *q_full, double *q_final, const double *uh_kernel, double *uh_state,
@@ -731,19 +720,12 @@ int rr_unit_route_uh_dev(rr_plan *P, double *q_ch, double *q_full, double *q_fin
 {
     int rc = check_route_args(P, false, T, nsub);
     if (rc) return rc;
-    const bool f32 = discharge32 != nullptr;
-    if (P->h.n > 0 && T > 0 && (!depth || !uh_kernel || !uh_state || (!discharge && !discharge32) || (discharge && discharge32) || n_ks < 1 ||
-                                (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
+    Rows io; io.dev_in = depth; io.rows_in = T; io.uh_kernel = uh_kernel; io.uh_state = uh_state; io.uh_nks = n_ks;
+    const bool out = dev_output(io, discharge, T, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!depth || !uh_kernel || !uh_state || !out || n_ks < 1 || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
         return fail(RR_E_INVALID, "rr_unit_route_uh_dev: null array, both or neither output, or n_ks < 1");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    if (n_ks > kUhFusedMaxTaps) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_dev: more than 64 kernel steps: convolve with rr_uh_convolve_dev, then rr_unit_route_dev");
-    if (f32) { rc = f32_output_applies(P, Mode::Unit, T, nsub, factor, true, true); if (rc) return rc; }
-    else { const Schedule sch = choose_schedule(P, Mode::Unit, T, nsub, false, false, true, 0, 0, false, true); if (!sch.tiled && !sch.direct) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_dev needs the time-tiled kernel or the direct row path, which this call does not get"); }
-    Rows io; io.dev_in = depth; io.rows_in = T;
-    if (f32) { io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor; }
-    else { io.dev_out = discharge; io.rows_out = T; }
-    io.uh_kernel = uh_kernel; io.uh_state = uh_state; io.uh_nks = n_ks;
-    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, q_final, uh_state);
+    if (P->h.n > 0 && T > 0 && n_ks > kUhFusedMaxTaps) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_dev: more than 64 kernel steps: convolve with rr_uh_convolve_dev, then rr_unit_route_dev");
+    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, "rr_unit_route_uh_dev", q_final, uh_state);
 }
 
 int rr_unit_route_uh_f32in_dev(rr_plan *P, double *q_ch, double *q_full, double *q_final, const double *uh_kernel, double *uh_state,
@@ -752,19 +734,12 @@ int rr_unit_route_uh_f32in_dev(rr_plan *P, double *q_ch, double *q_full, double 
 {
     int rc = check_route_args(P, false, T, nsub);
     if (rc) return rc;
-    const bool f32 = discharge32 != nullptr;
-    if (P->h.n > 0 && T > 0 && (!depth32 || !uh_kernel || !uh_state || (!discharge && !discharge32) || (discharge && discharge32) || n_ks < 1 ||
-                                (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
+    Rows io; io.dev_in32 = depth32; io.rows_in = T; io.uh_kernel = uh_kernel; io.uh_state = uh_state; io.uh_nks = n_ks;
+    const bool out = dev_output(io, discharge, T, discharge32, factor, T);
+    if (P->h.n > 0 && T > 0 && (!depth32 || !uh_kernel || !uh_state || !out || n_ks < 1 || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
         return fail(RR_E_INVALID, "rr_unit_route_uh_f32in_dev: null array, both or neither output, or n_ks < 1");
-    if (P->h.n == 0 || T == 0) return RR_OK;
-    if (n_ks > kUhFusedMaxTaps) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_f32in_dev: more than 64 kernel steps: convert the rows, convolve with rr_uh_convolve_dev, then rr_unit_route_dev");
-    if (f32) { rc = f32_output_applies(P, Mode::Unit, T, nsub, factor, true, true); if (rc) return rc; }
-    else { const Schedule sch = choose_schedule(P, Mode::Unit, T, nsub, false, false, true, 0, 0, false, true); if (!sch.tiled && !sch.direct) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_f32in_dev needs the time-tiled kernel or the direct row path, which this call does not get"); }
-    Rows io; io.dev_in32 = depth32; io.dev_in = uh_kernel; io.rows_in = T;      // (dev_in only has to be non-NULL for the executor)
-    if (f32) { io.dev_out32 = discharge32; io.out_factor = factor; io.rows_out = T / factor; }
-    else { io.dev_out = discharge; io.rows_out = T; }
-    io.uh_kernel = uh_kernel; io.uh_state = uh_state; io.uh_nks = n_ks;
-    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, q_final, uh_state);
+    if (P->h.n > 0 && T > 0 && n_ks > kUhFusedMaxTaps) return fail(RR_E_UNSUPPORTED, "rr_unit_route_uh_f32in_dev: more than 64 kernel steps: convert the rows, convolve with rr_uh_convolve_dev, then rr_unit_route_dev");
+    return unit_like(P, q_ch, q_full, io, T, nsub, (hipStream_t)stream, false, "rr_unit_route_uh_f32in_dev", q_final, uh_state);
 }
 
 int rr_uh_convolve_dev(int device, const double *kernel, double *state, const double *lateral, double *out,
@@ -784,7 +759,7 @@ int rr_rapid_route(rr_plan *P, double *q_t, const double *qlateral, double *disc
     if (rc) return rc;
     if (P->h.n > 0 && T > 0 && (!q_t || !qlateral || !discharge)) return fail(RR_E_INVALID, "rr_rapid_route: null array");
     Rows io; io.host_in = qlateral; io.host_out = discharge;
-    rc = rapid_like(P, Mode::Rapid, q_t, io, T, nsub, nullptr, true);
+    rc = rapid_like(P, Mode::Rapid, q_t, io, T, nsub, nullptr, true, "rr_rapid_route");
     if (rc == RR_OK) HIPCHK(hipStreamSynchronize(nullptr));
     return rc;
 }
@@ -795,7 +770,7 @@ int rr_muskingum_route(rr_plan *P, double *q_t, double *discharge, int64_t n_out
     if (rc) return rc;
     if (P->h.n > 0 && n_out > 0 && (!q_t || !discharge)) return fail(RR_E_INVALID, "rr_muskingum_route: null array");
     Rows io; io.host_out = discharge;
-    rc = rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, nullptr, true);
+    rc = rapid_like(P, Mode::Muskingum, q_t, io, n_out, n_per_out, nullptr, true, "rr_muskingum_route");
     if (rc == RR_OK) HIPCHK(hipStreamSynchronize(nullptr));
     return rc;
 }
@@ -808,7 +783,7 @@ int rr_unit_route(rr_plan *P, double *q_ch, double *q_full, const double *conv, 
     if (P->h.n > 0 && T > 0 && (!conv || !discharge || (!P->h.inner_pos.empty() && (!q_ch || !q_full))))
         return fail(RR_E_INVALID, "rr_unit_route: null array");
     Rows io; io.host_in = conv; io.host_out = discharge;
-    rc = unit_like(P, q_ch, q_full, io, T, nsub, nullptr, true);
+    rc = unit_like(P, q_ch, q_full, io, T, nsub, nullptr, true, "rr_unit_route");
     if (rc == RR_OK) HIPCHK(hipStreamSynchronize(nullptr));
     return rc;
 }

@@ -27,6 +27,34 @@ struct Rows {
     const RunoffArgs *runoff = nullptr;
 };
 
+// What a route call hands over, as far as the choice of its kernel is concerned.  Built in two places only -- call_shape (from the
+// call's Rows) and rr_plan_reserve (from its RR_ROWS_* bits) -- so that a reservation and the call it is made for get the same schedule.
+struct CallShape {
+    Mode mode = Mode::Rapid;
+    int64_t T = 0, nsub = 1;
+    bool host = false;           // rows in host arrays (the host-pointer entry points)
+    bool dev_rows = false;       // device rows the direct row path reads as they are: lateral inflow (float64 or float32; none in channel-only routing), or depths (uh)
+    bool in32 = false;           // float32 lateral rows or depths
+    bool out32 = false;          // float32 output rows, each the mean of `factor` routed rows
+    int64_t factor = 1;
+    bool uh = false;             // UnitMuskingum with the unit-hydrograph convolution fused in: the rows are runoff depths
+    bool runoff = false;         // gridded runoff: no lateral rows, the in-pass makes them
+    int64_t ring_in = 0, ring_out = 0;      // streaming calls (rr_stream_begin*): rows of the caller's cyclic lateral / discharge arrays
+};
+
+// streaming k_tick over rows, time-tiled k_tile over records, the direct row path (rr_plan_last_kernel, rr_plan_reserve's info[0])
+enum class Kernel { Tick = RR_KERNEL_TICK, Tile = RR_KERNEL_TILE, Direct = RR_KERNEL_DIRECT };
+
+// The schedule of a call (choose_schedule): its kernel, task length(s) and work memory.
+struct Schedule {
+    Kernel kernel = Kernel::Tick;
+    int64_t KC = 1;                   // record chunks per task (Tile); rows per task / 16 (Direct)
+    int64_t KS = 1;                   // Direct: record chunks per task of the skeleton's launches
+    int64_t chunks = 0;               // chunks of the record ring (Tile), of the skeleton's record ring (Direct)
+    int64_t ring = 0;                 // doubles of P->d_ring: record ring, or the work rows of the streaming kernel
+    int64_t mrows = 0, stage = 0;     // doubles of the intermediate rows (streaming permutation, convolved rows) / of the host staging rows
+};
+
 // One routing call in flight: rows enter (permutation in), ticks run, finished rows leave (permutation out).
 // route_core() runs a session start to finish; the rr_stream_* entry points keep it open between calls so the
 // lag pipeline is never drained while forcing or boundary series arrive in chunks (multi-GPU).
@@ -36,13 +64,14 @@ struct Session {
     int64_t T = 0, nsub = 1, total = 0, total_ticks = 0;
     Rows io;
     hipStream_t stream = nullptr;
-    bool direct = false, has_in = true;
+    Kernel kernel = Kernel::Tick;
+    bool in_place = false;        // Tick: engine order == params order, device rows: the streaming kernel works in the caller's arrays
+    bool has_in = true;
     int64_t ring_rows = 0;
     int64_t rows_loaded = 0, rows_stored = 0, tau = 0;
     const double *ghost_series = nullptr;
     double *export_series = nullptr;
     TickArgs a{};
-    bool wave = false;            // time-tiled k_tile over records instead of per-tick k_tick over rows
     int64_t KC = 1;               // record chunks per task: K = 16 * KC ticks
     int64_t rec_chunks = 0, in_batches = 0, n_in_batches = 0, out_batches = 0, n_out_batches = 0;
     int64_t ticks_stored = 0;     // tick-rows that have left the record ring
@@ -52,7 +81,6 @@ struct Session {
     int64_t ghost_slack = 0, export_skew = 0;      // boundary reaches of a partitioned network in the time-tiled schedule (level skew included)
     TileArgs ta{};
     // direct row path (rr_kernels_direct.hpp): K rows per task, the skeleton behind it on records
-    bool rows_direct = false;
     int64_t n_tasks = 0;          // direct launches: rows [d K, (d + 1) K) in launch d
     int64_t d_done = 0;           // direct launches made
     int64_t KS = 1;               // record chunks per task of the skeleton's launches (KS divides KC; shorter where the part feeds another GPU)
@@ -122,10 +150,10 @@ struct rr_plan {
 
     // time-tiled routing (k_tile): subtree tiles of rr::TilePlan
     rr::TilePlan tp;
-    bool wave_enabled = true, wave_forced = false, wave_now = false, weights_uniform = false;
+    bool wave_enabled = true, wave_forced = false, weights_uniform = false;
     int wave_threads = 512;
     int64_t wave_K = 0;          // ticks per task (multiple of 16); 0 = chosen per call
-    int64_t next_KC = 1, next_KS = 1, next_chunks = 0;   // prepare_call: task length(s) and record ring of the call about to start
+    Schedule sch;                // prepare_call: the schedule of the call about to start (or running, or just ended)
     int64_t kc_cap = int64_t{1} << 20;      // longest task (record chunks) the device had room for; 0: no record ring fits, the plan streams
     TileMeta *d_tmeta = nullptr;     // per tile (rr_kernels_tile.hpp)
     int4 *d_pmeta = nullptr;         // per position {lag | flags, first upstream position, xpos, upstream counts}
@@ -153,7 +181,7 @@ struct rr_plan {
     HostPipe pipe;      // staging of the host-pointer entry points (allocated at first use)
     // direct row path: column-range tiles where the params order numbers small subtrees contiguously (rr_plan.hpp: DirectPlan)
     rr::DirectPlan dp;
-    bool direct_enabled = true, direct_now = false;      // RR_DIRECT=0 (tests): records for every call
+    bool direct_enabled = true;          // RR_DIRECT=0 (tests): records for every call
     bool uh_rows_ok = true;      // false once the device refused the convolved rows of rr_unit_route_uh*_dev on the direct row path: records from then on
     int direct_window = 1;               // rows of the LDS window: largest span + 1 of the plan's tiles
     DirectTile *d_dtiles = nullptr;
@@ -429,28 +457,6 @@ int64_t pick_KC(const rr_plan *P, int64_t total_ticks)
     return total_ticks >= 32768 ? 16 : (total_ticks >= 16384 ? 8 : (total_ticks >= 4096 ? 4 : (total_ticks >= 512 ? 2 : 1)));
 }
 
-// Which routing kernel a call uses.  The time-tiled schedule needs one upstream weight per reach, a network that tiles
-// (rr::TilePlan) and room for its record ring; its fill and drain cost (levels x K) ticks more than the streaming kernel's, a
-// few launches, so only calls of a handful of sub-steps stream.  RR_WAVE=1 forces it where it applies, RR_WAVE=0 forbids it.
-//
-// Records are indexed by tick = tick-row + lag, modulo the ring, per position: a position's slots never hold another
-// position's data, so what the ring must cover is one position's tick-rows in flight.  Rows enter for all columns at once
-// (ahead of the level-0 tiles) and leave for all columns at once (after the last level has passed their tick + depth), so
-// every position keeps depth + levels * K tick-rows plus the batching of the two permutation passes; that its window sits
-// lag ticks later than a headwater's does not widen it.  The ring may take five eighths of the card; a deep network that
-// does not fit gets shorter tasks, then the streaming kernel.
-//
-// The choice is a pure function of the plan, the call's shape and kc_cap (lowered only when the device refuses an
-// allocation), so rr_plan_reserve and the call it prepares for agree on it.
-struct Schedule {
-    bool direct = false;              // direct row path: KC = rows per task / 16, chunks / ring = the skeleton's record ring
-    int64_t KS = 1;                   // direct row path: record chunks per task of the skeleton's launches
-    bool tiled = false;
-    int64_t KC = 1, chunks = 0;       // time-tiled: record chunks per task, chunks of the record ring
-    int64_t ring = 0;                 // doubles of P->d_ring: record ring, or the work rows of the streaming kernel
-    int64_t mrows = 0, stage = 0;     // streaming kernel: doubles of the permutation's intermediate rows / of the host staging rows
-};
-
 // Rows per task of the direct path: a task costs its tile `span` ticks of fill and drain (lanes start one after the other: 10 % at
 // 512 rows, 5 % at 1,024).  The skeleton's tasks are cut separately (Schedule::KS, direct_KS below): every tile level of the skeleton costs
 // one of ITS tasks of pipeline and of record ring, so long lane tasks over short skeleton tasks have both -- the year at 1M reaches
@@ -464,11 +470,44 @@ int64_t pick_direct_K(const rr_plan *P, int64_t T)
 }
 int64_t direct_KS(int64_t task_chunks, int64_t total_ticks)      // record chunks per skeleton task: 512 ticks in long calls, 128 in short ones; divides the lanes' task
 {
-    int64_t ks = std::min<int64_t>(task_chunks, (total_ticks >= 16384 ? 512 : 128) / kRec);
-    while (task_chunks % ks) --ks;
+    int64_t ks = std::max<int64_t>(1, std::min<int64_t>(task_chunks, (total_ticks >= 16384 ? 512 : 128) / kRec));
+    while (ks > 1 && task_chunks % ks) --ks;
     return ks;
 }
 
+// The shape of a route call (stream: rr_stream_begin*, whose rows arrive over rr_stream_advance in the caller's rings).  The direct row
+// path reads device rows as they are, but not gridded runoff, and not a UnitMuskingum stream (rr_stream_begin_unit keeps to records, and
+// engine.Plan.stream_begin_unit reserves for them).
+CallShape call_shape(Mode mode, int64_t T, int64_t nsub, const Rows &io, bool stream = false)
+{
+    CallShape s;
+    s.mode = mode; s.T = T; s.nsub = nsub;
+    s.host = io.host_in != nullptr || io.host_out != nullptr;
+    s.dev_rows = !s.host && !io.runoff && !(stream && mode == Mode::Unit);
+    s.in32 = io.dev_in32 != nullptr;
+    s.out32 = io.dev_out32 != nullptr; s.factor = io.out_factor;
+    s.uh = io.uh_kernel != nullptr;
+    s.runoff = io.runoff != nullptr;
+    if (stream) { s.ring_in = mode == Mode::Muskingum ? 0 : io.rows_in; s.ring_out = io.rows_out; }
+    return s;
+}
+
+// Which routing kernel a call uses.  The time-tiled schedule needs one upstream weight per reach, a network that tiles
+// (rr::TilePlan) and room for its record ring; its fill and drain cost (levels x K) ticks more than the streaming kernel's, a
+// few launches, so only calls of a handful of sub-steps stream.  RR_WAVE=1 forces it where it applies, RR_WAVE=0 forbids it.
+//
+// Records are indexed by tick = tick-row + lag, modulo the ring, per position: a position's slots never hold another
+// position's data, so what the ring must cover is one position's tick-rows in flight.  Rows enter for all columns at once
+// (ahead of the level-0 tiles) and leave for all columns at once (after the last level has passed their tick + depth), so
+// every position keeps depth + levels * K tick-rows plus the batching of the two permutation passes; that its window sits
+// lag ticks later than a headwater's does not widen it.  The ring may take five eighths of the card; a deep network that
+// does not fit gets shorter tasks, then the streaming kernel.
+//
+// The choice is a pure function of the plan, the call's shape and kc_cap (lowered only when the device refuses an
+// allocation), so rr_plan_reserve and the call it prepares for agree on it.
+//
+// host (the host-pointer entry points): the rows reach the time-tiled kernel through the PCIe pipeline's device rings (reserve_core
+// prepares it); where that kernel does not apply they are routed chunk by chunk by the streaming kernel through staging rows.
 // ring_in / ring_out (streaming calls, rr_stream_begin): rows of the caller's cyclic lateral / discharge arrays where those are shorter
 // than the call (0: they hold every row).  A caller may refill such a ring between two rr_stream_advance calls, so a direct task must
 // not span more rows than the ring holds: K is capped (a ring of fewer than 32 rows keeps to records, which take rows in batches of 128
@@ -478,45 +517,47 @@ int64_t direct_KS(int64_t task_chunks, int64_t total_ticks)      // record chunk
 // uh (rr_unit_route_uh*_dev: runoff depths + unit-hydrograph kernel): on the direct row path the convolution runs first, as a pass of its own
 // into T rows of work memory (mrows) that the lanes then read -- the reference's own two steps (UnitMuskingum.py:72-98) -- where those rows
 // fit a third of the card; otherwise the call keeps to records with the convolution fused into the in-pass.
-Schedule choose_schedule(const rr_plan *P, Mode mode, int64_t T, int64_t nsub, bool force_streaming, bool host_io, bool plain_rows = false,
-                         int64_t ring_in = 0, int64_t ring_out = 0, bool out32 = false, bool uh = false)
+Schedule choose_schedule(const rr_plan *P, const CallShape &s)
 {
     Schedule sch;
-    const int64_t total = T * nsub, dmax = P->h.depth - 1, n = P->h.n;
+    const Mode mode = s.mode;
+    const int64_t T = s.T, nsub = s.nsub, total = T * nsub, dmax = P->h.depth - 1, n = P->h.n;
     // The direct row path: RapidMuskingum, one sub-step per row, float64 rows in device arrays, one weight per reach -- the
     // headline's call -- on a params order that numbers small subtrees contiguously (boundary reaches of a partitioned network
     // included: rr_plan_set_boundary lays the direct plan out around them).
     // Sub-steps (up to kDirectMaxSub a row) and channel-only routing take it too; with sub-steps only without boundary ghosts.  UnitMuskingum: below.
     // UnitMuskingum (float64 rows of convolved lateral inflow, no boundary reaches) takes it as well.
     const bool unit_direct = mode == Mode::Unit && nsub <= kDirectMaxSub && P->n_ghost == 0 && P->n_export == 0 && !P->unit_general && P->tp.ok &&
-                             (!uh || (P->uh_rows_ok && (P->dev_total_bytes == 0 || T * n * 8 <= (int64_t)(P->dev_total_bytes / 3))));
-    if (plain_rows && P->direct_enabled && P->dp.ok && (mode == Mode::Rapid || mode == Mode::Muskingum || unit_direct) && nsub <= kDirectMaxSub && (nsub == 1 || P->n_ghost == 0) &&
-        P->weights_uniform && !force_streaming && !host_io && P->wave_enabled && total >= 8 && n < (int64_t{1} << 29)) {
+                             (!s.uh || (P->uh_rows_ok && (P->dev_total_bytes == 0 || T * n * 8 <= (int64_t)(P->dev_total_bytes / 3))));
+    if (s.dev_rows && P->direct_enabled && P->dp.ok && (mode != Mode::Unit || unit_direct) && nsub <= kDirectMaxSub && (nsub == 1 || P->n_ghost == 0) &&
+        P->weights_uniform && P->wave_enabled && total >= 8 && n < (int64_t{1} << 29)) {
         int64_t K = pick_direct_K(P, T);
         const int64_t levels = P->dp.skel.n_levels, np = P->dp.skel.np;
-        if (ring_in > 0 && ring_in < T) K = std::min(K, ring_in / kRec * kRec);
-        if (ring_out > 0 && ring_out < T) K = std::min(K, ring_out / kRec * kRec);
-        if (out32) K = std::max<int64_t>(kRecRows, K / kRecRows * kRecRows);
-        sch.direct = true; sch.KC = K / kRec;
-        // The skeleton's own tasks are shorter than the lanes' (several of the skeleton's launches per direct launch; a direct task is K rows =
-        // K nsub ticks): see pick_direct_K -- and 64 ticks in a part that feeds another GPU, whose boundary series every level delays by one
-        // task (as kc_long below).  KS divides KC nsub.
-        sch.KS = direct_KS(sch.KC * nsub, total);
-        if (P->n_export > 0 && P->wave_K <= 0) for (sch.KS = std::min<int64_t>(sch.KC * nsub, 4); (sch.KC * nsub) % sch.KS; --sch.KS) {}
-        if (np > 0) {      // a record lives from the launch that forwards its first row to the out-pass behind the skeleton's last level
-            // a ring cut to the call's length: with boundary ghosts it has to hold their in-pass's batches whole -- k_rec_in writes nine records per position and
-            // batch, zeros past the call's end, and in a ring shorter than that a batch wrapped onto its own first records (a 40- or 130-row call of a shallow part:
-            // wrong boundary inflow; a 200-row call: the last batch waited for its own slots for ever -- both found by profiles/microbench/parts_fuzz.py)
-            int64_t whole_call = (total + dmax) / kRec + 2;
-            if (P->n_ghost > 0) whole_call = std::max<int64_t>(whole_call, kRecBatch * ((total + 14) / kRecRows + 1) + (dmax >> 4) + 2);
-            sch.chunks = std::min<int64_t>((levels * sch.KS * kRec + 2 * K * nsub + 2 * dmax + kRecRows + 2 * kRec) / kRec + 2, whole_call);
-            sch.ring = sch.chunks * kRec * np;
+        if (s.ring_in > 0 && s.ring_in < T) K = std::min(K, s.ring_in / kRec * kRec);
+        if (s.ring_out > 0 && s.ring_out < T) K = std::min(K, s.ring_out / kRec * kRec);
+        if (s.out32) K = std::max<int64_t>(kRecRows, K / kRecRows * kRecRows);
+        if (K >= 2 * kRec) {      // (a shorter task -- a ring of fewer than 32 rows -- keeps to records)
+            sch.kernel = Kernel::Direct; sch.KC = K / kRec;
+            // The skeleton's own tasks are shorter than the lanes' (several of the skeleton's launches per direct launch; a direct task is K rows =
+            // K nsub ticks): see pick_direct_K -- and 64 ticks in a part that feeds another GPU, whose boundary series every level delays by one
+            // task (as kc_long below).  KS divides KC nsub.
+            sch.KS = direct_KS(sch.KC * nsub, total);
+            if (P->n_export > 0 && P->wave_K <= 0) for (sch.KS = std::min<int64_t>(sch.KC * nsub, 4); (sch.KC * nsub) % sch.KS; --sch.KS) {}
+            if (np > 0) {      // a record lives from the launch that forwards its first row to the out-pass behind the skeleton's last level
+                // a ring cut to the call's length: with boundary ghosts it has to hold their in-pass's batches whole -- k_rec_in writes nine records per position and
+                // batch, zeros past the call's end, and in a ring shorter than that a batch wrapped onto its own first records (a 40- or 130-row call of a shallow part:
+                // wrong boundary inflow; a 200-row call: the last batch waited for its own slots for ever -- both found by profiles/microbench/parts_fuzz.py)
+                int64_t whole_call = (total + dmax) / kRec + 2;
+                if (P->n_ghost > 0) whole_call = std::max<int64_t>(whole_call, kRecBatch * ((total + 14) / kRecRows + 1) + (dmax >> 4) + 2);
+                sch.chunks = std::min<int64_t>((levels * sch.KS * kRec + 2 * K * nsub + 2 * dmax + kRecRows + 2 * kRec) / kRec + 2, whole_call);
+                sch.ring = sch.chunks * kRec * np;
+            }
+            if (s.uh) sch.mrows = T * n;      // the convolved rows
+            if (np < (int64_t{1} << 25) && (P->dev_total_bytes == 0 || sch.ring * 8 <= (int64_t)(P->dev_total_bytes / 2))) return sch;
+            sch = Schedule();
         }
-        if (uh) sch.mrows = T * n;      // the convolved rows
-        if (K >= 2 * kRec && np < (int64_t{1} << 25) && (P->dev_total_bytes == 0 || sch.ring * 8 <= (int64_t)(P->dev_total_bytes / 2))) return sch;
-        sch = Schedule();
     }
-    bool ok = P->wave_enabled && P->tp.ok && P->weights_uniform && n > 0 && !force_streaming && P->tp.np < (int64_t{1} << 25) &&
+    bool ok = P->wave_enabled && P->tp.ok && P->weights_uniform && n > 0 && P->tp.np < (int64_t{1} << 25) &&
               !P->export_inside && P->kc_cap >= 1 && !(mode == Mode::Unit && P->unit_general);
     if (ok && !P->wave_forced) ok = total >= 32;
     if (ok) {
@@ -535,17 +576,17 @@ Schedule choose_schedule(const rr_plan *P, Mode mode, int64_t T, int64_t nsub, b
             // keeps depth x n work rows itself (1M reaches 24k deep: 204 GB of records at K = 16 against 192 GB of rows)
             if (P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 16 * (KC == 1 ? 13 : 10))) continue;
             if (KC > 4 && P->wave_K <= 0 && P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 5)) continue;      // long tasks only while the ring stays under a fifth of the card
-            sch.tiled = true; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np;
+            sch.kernel = Kernel::Tile; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np;
             ok = true;
             break;
         }
     }
     if (!ok) {      // streaming kernel: lateral rows come in, discharge rows overwrite them in place and stay until the outlet-most reaches have passed them
         const int64_t C = std::max<int64_t>(1, P->chunk_rows), lag_rows = (dmax + nsub - 1) / std::max<int64_t>(1, nsub);
-        const bool direct = P->h.identity && !host_io;
-        sch.ring = direct ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2) * n;
-        sch.mrows = direct ? 0 : C * n;
-        sch.stage = host_io ? C * n : 0;
+        const bool in_place = P->h.identity && !s.host;
+        sch.ring = in_place ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2) * n;
+        sch.mrows = in_place ? 0 : C * n;
+        sch.stage = s.host ? C * n : 0;
     }
     return sch;
 }
@@ -554,63 +595,63 @@ int host_pipe_prepare(rr_plan *P);
 
 // Sizes and allocates what a call of this shape works in.  The only place on a route call's path that allocates: the
 // host-pointer entry points come here by themselves, the *_dev ones expect rr_plan_reserve to have been here.
-int reserve_core(rr_plan *P, Mode mode, int64_t T, int64_t nsub, bool force_streaming, bool host_io, Schedule *out, bool plain_rows = false, bool out32 = false, bool uh = false)
+int reserve_core(rr_plan *P, const CallShape &s, Schedule *out)
 {
-    if (P->h.n == 0 || T <= 0) { if (out) *out = Schedule(); return RR_OK; }
+    if (P->h.n == 0 || s.T <= 0) { *out = Schedule(); return RR_OK; }
     Schedule sch;
     for (;;) {
-        sch = choose_schedule(P, mode, T, nsub, force_streaming, host_io, plain_rows, 0, 0, out32, uh);
-        if (sch.direct && uh && ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows) != RR_OK) {      // no room for the convolved rows: the fused form on records
+        sch = choose_schedule(P, s);
+        if (sch.kernel == Kernel::Direct && s.uh && ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows) != RR_OK) {      // no room for the convolved rows: the fused form on records
             (void)hipGetLastError();
             P->uh_rows_ok = false;
             continue;
         }
         if (ensure_cap(&P->d_ring, &P->ring_cap, sch.ring) == RR_OK) break;
         (void)hipGetLastError();
-        if (sch.direct) return fail(RR_E_ALLOC, "route: the skeleton's record ring does not fit on the device");
-        if (!sch.tiled) return fail(RR_E_ALLOC, "route: the work rows of the streaming kernel do not fit on the device");
+        if (sch.kernel == Kernel::Direct) return fail(RR_E_ALLOC, "route: the skeleton's record ring does not fit on the device");
+        if (sch.kernel == Kernel::Tick) return fail(RR_E_ALLOC, "route: the work rows of the streaming kernel do not fit on the device");
         P->kc_cap = sch.KC / 2;      // shorter tasks, a smaller ring; 0: this plan streams
     }
     int rc = ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows);
     if (!rc) rc = ensure_cap(&P->d_stage, &P->stage_cap, sch.stage);
-    if (!rc && !sch.tiled && !sch.direct && !P->perm_ready) rc = upload_tiled_permutations(P);
-    if (!rc && sch.tiled && host_io) rc = host_pipe_prepare(P);
+    if (!rc && sch.kernel == Kernel::Tick && !P->perm_ready) rc = upload_tiled_permutations(P);
+    if (!rc && sch.kernel == Kernel::Tile && s.host) rc = host_pipe_prepare(P);
     if (rc) return rc;
     // events: first / last of a call, the sampled launches (rr_plan_set_options), the second stream's
     if (!P->ev_first) { HIPCHK(hipEventCreate(&P->ev_first)); HIPCHK(hipEventCreate(&P->ev_last)); }
-    const int64_t K = sch.KC * kRec, total_ticks = T * nsub + P->h.depth - 1;
+    const int64_t K = sch.KC * kRec, total_ticks = s.T * s.nsub + P->h.depth - 1;
     size_t samples = P->sample_every >= kSampleGroup ? (size_t)std::min<int64_t>(4096, total_ticks / P->sample_every + 1) : 0;
-    if (sch.tiled && samples > 0) samples = (size_t)std::min<int64_t>(4096, ((total_ticks + K - 1) / K + P->tp.n_levels) / 4 + 1);
-    if (sch.direct && samples > 0) samples = (size_t)std::min<int64_t>(4096, (T + K - 1) / K + 1);      // every direct launch
+    if (sch.kernel == Kernel::Tile && samples > 0) samples = (size_t)std::min<int64_t>(4096, ((total_ticks + K - 1) / K + P->tp.n_levels) / 4 + 1);
+    if (sch.kernel == Kernel::Direct && samples > 0) samples = (size_t)std::min<int64_t>(4096, (s.T + K - 1) / K + 1);      // every direct launch
     while (P->ev.size() < 2 * samples) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); P->ev.push_back(e); }
     if (samples > 0) while (P->aux_ev.size() < 2 * rr_plan::kAuxSamples) { hipEvent_t e; HIPCHK(hipEventCreate(&e)); P->aux_ev.push_back(e); }
-    if (out) *out = sch;
+    *out = sch;
     return RR_OK;
 }
 
-// The schedule of the call about to start.  strict (the *_dev entry points, which only enqueue): everything must have been
-// reserved; otherwise it is reserved here.
-int prepare_call(rr_plan *P, Mode mode, int64_t T, int64_t nsub, bool force_streaming, bool host_io, bool strict, bool plain_rows = false,
-                 int64_t ring_in = 0, int64_t ring_out = 0, bool out32 = false, bool uh = false)
+// The schedule of the call about to start, kept on the plan for the call (P->sch).  The host-pointer entry points, which synchronise
+// anyway, reserve here; the others only enqueue, so everything must have been reserved (rr_plan_reserve).  Float32 rows, the fused
+// convolution and gridded runoff are parts of the record passes and of the direct row path: a call with any of them that would
+// stream is refused (RR_E_UNSUPPORTED; `who` names the entry point).
+int prepare_call(rr_plan *P, const CallShape &s, const char *who)
 {
-    Schedule sch;
-    if (!strict) {
-        int rc = reserve_core(P, mode, T, nsub, force_streaming, host_io, &sch, plain_rows, out32, uh);
-        if (rc) return rc;
-    } else {
-        sch = choose_schedule(P, mode, T, nsub, force_streaming, host_io, plain_rows, ring_in, ring_out, out32, uh);
-        const size_t samples = P->sample_every >= kSampleGroup ? 1 : 0;
-        if (P->h.n > 0 && T > 0 && (sch.ring > P->ring_cap || sch.mrows > P->mrows_cap || sch.stage > P->stage_cap || !P->ev_first || P->ev.size() < 2 * samples ||
-                                    (!sch.tiled && !sch.direct && !P->perm_ready && sch.mrows > 0)))
-            return fail(RR_E_STATE, "this call needs " + std::to_string((sch.ring + sch.mrows + sch.stage) * 8) + " bytes of work memory on the device (" +
-                                        std::to_string((P->ring_cap + P->mrows_cap + P->stage_cap) * 8) + " reserved): call rr_plan_reserve(plan, mode, " +
-                                        std::to_string(T) + ", " + std::to_string(nsub) + ", ...) first; the *_dev entry points only enqueue work");
-    }
-    P->wave_now = sch.tiled; P->direct_now = sch.direct; P->next_KC = sch.KC; P->next_KS = sch.KS; P->next_chunks = sch.chunks;
+    if (s.host) return reserve_core(P, s, &P->sch);
+    if (s.out32 && (s.factor < 1 || s.T % s.factor != 0))
+        return fail(RR_E_INVALID, std::string(who) + ": float32 output: the number of rows must be a multiple of factor >= 1");
+    if (s.out32 && kRecRows % (s.factor * s.nsub) != 0)
+        return fail(RR_E_UNSUPPORTED, std::string(who) + ": float32 output: factor x sub-steps must divide the rows of a record batch (128)");
+    const Schedule sch = choose_schedule(P, s);
+    if ((s.in32 || s.out32 || s.uh || s.runoff) && sch.kernel == Kernel::Tick)
+        return fail(RR_E_UNSUPPORTED, std::string(who) + " needs the time-tiled kernel or the direct row path, which this call does not get");
+    const size_t samples = P->sample_every >= kSampleGroup ? 1 : 0;
+    if (P->h.n > 0 && s.T > 0 && (sch.ring > P->ring_cap || sch.mrows > P->mrows_cap || sch.stage > P->stage_cap || !P->ev_first || P->ev.size() < 2 * samples ||
+                                  (sch.kernel == Kernel::Tick && !P->perm_ready && sch.mrows > 0)))
+        return fail(RR_E_STATE, "this call needs " + std::to_string((sch.ring + sch.mrows + sch.stage) * 8) + " bytes of work memory on the device (" +
+                                    std::to_string((P->ring_cap + P->mrows_cap + P->stage_cap) * 8) + " reserved): call rr_plan_reserve(plan, mode, " +
+                                    std::to_string(s.T) + ", " + std::to_string(s.nsub) + ", ...) first; the *_dev entry points only enqueue work");
+    P->sch = sch;
     return RR_OK;
 }
-
-bool use_wave(const rr_plan *P, Mode) { return P->wave_now; }
 
 // The record passes run on the caller's stream between the routing launches.  (On a second stream beside them they slow the
 // routing launch down by what they gain: 395 against 388 ms per year, slower on small networks too --
@@ -634,9 +675,8 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         return fail(RR_E_UNSUPPORTED, "more than 2^31 routing ticks or rows in one call: split it into several calls");
     S.has_in = mode != Mode::Muskingum;
     const bool host_io = io.host_out != nullptr || io.host_in != nullptr;
-    S.rows_direct = P->direct_now;
-    S.wave = use_wave(P, mode) && !S.rows_direct;
-    S.direct = H.identity && !host_io && !S.wave && !S.rows_direct;   // engine order == params order: the streaming kernel reads the caller's arrays
+    S.kernel = P->sch.kernel;
+    S.in_place = H.identity && !host_io && S.kernel == Kernel::Tick;
     const int64_t C = std::max<int64_t>(1, P->chunk_rows);
 
     P->prof_launches = P->prof_samples = P->prof_brackets = 0;
@@ -649,18 +689,16 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     if (n == 0 || S.total == 0) return RR_OK;
     if (P->n_ghost > 0 && !ghost_series) { S.open = false; return fail(RR_E_INVALID, "plan has ghost reaches but no ghost series was given"); }
     if (P->n_export > 0 && !export_series) { S.open = false; return fail(RR_E_INVALID, "plan has export reaches but no export series was given"); }
-    if (io.dev_out32 && !S.wave && !S.rows_direct) { S.open = false; return fail(RR_E_UNSUPPORTED, "float32 output needs the time-tiled kernel or the direct row path"); }
 
-    if (S.wave || S.rows_direct) { S.KC = P->next_KC; S.rec_chunks = P->next_chunks; }     // ring sized by choose_schedule, allocated by rr_plan_reserve
-    if (S.rows_direct) {
-        if (io.uh_kernel || io.runoff || (S.has_in && !io.dev_in && !io.dev_in32) || (!io.dev_out && !io.dev_out32) || (mode == Mode::Unit && (io.dev_in32 || P->n_ghost > 0 || P->n_export > 0)) || nsub > kDirectMaxSub ||
+    S.KC = P->sch.KC; S.KS = P->sch.KS; S.rec_chunks = P->sch.chunks;     // ring sized by choose_schedule, allocated by rr_plan_reserve
+    if (S.kernel == Kernel::Direct) {
+        if (io.uh_kernel || io.runoff || (!io.dev_out && !io.dev_out32) || (mode == Mode::Unit && (io.dev_in32 || P->n_ghost > 0 || P->n_export > 0)) || nsub > kDirectMaxSub ||
             (io.dev_out32 && (io.out_factor < 1 || (S.KC * kRec) % io.out_factor != 0 || T % io.out_factor != 0))) {
             S.open = false;
-            return fail(RR_E_STATE, "route: the direct row path was chosen for a call it does not take");      // (choose_schedule's plain_rows / out32)
+            return fail(RR_E_STATE, "route: the direct row path was chosen for a call it does not take");      // (choose_schedule: dev_rows / out32)
         }
         const rr::TilePlan &TP = P->dp.skel;
         const int64_t K = S.KC * kRec;
-        S.KS = std::max<int64_t>(1, P->next_KS);
         S.n_tasks = (S.T + K - 1) / K;
         S.n_macro = (S.total_ticks + S.KS * kRec - 1) / (S.KS * kRec);      // of the skeleton's launches
         S.n_diags = TP.n_tiles > 0 ? S.n_macro + TP.n_levels - 1 : 0;
@@ -687,12 +725,9 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         TileArgs &w = S.ta;      // the skeleton's k_tile launches
         w.tiles = P->d_ktmeta; w.pos = P->d_kpmeta; w.coef = P->d_kcoef;
         w.sq = P->d_ksq; w.ss = P->d_kss; w.si = P->d_ksi; w.sqch = P->d_ksqch;
-        w.exports = export_series; w.n_export = (int32_t)P->n_export;
-        w.rec = P->d_ring; w.rec_chunks = Div32((uint32_t)std::max<int64_t>(1, S.rec_chunks));
-        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KS; w.n_macro = (int32_t)S.n_macro; w.total = (int32_t)S.total;
-        w.has_lat = S.has_in ? 1 : 0; w.nsub = Div32((uint32_t)nsub); w.inv_nsub = 1.0 / (double)nsub;
+        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KS;
     }
-    if (S.wave) {
+    if (S.kernel == Kernel::Tile) {
         const rr::TilePlan &TP = P->tp;
         const int64_t K = S.KC * kRec;
         S.n_macro = (S.total_ticks + K - 1) / K;
@@ -705,34 +740,34 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         S.ghost_slack = P->ghost_reach.empty() ? 0 : S.total_ticks + (int64_t)TP.n_levels * K;
         for (int32_t i : P->ghost_reach) { const int32_t p = TP.inv[i]; S.ghost_slack = std::min<int64_t>(S.ghost_slack, (int64_t)TP.tile_level[TP.tile_of[p]] * K + (TP.lag[p] & kLagMask)); }
         for (int32_t i : P->export_reach) { const int32_t p = TP.inv[i]; S.export_skew = std::max<int64_t>(S.export_skew, (int64_t)TP.tile_level[TP.tile_of[p]] * K + (TP.lag[p] & kLagMask)); }
-        if (io.dev_out32) {
-            const int64_t step = io.out_factor * nsub;
-            if (io.out_factor < 1 || kRecRows % step != 0 || T % io.out_factor != 0) { S.open = false; return fail(RR_E_UNSUPPORTED, "float32 output: factor * sub-steps must divide the rows of a record batch (128) and factor the number of rows"); }
-        }
         TileArgs &w = S.ta;
         w.tiles = P->d_tmeta; w.pos = P->d_pmeta; w.coef = P->d_coef;
         w.sq = P->d_sq; w.ss = P->d_ss; w.si = P->d_si; w.sqch = P->d_sqch;
+        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KC;
+    }
+    if (S.kernel != Kernel::Tick) {      // the rest of the k_tile launches' arguments, the plan's tiles' or the skeleton's
+        TileArgs &w = S.ta;
         w.exports = export_series; w.n_export = (int32_t)P->n_export;
         w.rec = P->d_ring; w.rec_chunks = Div32((uint32_t)S.rec_chunks);
-        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KC; w.n_macro = (int32_t)S.n_macro; w.total = (int32_t)S.total;
+        w.n_macro = (int32_t)S.n_macro; w.total = (int32_t)S.total;
         w.has_lat = S.has_in ? 1 : 0; w.nsub = Div32((uint32_t)nsub); w.inv_nsub = 1.0 / (double)nsub;
     }
-    if (getenv("RR_VERBOSE") && S.rows_direct)
+    if (getenv("RR_VERBOSE") && S.kernel == Kernel::Direct)
         fprintf(stderr, "rr: n=%lld T=%lld direct rows: K=%lld tiles=%d window=%d holes=%lld outlets=%lld; skeleton: positions=%lld tiles=%d levels=%d ring_chunks=%lld (%.1f GB)\n",
                 (long long)n, (long long)T, (long long)(S.KC * kRec), P->dp.n_tiles, P->direct_window, (long long)P->dp.n_holes, (long long)P->dp.n_exports,
                 (long long)P->dp.skel.np, P->dp.skel.n_tiles, P->dp.skel.n_levels, (long long)S.rec_chunks, (double)S.rec_chunks * kRec * P->dp.skel.np * 8 / 1e9);
     else if (getenv("RR_VERBOSE"))
         fprintf(stderr, "rr: n=%lld T=%lld nsub=%lld tiled=%d K=%lld tiles=%d levels=%d block=%d ghosts=%lld ring_chunks=%lld (%.1f GB) lds=%zu\n",
-                (long long)n, (long long)T, (long long)nsub, (int)S.wave, (long long)(S.KC * kRec), P->tp.n_tiles, P->tp.n_levels, P->tp.block,
-                (long long)P->tp.n_ghost, (long long)S.rec_chunks, S.wave ? (double)S.rec_chunks * kRec * P->tp.np * 8 / 1e9 : 0.0,
+                (long long)n, (long long)T, (long long)nsub, (int)(S.kernel == Kernel::Tile), (long long)(S.KC * kRec), P->tp.n_tiles, P->tp.n_levels, P->tp.block,
+                (long long)P->tp.n_ghost, (long long)S.rec_chunks, S.kernel == Kernel::Tile ? (double)S.rec_chunks * kRec * P->tp.np * 8 / 1e9 : 0.0,
                 tile_lds_bytes(P->wave_threads));
-    if (!S.wave && !S.rows_direct) {
+    if (S.kernel == Kernel::Tick) {
         // work ring in engine order: lateral rows come in, discharge rows overwrite them in place; rows stay until the
         // outlet-most reaches have passed them
         const int64_t lag_rows = (dmax + nsub - 1) / nsub;
-        S.ring_rows = S.direct ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2);
+        S.ring_rows = S.in_place ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2);
         if (S.ring_rows > 0xFFFFFFFFLL || T > 0x7FFFFFFFLL) { S.open = false; return fail(RR_E_INVALID, "route: too many time rows"); }
-        if (S.ring_rows * n > P->ring_cap || (!S.direct && C * n > P->mrows_cap) || (host_io && C * n > P->stage_cap)) {      // prepare_call sized them
+        if (S.ring_rows * n > P->ring_cap || (!S.in_place && C * n > P->mrows_cap) || (host_io && C * n > P->stage_cap)) {      // prepare_call sized them
             S.open = false;
             return fail(RR_E_STATE, "route: work rows of the streaming kernel were not reserved");
         }
@@ -742,7 +777,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         a.isum = P->d_isum; a.bidx = P->d_bidx;
         a.ghost = ghost_series; a.exports = export_series; a.n_ghost = (int32_t)P->n_ghost; a.n_export = (int32_t)P->n_export;
         a.total_substeps = S.total; a.nsub = Div32((uint32_t)nsub); a.inv_nsub = 1.0 / (double)nsub;
-        if (S.direct) {
+        if (S.in_place) {
             a.in = io.dev_in; a.in_ld = n; a.in_rows = Div32((uint32_t)std::max<int64_t>(1, io.rows_in));
             a.out = io.dev_out; a.out_ld = n; a.out_rows = Div32((uint32_t)io.rows_out);
         } else {
@@ -751,8 +786,8 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         }
     }
     S.max_samples = P->sample_every >= kSampleGroup ? (size_t)std::min<int64_t>(4096, S.total_ticks / P->sample_every + 1) : 0;
-    if (S.wave && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_diags / 4 + 1);     // every fourth launch
-    if (S.rows_direct && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_tasks);            // every direct launch
+    if (S.kernel == Kernel::Tile && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_diags / 4 + 1);     // every fourth launch
+    if (S.kernel == Kernel::Direct && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_tasks);            // every direct launch
     S.max_samples = std::min(S.max_samples, P->ev.size() / 2);      // events are made by rr_plan_reserve, never here
     if (!P->ev_first) { S.open = false; return fail(RR_E_STATE, "route: the plan's events were not reserved"); }
     HIPCHK(hipEventRecord(P->ev_first, stream));
@@ -778,7 +813,7 @@ void permute_rows(rr_plan *P, int which, const RowView &src, const RowView &dst,
 int session_load_rows(rr_plan *P, int64_t r0, int64_t r1)   // params order -> ring
 {
     Session &S = P->ses;
-    if (S.direct || !S.has_in) return RR_OK;
+    if (S.in_place || !S.has_in) return RR_OK;
     const int64_t n = P->h.n, C = std::max<int64_t>(1, P->chunk_rows);
     const int nrows = (int)(r1 - r0);
     const RowView ring_view{P->d_ring, n, 0, (uint32_t)std::max<int64_t>(1, S.ring_rows)};
@@ -796,7 +831,7 @@ int session_load_rows(rr_plan *P, int64_t r0, int64_t r1)   // params order -> r
 int session_store_rows(rr_plan *P, int64_t r0, int64_t r1)   // ring -> params order
 {
     Session &S = P->ses;
-    if (S.direct) return RR_OK;
+    if (S.in_place) return RR_OK;
     const int64_t n = P->h.n, C = std::max<int64_t>(1, P->chunk_rows);
     const RowView ring_view{P->d_ring, n, 0, (uint32_t)std::max<int64_t>(1, S.ring_rows)};
     for (int64_t b0 = r0; b0 < r1; b0 += C) {
@@ -959,8 +994,8 @@ void launch_ghost_permute(rr_plan *P, int64_t batch)
     RecPermArgs ra{};
     ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
     // (direct row path: the ghosts' records are those of the skeleton's positions that mirror them)
-    ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = P->n_ghost; ra.np = S.rows_direct ? P->dp.skel.np : P->tp.np; ra.T = S.total; ra.total = S.total;
-    ra.batch = batch; ra.nsub = Div32(1u); ra.colmeta = S.rows_direct ? P->d_kghostmeta : P->d_ghostmeta; ra.scale = nullptr;
+    ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = P->n_ghost; ra.np = S.kernel == Kernel::Direct ? P->dp.skel.np : P->tp.np; ra.T = S.total; ra.total = S.total;
+    ra.batch = batch; ra.nsub = Div32(1u); ra.colmeta = S.kernel == Kernel::Direct ? P->d_kghostmeta : P->d_ghostmeta; ra.scale = nullptr;
     ra.rows = RowView{const_cast<double *>(S.ghost_series), P->n_ghost, 0, (uint32_t)S.total};
     ra.factor = Div32(1u);
     hipLaunchKernelGGL(k_rec_in<false>, dim3((unsigned)((P->n_ghost + kRecInCols - 1) / kRecInCols)), dim3(kRecInThreads), 0, rec_stream(P), ra);
@@ -979,6 +1014,19 @@ rec_in_uh_t rec_in_uh_kernel(bool sub, int64_t n_ks, int batches, bool in32 = fa
 #undef RR_UHIN_PICK
 #undef RR_UHIN_SUB
 #undef RR_UHIN_IN
+}
+
+// The out-pass k_rec_out<SUB, F32> over `cols` columns (the plan's, or the holes' of the direct row path).
+void launch_rec_out(const RecPermArgs &ra, bool sub, int64_t cols, hipStream_t st)
+{
+    const dim3 g((unsigned)((cols + kRecOutCols - 1) / kRecOutCols));
+    if (ra.rows32) {
+        if (sub) hipLaunchKernelGGL((k_rec_out<true, true>), g, dim3(kRecOutThreads), 0, st, ra);
+        else hipLaunchKernelGGL((k_rec_out<false, true>), g, dim3(kRecOutThreads), 0, st, ra);
+    } else {
+        if (sub) hipLaunchKernelGGL((k_rec_out<true, false>), g, dim3(kRecOutThreads), 0, st, ra);
+        else hipLaunchKernelGGL((k_rec_out<false, false>), g, dim3(kRecOutThreads), 0, st, ra);
+    }
 }
 
 // `count` batches from `batch` on: 1, or 2 for the fused convolution when its rows are there (session_advance_tile)
@@ -1005,7 +1053,7 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     ra.swizzle = in ? 0 : 1;
     // one column tile per workgroup, dispatched in address order: a persistent grid with the next tile's loads in flight was no
     // faster (427 / 469 us per 128 rows against 419 / 434-448 at 1M reaches; a plain copy shows the same, profiles/r03_hbm_probe_*.txt)
-    const dim3 gp((unsigned)((n + (in ? kRecInCols : kRecOutCols) - 1) / (in ? kRecInCols : kRecOutCols)));
+    const dim3 gp((unsigned)((n + kRecInCols - 1) / kRecInCols));      // (the in-pass's; launch_rec_out has its own)
     const bool sub = S.nsub > 1;
     hipStream_t st = rec_stream(P);
     const int aux = aux_begin(P, in ? 0 : 1, st);
@@ -1023,12 +1071,8 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     } else if (in) {
         if (sub) hipLaunchKernelGGL(k_rec_in<true>, gp, dim3(kRecInThreads), 0, st, ra);
         else hipLaunchKernelGGL(k_rec_in<false>, gp, dim3(kRecInThreads), 0, st, ra);
-    } else if (ra.rows32) {
-        if (sub) hipLaunchKernelGGL((k_rec_out<true, true>), gp, dim3(kRecOutThreads), 0, st, ra);
-        else hipLaunchKernelGGL((k_rec_out<false, true>), gp, dim3(kRecOutThreads), 0, st, ra);
     } else {
-        if (sub) hipLaunchKernelGGL((k_rec_out<true, false>), gp, dim3(kRecOutThreads), 0, st, ra);
-        else hipLaunchKernelGGL((k_rec_out<false, false>), gp, dim3(kRecOutThreads), 0, st, ra);
+        launch_rec_out(ra, sub, n, st);
     }
     aux_end(P, aux, st);
 }
@@ -1190,19 +1234,14 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
             done = std::min(done, std::min(sk, S.total));
             while (S.out_batches < S.n_out_batches && done >= std::min(kRecRows * (S.out_batches + 1), S.total)) {
                 RecPermArgs ra{};
-    ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
+                ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
                 ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = P->n_kholes; ra.np = TP.np; ra.T = S.T; ra.total = S.total;
                 ra.batch = S.out_batches; ra.nsub = Div32((uint32_t)S.nsub); ra.colmeta = P->d_kholemeta; ra.cols = P->d_kholecol; ra.scale = nullptr;
                 ra.rows = RowView{S.io.dev_out, n, 0, (uint32_t)std::max<int64_t>(1, S.io.rows_out)};
                 ra.rows32 = S.io.dev_out32;
                 ra.factor = Div32((uint32_t)std::max<int64_t>(1, S.io.out_factor)); ra.clamp = S.nsub > 1 ? 0 : 1; ra.swizzle = 0;
                 const int aux = aux_begin(P, 3, S.stream);
-                const dim3 gh((unsigned)((P->n_kholes + kRecOutCols - 1) / kRecOutCols));
-                if (P->n_kholes > 0) {
-                    if (S.nsub > 1) { if (ra.rows32) hipLaunchKernelGGL((k_rec_out<true, true>), gh, dim3(kRecOutThreads), 0, S.stream, ra); else hipLaunchKernelGGL((k_rec_out<true, false>), gh, dim3(kRecOutThreads), 0, S.stream, ra); }
-                    else if (ra.rows32) hipLaunchKernelGGL((k_rec_out<false, true>), gh, dim3(kRecOutThreads), 0, S.stream, ra);
-                    else hipLaunchKernelGGL((k_rec_out<false, false>), gh, dim3(kRecOutThreads), 0, S.stream, ra);
-                }
+                if (P->n_kholes > 0) launch_rec_out(ra, S.nsub > 1, P->n_kholes, S.stream);
                 aux_end(P, aux, S.stream);
                 ++S.out_batches;
                 S.ticks_stored = std::min(S.total, kRecRows * S.out_batches);
@@ -1232,8 +1271,8 @@ int session_advance(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, int64_t
     const int64_t n = P->h.n, dmax = P->h.depth - 1, C = std::max<int64_t>(1, P->chunk_rows);
     if (export_ready) *export_ready = 0;
     if (n == 0 || S.total == 0) { if (export_ready) *export_ready = S.total; return RR_OK; }
-    if (S.wave) return session_advance_tile(P, rows_ready, std::min(ghost_ready, S.total), export_ready);
-    if (S.rows_direct) return session_advance_direct(P, rows_ready, std::min(ghost_ready, S.total), export_ready);
+    if (S.kernel == Kernel::Tile) return session_advance_tile(P, rows_ready, std::min(ghost_ready, S.total), export_ready);
+    if (S.kernel == Kernel::Direct) return session_advance_direct(P, rows_ready, std::min(ghost_ready, S.total), export_ready);
     rows_ready = std::min(rows_ready, S.T);
     ghost_ready = std::min(ghost_ready, S.total);
     // a ghost at lag L is read at tick tau for sub-step tau - L: ticks below ghost_ready + min lag are safe
@@ -1285,7 +1324,7 @@ int session_end(rr_plan *P)
     if (!complete && getenv("RR_VERBOSE"))
         fprintf(stderr, "rr: incomplete call: T=%lld total=%lld tau=%lld/%lld rows_loaded=%lld rows_stored=%lld | direct=%d tasks %lld/%lld diag %lld/%lld in_batches %lld ghost_batches %lld/%lld out_batches %lld/%lld "
                         "ticks_stored=%lld K=%lld KS=%lld chunks=%lld macro=%lld\n", (long long)S.T, (long long)S.total, (long long)S.tau, (long long)S.total_ticks, (long long)S.rows_loaded, (long long)S.rows_stored,
-                (int)S.rows_direct, (long long)S.d_done, (long long)S.n_tasks, (long long)S.diag, (long long)S.n_diags, (long long)S.in_batches, (long long)S.ghost_batches, (long long)S.n_in_batches,
+                (int)(S.kernel == Kernel::Direct), (long long)S.d_done, (long long)S.n_tasks, (long long)S.diag, (long long)S.n_diags, (long long)S.in_batches, (long long)S.ghost_batches, (long long)S.n_in_batches,
                 (long long)S.out_batches, (long long)S.n_out_batches, (long long)S.ticks_stored, (long long)(S.KC * kRec), (long long)(S.KS * kRec), (long long)S.rec_chunks, (long long)S.n_macro);
     if (!complete) return fail(RR_E_STATE, "routing call closed before all of its time steps were routed");
     if (P->h.n == 0 || S.total == 0) return RR_OK;
@@ -1318,20 +1357,16 @@ int check_route_args(rr_plan *P, bool need_c4, int64_t T, int64_t nsub)
     return RR_OK;
 }
 
-int launch_state_in(rr_plan *P, Mode mode, const double *d_q, hipStream_t stream)
+int launch_state_in(rr_plan *P, const double *d_q, hipStream_t stream)
 {
     const int64_t n = P->h.n;
-    if (P->direct_now) {      // the lanes carry their discharge in params order; the skeleton's positions and ghosts as k_tile wants them
-        HIPCHK(hipMemcpyAsync(P->d_dq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
-        const int64_t np = P->dp.skel.np;
+    if (P->sch.kernel != Kernel::Tick) {      // positions and ghosts as k_tile wants them (direct row path: the skeleton's; the lanes carry their discharge in params order)
+        const bool d = P->sch.kernel == Kernel::Direct;
+        const int64_t np = d ? P->dp.skel.np : P->tp.np;
+        if (d) HIPCHK(hipMemcpyAsync(P->d_dq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         if (np > 0)
-            hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, P->d_ksq, P->d_kss, P->d_ksi, d_q, P->d_kperm, P->d_kpmeta, (int32_t)np);
-        return RR_OK;
-    }
-    if (use_wave(P, mode)) {
-        const int64_t np = P->tp.np;
-        hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, P->d_sq, P->d_ss, P->d_si, d_q, P->d_tperm,
-                           P->d_pmeta, (int32_t)np);
+            hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, d ? P->d_ksq : P->d_sq, d ? P->d_kss : P->d_ss, d ? P->d_ksi : P->d_si, d_q,
+                               d ? P->d_kperm : P->d_tperm, d ? P->d_kpmeta : P->d_pmeta, (int32_t)np);
         return RR_OK;
     }
     hipLaunchKernelGGL(k_state_in, grid1(n), dim3(kBlock), 0, stream, P->d_x, P->d_x + n, P->d_x + 2 * n, d_q,
@@ -1339,16 +1374,16 @@ int launch_state_in(rr_plan *P, Mode mode, const double *d_q, hipStream_t stream
     return RR_OK;
 }
 
-void launch_state_out(rr_plan *P, Mode mode, double *d_q, int64_t total, hipStream_t stream)
+void launch_state_out(rr_plan *P, double *d_q, int64_t total, hipStream_t stream)
 {
     const int64_t n = P->h.n;
-    if (P->direct_now) {
+    if (P->sch.kernel == Kernel::Direct) {
         (void)hipMemcpyAsync(d_q, P->d_dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream);
         const int64_t np = P->dp.skel.np;
         if (np > 0) hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, d_q, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
         return;
     }
-    if (use_wave(P, mode)) {
+    if (P->sch.kernel == Kernel::Tile) {
         hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q, (const double *)P->d_sq, P->d_tinv,
                            (int32_t)n);
         return;
@@ -1509,43 +1544,54 @@ int route_host_pipelined(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const d
     return session_end(P);
 }
 
-int rapid_like(rr_plan *P, Mode mode, double *q_t, const Rows &io_in, int64_t T, int64_t nsub, hipStream_t stream,
-               bool q_on_host)
+// Host rows on the time-tiled kernel go through the PCIe pipeline; every other call is one session (route_core).
+int route_rows(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io, hipStream_t stream)
 {
-    const int64_t n = P->h.n;
-    if (n == 0 || T == 0) return RR_OK;
-    const Rows &io = io_in;
-    const bool host_rows = io.host_in != nullptr || io.host_out != nullptr;
-    // host rows reach the time-tiled kernel through the PCIe pipeline's device rings; where it does not apply they are
-    // routed chunk by chunk by the streaming kernel
-    {   // host rows reach the time-tiled kernel through the PCIe pipeline's device rings (they are "device rows" to the schedule)
-        const bool plain = !host_rows && (mode == Mode::Muskingum || io.dev_in || io.dev_in32) && (io.dev_out || io.dev_out32) && !io.uh_kernel && !io.runoff;      // rows in device arrays, float64 or float32: the direct row path applies
-        int rc = prepare_call(P, mode, T, nsub, false, false, !host_rows, plain, 0, 0, io.dev_out32 != nullptr);
-        if (rc == RR_OK && host_rows && !P->wave_now) rc = prepare_call(P, mode, T, nsub, true, true, false);
-        if (rc == RR_OK && host_rows && P->wave_now) rc = host_pipe_prepare(P);
-        if (rc) return rc;
-    }
-    const bool piped = host_rows && P->wave_now;
-    double *d_q = q_t;
+    if ((io.host_in || io.host_out) && P->sch.kernel == Kernel::Tile) return route_host_pipelined(P, mode, T, nsub, io.host_in, io.host_out, stream);
+    return route_core(P, mode, T, nsub, io, stream);
+}
+
+// The state arrays of a route call: device arrays as given, or (on_host: the host-pointer entry points) staged in one device buffer
+// for the call, `count` doubles each; out() copies them back.
+struct CallState {
+    std::vector<double *> host, dev;
     double *tmp = nullptr;
-    if (q_on_host) {
-        int rc = dev_alloc(&tmp, n);
-        if (rc) return rc;
-        d_q = tmp;
-        hipError_t e = hipMemcpyAsync(d_q, q_t, n * sizeof(double), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { (void)hipFree(tmp); return fail(RR_E_HIP, hipGetErrorString(e)); }
+    int64_t count = 0;
+    hipStream_t stream = nullptr;
+    int in(bool on_host, std::vector<double *> arrays, int64_t count_, hipStream_t stream_)
+    {
+        host = dev = arrays; count = count_; stream = stream_;
+        const int64_t each = std::max<int64_t>(count, 1);
+        if (!on_host) return RR_OK;
+        if (int rc = dev_alloc(&tmp, (int64_t)host.size() * each)) return rc;
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; i < host.size() && e == hipSuccess; ++i)
+            e = hipMemcpyAsync(dev[i] = tmp + i * each, host[i], count * sizeof(double), hipMemcpyHostToDevice, stream);
+        return e == hipSuccess ? RR_OK : fail(RR_E_HIP, hipGetErrorString(e));
     }
-    int rc = launch_state_in(P, mode, d_q, stream);
-    if (rc == RR_OK) rc = piped ? route_host_pipelined(P, mode, T, nsub, io.host_in, io.host_out, stream) : route_core(P, mode, T, nsub, io, stream);
-    if (rc == RR_OK) {
-        launch_state_out(P, mode, d_q, T * nsub, stream);
-        if (q_on_host) {
-            hipError_t e = hipMemcpyAsync(q_t, d_q, n * sizeof(double), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
-        }
+    int out()
+    {
+        hipError_t e = hipSuccess;
+        for (size_t i = 0; tmp && i < host.size() && e == hipSuccess; ++i) e = hipMemcpyAsync(host[i], dev[i], count * sizeof(double), hipMemcpyDeviceToHost, stream);
+        if (tmp && e == hipSuccess) e = hipStreamSynchronize(stream);
+        return e == hipSuccess ? RR_OK : fail(RR_E_HIP, hipGetErrorString(e));
     }
-    if (tmp) { (void)hipStreamSynchronize(stream); (void)hipFree(tmp); }
+    ~CallState() { if (tmp) { (void)hipStreamSynchronize(stream); (void)hipFree(tmp); } }
+};
+
+// RapidMuskingum / channel-only Muskingum.  `who` names the entry point in the errors of prepare_call.
+int rapid_like(rr_plan *P, Mode mode, double *q_t, const Rows &io, int64_t T, int64_t nsub, hipStream_t stream, bool q_on_host, const char *who)
+{
+    if (P->h.n == 0 || T == 0) return RR_OK;
+    int rc = prepare_call(P, call_shape(mode, T, nsub, io), who);
+    CallState q;
+    if (!rc) rc = q.in(q_on_host, {q_t}, P->h.n, stream);
+    if (!rc) rc = launch_state_in(P, q.dev[0], stream);
+    if (!rc) rc = route_rows(P, mode, T, nsub, io, stream);
+    if (!rc) {
+        launch_state_out(P, q.dev[0], T * nsub, stream);
+        rc = q.out();
+    }
     return rc;
 }
 
@@ -1555,23 +1601,19 @@ int unit_state_in(rr_plan *P, const double *d_qch, const double *d_qfull, hipStr
 {
     const int64_t n = P->h.n, ni = (int64_t)P->h.inner_pos.size();
     hipError_t e0 = hipSuccess;
-    if (P->direct_now) {      // the lanes carry q_full and q_ch in params order (zeros on headwaters); the skeleton's positions as k_tile<UNIT> wants them
+    if (P->sch.kernel != Kernel::Tick) {
+        // q_full / q_ch scattered to params order (zeros on headwaters: the direct row path's lanes carry them so), then gathered position by
+        // position as k_tile<UNIT> wants them (on the direct row path: the skeleton's positions)
+        const bool d = P->sch.kernel == Kernel::Direct;
+        const int64_t np = d ? P->dp.skel.np : P->tp.np;
         e0 = hipMemsetAsync(P->d_full, 0, n * sizeof(double), stream);
         if (e0 == hipSuccess) e0 = hipMemsetAsync(P->d_chan, 0, n * sizeof(double), stream);
         if (e0 == hipSuccess && ni > 0)
             hipLaunchKernelGGL(k_unit_scatter, grid1(ni), dim3(kBlock), 0, stream, P->d_full, P->d_chan, d_qfull, d_qch, P->d_inner_idx, (int32_t)ni);
-        const int64_t np = P->dp.skel.np;
         if (e0 == hipSuccess && np > 0)
-            hipLaunchKernelGGL(k_tile_unit_state_in, grid1(np), dim3(kBlock), 0, stream, P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch,
-                               (const double *)P->d_full, (const double *)P->d_chan, P->d_kperm, P->d_kpmeta, (int32_t)np);
-    } else if (use_wave(P, Mode::Unit)) {   // q_full / q_ch scattered to params order (zeros on headwaters), then gathered position by position
-        e0 = hipMemsetAsync(P->d_full, 0, n * sizeof(double), stream);
-        if (e0 == hipSuccess) e0 = hipMemsetAsync(P->d_chan, 0, n * sizeof(double), stream);
-        if (e0 == hipSuccess && ni > 0)
-            hipLaunchKernelGGL(k_unit_scatter, grid1(ni), dim3(kBlock), 0, stream, P->d_full, P->d_chan, d_qfull, d_qch, P->d_inner_idx, (int32_t)ni);
-        if (e0 == hipSuccess)
-            hipLaunchKernelGGL(k_tile_unit_state_in, grid1(P->tp.np), dim3(kBlock), 0, stream, P->d_sq, P->d_ss, P->d_si, P->d_sqch,
-                               (const double *)P->d_full, (const double *)P->d_chan, P->d_tperm, P->d_pmeta, (int32_t)P->tp.np);
+            hipLaunchKernelGGL(k_tile_unit_state_in, grid1(np), dim3(kBlock), 0, stream, d ? P->d_ksq : P->d_sq, d ? P->d_kss : P->d_ss, d ? P->d_ksi : P->d_si,
+                               d ? P->d_ksqch : P->d_sqch, (const double *)P->d_full, (const double *)P->d_chan, d ? P->d_kperm : P->d_tperm,
+                               d ? P->d_kpmeta : P->d_pmeta, (int32_t)np);
     } else {
         e0 = hipMemsetAsync(P->d_x, 0, 3 * n * sizeof(double), stream);
         if (e0 == hipSuccess && ni > 0)
@@ -1585,14 +1627,14 @@ void unit_state_out(rr_plan *P, double *d_qch, double *d_qfull, int64_t total, h
 {
     const int64_t n = P->h.n, ni = (int64_t)P->h.inner_pos.size();
     if (ni == 0) return;
-    if (P->direct_now) {      // the skeleton's reaches back into the params-order arrays the lanes kept, then the inner reaches' pairs
+    if (P->sch.kernel == Kernel::Direct) {      // the skeleton's reaches back into the params-order arrays the lanes kept, then the inner reaches' pairs
         const int64_t np = P->dp.skel.np;
         if (np > 0) {
             hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_full, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
             hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_chan, (const double *)P->d_ksqch, P->d_kperm, P->d_kpmeta, (int32_t)np);
         }
         hipLaunchKernelGGL(k_unit_gather, grid1(ni), dim3(kBlock), 0, stream, d_qch, d_qfull, (const double *)P->d_chan, (const double *)P->d_full, P->d_inner_idx, (int32_t)ni);
-    } else if (use_wave(P, Mode::Unit))
+    } else if (P->sch.kernel == Kernel::Tile)
         hipLaunchKernelGGL(k_tile_unit_state_out, grid1(ni), dim3(kBlock), 0, stream, d_qch, d_qfull,
                            (const double *)P->d_sq, (const double *)P->d_sqch, P->d_inner_idx, P->d_tinv, (int32_t)ni);
     else
@@ -1600,76 +1642,57 @@ void unit_state_out(rr_plan *P, double *d_qch, double *d_qfull, int64_t total, h
                            (const double *)P->d_x, n, (const double *)P->d_qch, P->d_lag, P->d_inner_pos, (int32_t)ni, total);
 }
 
+// Carry-over state of the unit-hydrograph convolution, in place, enqueued after every pass that reads the old one (same stream).
+template <typename TIn>
+void launch_uh_tail(const double *kernel, double *state, const TIn *rows, int64_t T, int64_t n_ks, int64_t n, hipStream_t stream, uint32_t sel)
+{
+    const dim3 gt((unsigned)((n + kUhTailThreads - 1) / kUhTailThreads));
+    const int32_t nks = (int32_t)n_ks;
+    if (nks <= 16) hipLaunchKernelGGL((k_uh_tail<16, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
+    else if (nks <= 48) hipLaunchKernelGGL((k_uh_tail<48, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
+    else hipLaunchKernelGGL((k_uh_tail<0, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
+}
+
 template <typename TIn>
 int uh_convolve_core(const double *d_kernel, double *d_state, const TIn *d_lateral, double *d_out, int64_t T, int64_t n_ks, int64_t n, hipStream_t stream, uint32_t sel);
 
-int unit_like(rr_plan *P, double *q_ch, double *q_full, const Rows &io_in, int64_t T, int64_t nsub,
-              hipStream_t stream, bool q_on_host, double *d_q_final = nullptr, double *uh_state_inout = nullptr)
+// UnitMuskingum.  `who` names the entry point in the errors of prepare_call.
+int unit_like(rr_plan *P, double *q_ch, double *q_full, const Rows &io_in, int64_t T, int64_t nsub, hipStream_t stream, bool q_on_host,
+              const char *who, double *d_q_final = nullptr, double *uh_state_inout = nullptr)
 {
     const int64_t n = P->h.n, ni = (int64_t)P->h.inner_pos.size();
     if (n == 0 || T == 0) return RR_OK;
     Rows io = io_in;
-    const bool host_rows = io.host_in != nullptr || io.host_out != nullptr;
-    {
-        // rows in device arrays -- convolved lateral inflow, or runoff depths (float64 / float32) with the unit-hydrograph kernel: the direct row path applies
-        const bool plain = !host_rows && (io.dev_in || io.dev_in32) && (io.dev_out || io.dev_out32) && !io.runoff && (io.uh_kernel || !io.dev_in32) && (!io.uh_kernel || uh_state_inout);
-        int rc = prepare_call(P, Mode::Unit, T, nsub, false, false, !host_rows, plain, 0, 0, io.dev_out32 != nullptr, io.uh_kernel != nullptr);
-        if (rc == RR_OK && host_rows && !P->wave_now) rc = prepare_call(P, Mode::Unit, T, nsub, true, true, false);
-        if (rc == RR_OK && host_rows && P->wave_now) rc = host_pipe_prepare(P);
-        if (rc) return rc;
-    }
-    const bool piped = host_rows && P->wave_now;
-    double *d_qch = q_ch, *d_qfull = q_full, *tmp = nullptr;
-    if (q_on_host) {
-        int rc = dev_alloc(&tmp, 2 * std::max<int64_t>(ni, 1));
-        if (rc) return rc;
-        d_qch = tmp; d_qfull = tmp + std::max<int64_t>(ni, 1);
-        hipError_t e = hipMemcpyAsync(d_qch, q_ch, ni * sizeof(double), hipMemcpyHostToDevice, stream);
-        if (e == hipSuccess) e = hipMemcpyAsync(d_qfull, q_full, ni * sizeof(double), hipMemcpyHostToDevice, stream);
-        if (e != hipSuccess) { (void)hipFree(tmp); return fail(RR_E_HIP, hipGetErrorString(e)); }
-    }
-    const bool wave = use_wave(P, Mode::Unit);
-    int rc = unit_state_in(P, d_qch, d_qfull, stream);
-    if (rc == RR_OK && P->direct_now && io.uh_kernel) {
+    int rc = prepare_call(P, call_shape(Mode::Unit, T, nsub, io), who);
+    const Kernel kernel = P->sch.kernel;
+    const uint32_t sel32 = P->in32_big_endian ? kSelSwap : kSelNative;
+    CallState q;
+    if (!rc) rc = q.in(q_on_host, {q_ch, q_full}, ni, stream);
+    if (!rc) rc = unit_state_in(P, q.dev[0], q.dev[1], stream);
+    if (!rc && kernel == Kernel::Direct && io.uh_kernel) {
         // the direct row path: the convolution first, into the work rows (choose_schedule: uh), carry-over state updated in place;
         // the lanes then route those rows
         if (T * n > P->mrows_cap) rc = fail(RR_E_STATE, "route: the convolved rows of the direct row path were not reserved");
-        else if (io.dev_in32) rc = uh_convolve_core<float>(io.uh_kernel, uh_state_inout, io.dev_in32, P->d_mrows, T, io.uh_nks, n, stream, P->in32_big_endian ? kSelSwap : kSelNative);
+        else if (io.dev_in32) rc = uh_convolve_core<float>(io.uh_kernel, uh_state_inout, io.dev_in32, P->d_mrows, T, io.uh_nks, n, stream, sel32);
         else rc = uh_convolve_core<double>(io.uh_kernel, uh_state_inout, io.dev_in, P->d_mrows, T, io.uh_nks, n, stream, kSelNative);
         io.dev_in = P->d_mrows; io.dev_in32 = nullptr; io.rows_in = T; io.uh_kernel = nullptr; io.uh_state = nullptr;
     }
-    if (rc) { if (tmp) (void)hipFree(tmp); return rc; }
-    if (rc == RR_OK) rc = piped ? route_host_pipelined(P, Mode::Unit, T, nsub, io.host_in, io.host_out, stream) : route_core(P, Mode::Unit, T, nsub, io, stream);
-    if (rc == RR_OK && wave && d_q_final)      // every reach: a headwater's state is its last lateral inflow, an inner reach's q_full
+    if (!rc) rc = route_rows(P, Mode::Unit, T, nsub, io, stream);
+    if (!rc && kernel == Kernel::Tile && d_q_final)      // every reach: a headwater's state is its last lateral inflow, an inner reach's q_full
         hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q_final, (const double *)P->d_sq, P->d_tinv, (int32_t)n);
-    if (rc == RR_OK && P->direct_now && d_q_final) {      // the lanes' columns hold exactly that; the skeleton's reaches join them
+    if (!rc && kernel == Kernel::Direct && d_q_final) {      // the lanes' columns hold exactly that; the skeleton's reaches join them
         const int64_t np = P->dp.skel.np;
         if (np > 0) hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_full, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
         (void)hipMemcpyAsync(d_q_final, P->d_full, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream);
     }
-    if (rc == RR_OK && io.uh_kernel && uh_state_inout) {      // carry-over state of the fused convolution, in place, after every batch has read the old one
-        const dim3 gt((unsigned)((n + kUhTailThreads - 1) / kUhTailThreads));
-        const int32_t nks = (int32_t)io.uh_nks;
-        if (io.dev_in32) {      // float32 depth rows
-            const uint32_t sel = P->in32_big_endian ? kSelSwap : kSelNative;
-            if (nks <= 16) hipLaunchKernelGGL((k_uh_tail<16, float>), gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in32, T, nks, n, sel);
-            else if (nks <= 48) hipLaunchKernelGGL((k_uh_tail<48, float>), gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in32, T, nks, n, sel);
-            else hipLaunchKernelGGL((k_uh_tail<0, float>), gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in32, T, nks, n, sel);
-        }
-        else if (nks <= 16) hipLaunchKernelGGL(k_uh_tail<16>, gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in, T, nks, n);
-        else if (nks <= 48) hipLaunchKernelGGL(k_uh_tail<48>, gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in, T, nks, n);
-        else hipLaunchKernelGGL(k_uh_tail<0>, gt, dim3(kUhTailThreads), 0, stream, io.uh_kernel, uh_state_inout, io.dev_in, T, nks, n);
+    if (!rc && io.uh_kernel && uh_state_inout) {      // carry-over state of the fused convolution, after every batch has read the old one
+        if (io.dev_in32) launch_uh_tail<float>(io.uh_kernel, uh_state_inout, io.dev_in32, T, io.uh_nks, n, stream, sel32);
+        else launch_uh_tail<double>(io.uh_kernel, uh_state_inout, io.dev_in, T, io.uh_nks, n, stream, kSelNative);
     }
-    if (rc == RR_OK && ni > 0) {
-        unit_state_out(P, d_qch, d_qfull, T * nsub, stream);
-        if (q_on_host) {
-            hipError_t e = hipMemcpyAsync(q_ch, d_qch, ni * sizeof(double), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipMemcpyAsync(q_full, d_qfull, ni * sizeof(double), hipMemcpyDeviceToHost, stream);
-            if (e == hipSuccess) e = hipStreamSynchronize(stream);
-            if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
-        }
+    if (!rc && ni > 0) {
+        unit_state_out(P, q.dev[0], q.dev[1], T * nsub, stream);
+        rc = q.out();
     }
-    if (tmp) { (void)hipStreamSynchronize(stream); (void)hipFree(tmp); }
     return rc;
 }
 
@@ -1708,10 +1731,7 @@ int uh_convolve_core(const double *d_kernel, double *d_state, const TIn *d_later
                            d_out, T, (int32_t)n_ks, n, sel);
     }
     // carry-over state, in place, after the rows above have read the old one (same stream)
-    const dim3 gt((unsigned)((n + kUhTailThreads - 1) / kUhTailThreads));
-    if (n_ks <= 16) hipLaunchKernelGGL((k_uh_tail<16, TIn>), gt, dim3(kUhTailThreads), 0, stream, d_kernel, d_state, d_lateral, T, (int32_t)n_ks, n, sel);
-    else if (n_ks <= 48) hipLaunchKernelGGL((k_uh_tail<48, TIn>), gt, dim3(kUhTailThreads), 0, stream, d_kernel, d_state, d_lateral, T, (int32_t)n_ks, n, sel);
-    else hipLaunchKernelGGL((k_uh_tail<0, TIn>), gt, dim3(kUhTailThreads), 0, stream, d_kernel, d_state, d_lateral, T, (int32_t)n_ks, n, sel);
+    launch_uh_tail<TIn>(d_kernel, d_state, d_lateral, T, n_ks, n, stream, sel);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

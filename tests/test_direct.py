@@ -471,6 +471,39 @@ def test_stream_session_with_a_refilled_lateral_ring_shorter_than_a_task(monkeyp
             assert_close(q.cpu().numpy(), q_ref, 'state')
 
 
+@pytest.mark.gpu
+def test_stream_session_with_a_ring_shorter_than_two_chunks_keeps_to_records(monkeypatch):
+    """A lateral or discharge ring of fewer than 32 rows leaves no direct task (K < 32; at 8 rows K = 0): the call goes to records, as
+    engine.Plan.stream_begin reserves.  Lateral rings of 8 and 24 rows hold a periodic series, announced whole (a ring refilled at this
+    size is outside the record path's contract): discharge and state against the oracle on the series the ring stands for.  A discharge
+    ring of 8 rows: the final state against the oracle (which of the rows sharing a slot an out-pass writes last is not specified)."""
+    import torch
+    set_env(monkeypatch, {})
+    n, T = 60_000, 300
+    net, indptr, indices, c1, c2, c3 = _case(n, 43)
+    lhs, c4_dt = -c1[indices], (c1 + c2) / 900.0
+    ql = synth.synth_qlateral(n, 0, T)
+    dev = torch.device('cuda:0')
+    stream = torch.cuda.current_stream().cuda_stream
+    for lat_rows, out_rows in ((8, T), (24, T), (T, 8)):
+        series = ql[np.arange(T) % lat_rows]
+        q_ref, d_ref = np.zeros(n), np.zeros((T, n))
+        oracle.rapid_route(indptr, indices, lhs, c2, c3, c4_dt, q_ref, series, d_ref, 1)
+        with Plan(indptr, indices) as plan:
+            plan.set_coeffs(lhs, c2, c3, c4_dt)
+            q = torch.zeros(n, dtype=torch.float64, device=dev)
+            lat = torch.from_numpy(np.ascontiguousarray(series[:lat_rows])).to(dev)
+            out = torch.zeros((out_rows, n), dtype=torch.float64, device=dev)
+            plan.stream_begin(q, lat, lat_rows, out, out_rows, T, 1, stream=stream)
+            plan.stream_advance(T, T)
+            plan.stream_end(q)
+            torch.cuda.synchronize()
+            assert plan.last_kernel() == 'tile', (lat_rows, out_rows)
+            if out_rows == T:
+                assert_close(out.cpu().numpy(), d_ref, f'discharge, lateral ring of {lat_rows} rows')
+            assert_close(q.cpu().numpy(), q_ref, f'state, rings of {lat_rows} / {out_rows} rows')
+
+
 def test_parts_of_a_cut_postorder_network_lay_out_around_their_boundary_reaches():
     """rr_plan_set_boundary lays the direct plan out again: a ghost's column (first in a part's local order, far from the reach it
     flows into) is passed through, the reaches below it join the skeleton, an export is a lane's or the skeleton's."""
