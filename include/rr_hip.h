@@ -347,6 +347,23 @@ int rr_runoff_to_qlateral_dev(int device, int64_t n_rivers, int64_t n_points, in
                               int64_t stride_t, int64_t stride_p, const double *area, int flags, double *qlateral,
                               void *stream);
 
+/* ---- skill scores of (time, reach) rows on the device (river_route/metrics.py; DESIGN.md section "Skill scores") ----
+ * Per column j of n: y_true[r, j] against y_pred[r, pred_columns[j]] (pred_columns NULL: column j), r < rows.  Element (r, c)
+ * of an array is at base[r * pitch + c] (pitch in elements, >= the columns read), float when *_is_f32, else double; both are
+ * widened to double.  `state` is RR_METRICS_STATE x n doubles, field-major (state[k * n + j]), zero-filled by the caller
+ * before the first update; each update merges its rows into it, so a series may arrive in row blocks (same inputs and
+ * the same sequence of updates: bit-identical results).  An update needs rr_metrics_work_bytes bytes of work memory (0
+ * when rows == 0).  rr_metrics_finish_dev writes out[5 * n]: out[k * n + j] = mean error, mean absolute error, mean
+ * square error, Pearson r, KGE-2012 of column j, with the reference's NaN rules (a column without rows: all NaN).
+ * The _dev calls only enqueue on `stream` and allocate nothing; pred_columns is not range-checked on the device. */
+#define RR_METRICS_STATE 9
+#define RR_METRICS_SCORES 5
+int rr_metrics_work_bytes(int64_t n, int64_t rows, int64_t *bytes);
+int rr_metrics_update_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                          const void *y_pred, int pred_is_f32, int64_t pred_pitch, const int32_t *pred_columns, double *state,
+                          void *work, int64_t work_bytes, void *stream);
+int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *out, void *stream);
+
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);

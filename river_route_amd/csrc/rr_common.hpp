@@ -20,7 +20,7 @@
 #include "../../include/rr_hip.h"
 #include "rr_plan.hpp"
 
-#define RR_VERSION_NUM 100
+#define RR_VERSION_NUM 200
 
 namespace {
 

@@ -13,7 +13,7 @@
 // Layout: rr_plan.hpp.  No CPU fallback anywhere in this file.
 //
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
-// rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp (device code), rr_exec.hpp (plan object, executor), then the
+// rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp (device code), rr_exec.hpp (plan object, executor), then the
 // C ABI below.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
@@ -22,6 +22,7 @@
 #include "rr_kernels_rec.hpp"
 #include "rr_kernels_runoff.hpp"
 #include "rr_kernels_direct.hpp"
+#include "rr_kernels_metrics.hpp"
 #include "rr_exec.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -911,6 +912,62 @@ int rr_runoff_to_qlateral(int device, int64_t n_rivers, int64_t n_points, int64_
     }
     release();
     return rc;
+}
+
+// ---- skill scores (rr_kernels_metrics.hpp) ----
+
+int rr_metrics_work_bytes(int64_t n, int64_t rows, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, "rr_metrics_work_bytes: null out");
+    if (n < 0 || rows < 0 || n > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_metrics_work_bytes: sizes out of range");
+    *bytes = 0;
+    if (n == 0 || rows == 0) return RR_OK;
+    int64_t splits, rows_per_split;
+    metrics_split(n, rows, splits, rows_per_split);
+    *bytes = splits * RR_METRICS_STATE * n * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_metrics_update_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                          const void *y_pred, int pred_is_f32, int64_t pred_pitch, const int32_t *pred_columns, double *state,
+                          void *work, int64_t work_bytes, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_update_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    int64_t need = 0;
+    if (int rc = rr_metrics_work_bytes(n, rows, &need)) return rc;
+    if (n == 0 || rows == 0) return RR_OK;
+    if (!y_true || !y_pred || !state) return fail(RR_E_INVALID, "rr_metrics_update_dev: null array");
+    if (true_pitch < n || pred_pitch < (pred_columns ? 1 : n))
+        return fail(RR_E_INVALID, "rr_metrics_update_dev: row pitch shorter than the columns read");
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_metrics_update_dev: work memory smaller than rr_metrics_work_bytes (" + std::to_string(need) + " bytes)");
+    int64_t splits, rows_per_split;
+    metrics_split(n, rows, splits, rows_per_split);
+    double *slab = static_cast<double *>(work);
+    const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)splits);
+#define RR_METRICS_LAUNCH(TT_, TP_)                                                                                       \
+    hipLaunchKernelGGL((k_metrics_partial<TT_, TP_>), g, dim3(kBlock), 0, (hipStream_t)stream, (const TT_ *)y_true,        \
+                       true_pitch, (const TP_ *)y_pred, pred_pitch, pred_columns, n, rows, rows_per_split, slab)
+    if (true_is_f32) { if (pred_is_f32) RR_METRICS_LAUNCH(float, float); else RR_METRICS_LAUNCH(float, double); }
+    else { if (pred_is_f32) RR_METRICS_LAUNCH(double, float); else RR_METRICS_LAUNCH(double, double); }
+#undef RR_METRICS_LAUNCH
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_metrics_merge, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, slab, splits, n, state);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *out, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_finish_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    if (n < 0 || n > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_metrics_finish_dev: sizes out of range");
+    if (n == 0) return RR_OK;
+    if (!state || !out) return fail(RR_E_INVALID, "rr_metrics_finish_dev: null array");
+    hipLaunchKernelGGL(k_metrics_finish, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, state, n, out);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
 }
 
 // ---- device helpers ----

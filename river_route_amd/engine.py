@@ -12,7 +12,8 @@ from . import _lib
 from ._lib import RRError, check, ptr
 
 __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
-           'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download']
+           'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
+           'metrics_update_dev', 'metrics_finish_dev']
 
 
 MODE_RAPID, MODE_MUSKINGUM, MODE_UNIT = 0, 1, 2      # include/rr_hip.h: RR_MODE_*
@@ -393,6 +394,29 @@ def runoff_to_qlateral_dev(n_rivers, n_points, T, indptr, indices, weights, runo
 def resample_cast_dev(discharge, num_rows, n, factor, out, device: int = 0, stream=None) -> None:
     """Device-side mean over `factor` rows + float32 cast (rr_resample_cast_dev)."""
     check(_lib.lib().rr_resample_cast_dev(int(device), ptr(discharge), int(num_rows), int(n), int(factor), ptr(out), stream))
+
+
+METRICS_STATE, METRICS_SCORES = 9, 5      # include/rr_hip.h: RR_METRICS_STATE, RR_METRICS_SCORES
+
+
+def metrics_work_bytes(n: int, rows: int) -> int:
+    """rr_metrics_work_bytes: device work memory one rr_metrics_update_dev of `rows` rows of n columns needs."""
+    out = C.c_int64(0)
+    check(_lib.lib().rr_metrics_work_bytes(int(n), int(rows), C.byref(out)))
+    return int(out.value)
+
+
+def metrics_update_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is_f32, pred_pitch, pred_columns, state, work,
+                       work_bytes, device: int = 0, stream=None) -> None:
+    """rr_metrics_update_dev: merge `rows` device rows into the [9][n] float64 score state; only enqueues."""
+    check(_lib.lib().rr_metrics_update_dev(int(device), int(n), int(rows), ptr(y_true), int(bool(true_is_f32)), int(true_pitch),
+                                           ptr(y_pred), int(bool(pred_is_f32)), int(pred_pitch), ptr(pred_columns), ptr(state),
+                                           ptr(work), int(work_bytes), stream))
+
+
+def metrics_finish_dev(n, state, out, device: int = 0, stream=None) -> None:
+    """rr_metrics_finish_dev: [9][n] state -> out[5][n] (me, mae, mse, pearson_r, kge2012); only enqueues."""
+    check(_lib.lib().rr_metrics_finish_dev(int(device), int(n), ptr(state), ptr(out), stream))
 
 
 class DeviceBuffer:

@@ -1,0 +1,242 @@
+"""
+Skill scores of a routed run: river_route.metrics of the reference (`rr.metrics.kge2012(obs, sim)`), plus a batched form
+that scores every column of a (time, reach) array where it already lies, on the GPU.
+
+1-D inputs (one series each) are scored on the host with numpy, exactly as the reference does: a numpy scalar comes back
+and no GPU or built library is needed.  2-D inputs of shape (T, n) give one score per column, shape (n,), computed on the
+GPU in one streaming read (rr_metrics_update_dev / rr_metrics_finish_dev, include/rr_hip.h): numpy arrays are uploaded
+and numpy comes back; torch tensors on the device (float32 or float64) are read in place when their columns are adjacent
+and their rows do not overlap (any row stride from the width up; other views, broadcast rows among them, are copied
+first), and device tensors come back.  `scores` returns all five scores of one pass; `Accumulator` scores a series that
+arrives in row blocks, its per-column state staying on the device between blocks.
+
+The device path merges per-column counts, means, M2 terms and co-moments exactly (Chan et al.) and matches the host
+path run on each column of the float64 data (float32 data: widened to float64) to rtol 1e-10.  One divergence is known:
+a column that is exactly constant has M2 == 0 on the device, so its pearson_r and kge2012 are nan, where numpy's
+mean-then-subtract can leave a tiny non-zero standard deviation (1.4e-17 for 35,040 copies of 0.1) and the reference's
+KGE then returns a finite number.
+"""
+from __future__ import annotations
+
+import sys
+
+import numpy as np
+
+__all__ = ['mean_error', 'mean_absolute_error', 'mean_square_error', 'pearson_r', 'kling_gupta_efficiency_2012',
+           'me', 'mae', 'mse', 'kge2012', 'scores', 'Accumulator', 'SCORES']
+
+SCORES = ('me', 'mae', 'mse', 'pearson_r', 'kge2012')       # the rows of rr_metrics_finish_dev's out[5][n]
+_UNUSED = object()      # Accumulator._stream before the first launch
+
+
+def _torch_tensor(a) -> bool:
+    t = sys.modules.get('torch')
+    return t is not None and isinstance(a, t.Tensor)
+
+
+def _batched(y_true, y_pred) -> bool:
+    """Per-column scores on the GPU: a torch tensor, or a 2-D array."""
+    return _torch_tensor(y_true) or _torch_tensor(y_pred) or np.ndim(y_true) == 2 or np.ndim(y_pred) == 2
+
+
+def mean_error(y_true, y_pred):
+    """Mean of y_true - y_pred (the reference's sign: positive when the simulation is low)."""
+    if _batched(y_true, y_pred):
+        return scores(y_true, y_pred)['me']
+    return np.mean(np.asarray(y_true) - np.asarray(y_pred))
+
+
+def mean_absolute_error(y_true, y_pred):
+    """Mean of |y_true - y_pred|."""
+    if _batched(y_true, y_pred):
+        return scores(y_true, y_pred)['mae']
+    return np.mean(np.abs(np.asarray(y_true) - np.asarray(y_pred)))
+
+
+def mean_square_error(y_true, y_pred):
+    """Mean of (y_true - y_pred) ** 2."""
+    if _batched(y_true, y_pred):
+        return scores(y_true, y_pred)['mse']
+    return np.mean((np.asarray(y_true) - np.asarray(y_pred)) ** 2)
+
+
+def pearson_r(y_true, y_pred):
+    """Pearson correlation as np.corrcoef gives it: clipped to [-1, 1], nan when either series has zero variance."""
+    if _batched(y_true, y_pred):
+        return scores(y_true, y_pred)['pearson_r']
+    return np.corrcoef(y_true, y_pred)[0, 1]
+
+
+def kling_gupta_efficiency_2012(y_true, y_pred):
+    """Kling-Gupta efficiency as the reference computes it: 1 - sqrt((r - 1)^2 + (beta - 1)^2 + (gamma - 1)^2) with
+    beta = mean_pred / mean_true and gamma = (mean_pred / std_pred) / (mean_true / std_true), standard deviations with
+    ddof 0; nan when std_true, std_pred or mean_true is 0.
+
+    Note: this gamma is the INVERSE of the coefficient-of-variation ratio of Kling et al. (2012), (std_pred / mean_pred) /
+    (std_true / mean_true).  It is kept as the reference has it, so that scores agree with the reference's."""
+    if _batched(y_true, y_pred):
+        return scores(y_true, y_pred)['kge2012']
+    r = pearson_r(y_true, y_pred)
+    mean_true, mean_pred = np.mean(y_true), np.mean(y_pred)
+    std_true, std_pred = np.std(y_true), np.std(y_pred)
+    if std_true == 0 or std_pred == 0 or mean_true == 0:
+        return np.nan
+    beta = mean_pred / mean_true
+    gamma = (mean_pred / std_pred) / (mean_true / std_true)
+    return 1 - np.sqrt(np.power(r - 1, 2) + np.power(beta - 1, 2) + np.power(gamma - 1, 2))
+
+
+me = mean_error
+mae = mean_absolute_error
+mse = mean_square_error
+kge2012 = kling_gupta_efficiency_2012
+
+
+def scores(y_true, y_pred, columns=None) -> dict:
+    """All five scores per column from one read of (T, n) y_true and (T, m) y_pred: {'me', 'mae', 'mse', 'pearson_r',
+    'kge2012'} -> (n,) arrays (numpy in: numpy out; torch in: device tensors out).  columns: optional int array of
+    length n, column j of y_true is scored against column columns[j] of y_pred (repeats allowed; no gather copy is
+    made); without it m must equal n.  1-D inputs are scored as one column."""
+    t, p = _Rows(y_true, 'y_true'), _Rows(y_pred, 'y_pred')
+    device = t.device if t.device is not None else (p.device if p.device is not None else 0)
+    acc = Accumulator(t.cols, columns=columns, device=device)
+    acc._update(t, p)
+    return acc.result()
+
+
+class Accumulator:
+    """Per-column scores of series that arrive in row blocks: the rows of each input file of a run, or rows streamed
+    from disk.  `update(true_rows, pred_rows)` merges (k, n) and (k, m) blocks into a per-column state kept on the GPU;
+    `result()` returns the scores of all rows so far as `scores` does.  Splitting the rows differently changes results
+    by rounding only (within 1e-12 relative); the same blocks in the same order give bit-identical results."""
+
+    def __init__(self, n: int, columns=None, device: int = 0):
+        from . import engine
+        self._engine = engine
+        self.n, self.device, self.rows = int(n), int(device), 0
+        if self.n < 1:
+            raise ValueError('Accumulator needs n >= 1 columns')
+        self._columns, self._cols_dev = None, None
+        if columns is not None:
+            cols = np.asarray(columns.detach().cpu() if _torch_tensor(columns) else columns)
+            if cols.shape != (self.n,) or not np.issubdtype(cols.dtype, np.integer):
+                raise ValueError(f'columns must be a 1-D integer array of length {self.n}')
+            if cols.min() < 0 or cols.max() > np.iinfo(np.int32).max:
+                raise ValueError('columns holds a negative or too large column index')
+            self._columns = cols.astype(np.int32)
+            self._cols_dev = engine.DeviceBuffer(self._columns.nbytes, self.device).upload(self._columns)
+        self._state = engine.DeviceBuffer(engine.METRICS_STATE * self.n * 8, self.device)
+        self._state.upload(np.zeros(engine.METRICS_STATE * self.n))
+        self._work, self._stream, self._torch = None, _UNUSED, False
+
+    def update(self, true_rows, pred_rows) -> 'Accumulator':
+        self._update(_Rows(true_rows, 'true_rows'), _Rows(pred_rows, 'pred_rows'))
+        return self
+
+    def _update(self, t: '_Rows', p: '_Rows') -> None:
+        e = self._engine
+        if t.cols != self.n:
+            raise ValueError(f'true rows have {t.cols} columns, the accumulator {self.n}')
+        if t.rows != p.rows:
+            raise ValueError(f'true rows ({t.rows}) and predicted rows ({p.rows}) differ in number')
+        if self._columns is None and p.cols != self.n:
+            raise ValueError(f'predicted rows have {p.cols} columns, expected {self.n} (or pass columns=)')
+        if self._columns is not None and self._columns.max() >= p.cols:
+            raise ValueError(f'columns refers to column {int(self._columns.max())} of predicted rows with {p.cols} columns')
+        for r in (t, p):
+            if r.device is not None and r.device != self.device:
+                raise ValueError(f'rows on device {r.device}, accumulator on device {self.device}')
+        if t.rows == 0:
+            return
+        torch_in = t.tensor is not None or p.tensor is not None
+        stream = None
+        if torch_in:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._torch = True
+        self._enter_stream(stream)
+        t.to_device(self.device)
+        p.to_device(self.device)
+        need = e.metrics_work_bytes(self.n, t.rows)
+        if self._work is None or self._work.nbytes < need:
+            if self._work is not None:
+                self._work.free()
+            self._work = e.DeviceBuffer(need, self.device)
+        e.metrics_update_dev(self.n, t.rows, t.address, t.is_f32, t.pitch, p.address, p.is_f32, p.pitch, self._cols_dev, self._state,
+                             self._work, self._work.nbytes, device=self.device, stream=stream)
+        if t.uploaded is not None or p.uploaded is not None:
+            e.synchronize(self.device)            # the uploaded copies are freed on return
+        self.rows += t.rows
+
+    def _enter_stream(self, stream) -> None:
+        """Enqueue on `stream` from here on: work the state and the work slab took part in on another stream is finished first."""
+        if self._stream is not _UNUSED and stream != self._stream:
+            self._engine.synchronize(self.device)
+        self._stream = stream
+
+    def result(self) -> dict:
+        """{'me', 'mae', 'mse', 'pearson_r', 'kge2012'} -> (n,) scores of every row so far: device tensors if any update
+        came as torch tensors, else numpy arrays."""
+        e = self._engine
+        if self._torch:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._enter_stream(stream)
+            out = torch.empty((len(SCORES), self.n), dtype=torch.float64, device=torch.device('cuda', self.device))
+            e.metrics_finish_dev(self.n, self._state, out.data_ptr(), device=self.device, stream=stream)
+        else:
+            self._enter_stream(None)
+            buf = e.DeviceBuffer(len(SCORES) * self.n * 8, self.device)
+            e.metrics_finish_dev(self.n, self._state, buf, device=self.device)
+            e.synchronize(self.device)
+            out = buf.download(np.float64, (len(SCORES), self.n))
+            buf.free()
+        return {k: out[i] for i, k in enumerate(SCORES)}
+
+
+class _Rows:
+    """One input of an update: a (rows, cols) float32/float64 block in device memory, row `pitch` elements apart.
+    numpy arrays (other dtypes: as float64) are uploaded by to_device; torch tensors on the GPU are used in place."""
+
+    def __init__(self, a, name: str):
+        self.tensor, self.uploaded, self.device = None, None, None
+        if _torch_tensor(a):
+            import torch
+            if a.device.type != 'cuda':
+                raise ValueError(f'{name}: torch tensor must be on the GPU (got {a.device})')
+            if a.dtype not in (torch.float32, torch.float64):
+                a = a.to(torch.float64)
+            if a.dim() == 1:
+                a = a.reshape(-1, 1)
+            if a.dim() != 2:
+                raise ValueError(f'{name} must be 1-D or 2-D (time, column)')
+            # the kernel reads element (r, c) at r * pitch + c: rows that share elements (a broadcast or overlapping
+            # view, row stride below the width) or columns that are not adjacent are copied into whole rows first
+            if (a.shape[1] > 1 and a.stride(1) != 1) or (a.shape[0] > 1 and a.stride(0) < a.shape[1]):
+                a = a.contiguous()
+            self.tensor, self.device = a, a.device.index or 0
+            self.rows, self.cols = int(a.shape[0]), int(a.shape[1])
+            self.is_f32 = a.dtype == torch.float32
+            self.pitch = int(a.stride(0)) if self.rows > 1 else self.cols
+        else:
+            a = np.asarray(a)
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float64)
+            if a.ndim == 1:
+                a = a.reshape(-1, 1)
+            if a.ndim != 2:
+                raise ValueError(f'{name} must be 1-D or 2-D (time, column)')
+            self.host = np.ascontiguousarray(a)
+            self.rows, self.cols = int(a.shape[0]), int(a.shape[1])
+            self.is_f32 = a.dtype == np.float32
+            self.pitch = self.cols
+
+    def to_device(self, device: int) -> None:
+        if self.tensor is not None or self.uploaded is not None:
+            return
+        from .engine import DeviceBuffer
+        self.uploaded = DeviceBuffer(max(self.host.nbytes, 8), device).upload(self.host)
+
+    @property
+    def address(self) -> int:
+        return int(self.tensor.data_ptr()) if self.tensor is not None else int(self.uploaded.address)
