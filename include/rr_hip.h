@@ -154,6 +154,7 @@ int rr_plan_profile_aux(rr_plan *plan, double aux[12]);
 #define RR_KERNEL_TICK 0
 #define RR_KERNEL_TILE 1
 #define RR_KERNEL_DIRECT 2
+#define RR_KERNEL_TILE_ENSEMBLE 3      /* rr_rapid_route_ensemble_dev: the time-tiled kernel over (tile, member) tasks */
 int rr_plan_last_kernel(const rr_plan *plan);
 
 /* Byte order of the FLOAT32 rows of the calls to come (rr_*_f32in_dev's lateral / depth rows, rr_*_f32*_dev's discharge rows): non-zero =
@@ -223,6 +224,29 @@ int rr_rapid_route_f32_dev(rr_plan *plan, double *q_t, const double *qlateral, i
  * rr_rapid_route_dev). */
 int rr_rapid_route_f32in_dev(rr_plan *plan, double *q_t, const float *qlateral32, int64_t ql_rows, double *discharge, int64_t out_rows,
                              float *discharge32, int64_t factor, int64_t T, int64_t nsub, void *stream);
+
+/* Ensembles: `members` RapidMuskingum calls over the same period on one plan -- same network, coefficients and shape, each member
+ * with its own lateral rows, discharge rows and initial state -- routed together on the time-tiled kernel.  One launch runs the
+ * (tile, member) tasks of every member, so the pipeline's fill and drain (rr_plan_reserve's info[6] ticks) is paid once per group
+ * instead of once per member, and a network of a few hundred tiles still fills the card.  Member m's results are bit for bit those of
+ * rr_rapid_route_dev / _f32_dev / _f32in_dev on member m's rows (time-tiled) -- with one exception at one sub-step
+ * per row: the batched call runs the general tick there where a single-member call runs the short one (RR_TILE_LEAN), whose sums of
+ * three upstream values may differ in the sign of a zero (-0.0 against +0.0) when every term is a negative zero.
+ * rr_plan_reserve_ensemble: the work memory of such calls (one record ring per member, and the members' carried state); flags:
+ * RR_ROWS_F32_IN (float32 lateral rows) | RR_ROWS_F32_OUT (float32 discharge rows).  info as rr_plan_reserve's ([0] is 1), plus
+ * [8] the largest member count whose record rings fit the card at this shape (reserve and route groups of at most that many).
+ * rr_rapid_route_ensemble_dev only enqueues.  Rows are whole calls: member m's T lateral rows (float64, or float32 with lateral_is_f32)
+ * start at lateral + m * lateral_member_pitch elements; its discharge rows at discharge + m * discharge_member_pitch elements: T float64
+ * rows, or with discharge_is_f32 T / factor float32 rows, each the mean of `factor` routed rows (as rr_rapid_route_f32_dev).  q_t holds
+ * member m's initial state at q_t + m * q_pitch on entry, its final state on return.  RR_E_INVALID: members < 1 (or > 65535), a null
+ * array, a pitch shorter than a member; RR_E_STATE: more than was reserved (the message names the rr_plan_reserve_ensemble call to
+ * make); RR_E_UNSUPPORTED, with the reason: the call would not get the time-tiled kernel -- per-edge weights, T x nsub < 32, a plan
+ * with boundary reaches, or record rings too large for the card (fewer members per call). */
+#define RR_ROWS_F32_IN 16
+int rr_plan_reserve_ensemble(rr_plan *plan, int64_t members, int64_t T, int64_t nsub, int flags, int64_t info[9]);
+int rr_rapid_route_ensemble_dev(rr_plan *plan, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
+                                int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                                int64_t factor, int64_t T, int64_t nsub, void *stream);
 int rr_muskingum_route_f32_dev(rr_plan *plan, double *q_t, float *discharge32, int64_t num_output_steps,
                                int64_t num_routing_per_output, void *stream);
 int rr_unit_route_f32_dev(rr_plan *plan, double *q_ch, double *q_full, const double *convolved_lateral, int64_t conv_rows,

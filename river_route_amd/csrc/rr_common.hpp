@@ -20,7 +20,7 @@
 #include "../../include/rr_hip.h"
 #include "rr_plan.hpp"
 
-#define RR_VERSION_NUM 200
+#define RR_VERSION_NUM 210
 
 namespace {
 

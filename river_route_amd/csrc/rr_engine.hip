@@ -53,7 +53,7 @@ void rr_plan_destroy(rr_plan *P)
                         P->d_c3, P->d_c4, P->d_x, P->d_isum, P->d_qch, P->d_a2, P->d_c1own, P->d_z, P->d_ring, P->d_stage, P->d_mrows,
                         P->d_slot_a[0], P->d_slot_a[1], P->d_slot_b[0], P->d_slot_b[1], P->d_m_index[0], P->d_m_index[1],
                         P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef, P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch,
-                        P->d_kholemeta, P->d_kghostmeta};
+                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi};
         for (void *p : ptrs) if (p) (void)hipFree(p);
         P->pipe.destroy();
         for (hipEvent_t e : P->ev) (void)hipEventDestroy(e);
@@ -117,6 +117,11 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
                                     (int)tile_lds_bytes(P->wave_threads)) != hipSuccess) {
                 (void)hipGetLastError();
                 P->wave_enabled = false;
+            }
+        for (int v = 0; v < 2; ++v)    // the same for the member-batched forms (ensembles)
+            if (hipFuncSetAttribute((const void *)tile_ens_kernel(v == 1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(kTileThreads)) != hipSuccess) {
+                (void)hipGetLastError();
+                P->ens_enabled = false;
             }
         if (const char *e2 = getenv("RR_UH_PAIRS")) P->uh_pairs = atoi(e2) != 0;
         for (int v = 0; v < 4; ++v)
@@ -244,7 +249,7 @@ int rr_plan_direct_layout(const rr_plan *P, int32_t *tile_c0, int32_t *tile_nc, 
 int rr_plan_last_kernel(const rr_plan *P)
 {
     if (!P) return -1;
-    return (int)P->ses.kernel;
+    return P->ses.members > 0 ? RR_KERNEL_TILE_ENSEMBLE : (int)P->ses.kernel;
 }
 
 int rr_plan_set_options(rr_plan *P, int64_t rows_per_chunk, int64_t sample_every)
@@ -372,6 +377,78 @@ int rr_plan_reserve(rr_plan *P, int mode, int64_t T, int64_t nsub, int host_rows
         info[5] = piped ? 2 * HostPipe::kPinned * P->pipe.pin_cap * (int64_t)sizeof(double) : 0;
         info[6] = P->h.depth - 1 + levels * sch.KC * kRec;      // pipeline depth in ticks
         info[7] = sch.ring * (int64_t)sizeof(double);
+    }
+    return RR_OK;
+}
+
+// ---- ensembles (rr_rapid_route_ensemble_dev) ----
+
+// Why an ensemble call of this shape does not get the time-tiled kernel, or NULL (record rings that do not fit: ensemble_member_cap).
+static const char *ensemble_unsupported(const rr_plan *P, int64_t T, int64_t nsub)
+{
+    if (!P->weights_uniform) return "per-edge weights (the time-tiled kernel keeps one upstream weight per reach)";
+    if (T * nsub < 32) return "fewer than 32 routing sub-steps (T x nsub) in a call";
+    if (P->n_ghost > 0 || P->n_export > 0) return "the plan has boundary reaches (a partitioned network)";
+    if (!P->tp.ok || !P->wave_enabled || !P->ens_enabled || P->wave_threads != kTileThreads || P->export_inside || P->tp.np >= (int64_t{1} << 25)) return "the network does not take the time-tiled kernel";
+    return nullptr;
+}
+
+static CallShape ensemble_shape(int64_t members, int64_t T, int64_t nsub, bool in32, bool out32, int64_t factor)
+{
+    CallShape s;
+    s.mode = Mode::Rapid; s.T = T; s.nsub = nsub; s.in32 = in32; s.out32 = out32; s.factor = factor; s.members = members;
+    return s;
+}
+
+// The largest member count whose record rings fit the card at this shape (choose_schedule keeps to the time-tiled kernel: the ring
+// only grows with the members).
+static int64_t ensemble_member_cap(const rr_plan *P, CallShape s)
+{
+    int64_t lo = 0, hi = 65535;      // (the member is blockIdx.y)
+    while (lo < hi) {
+        const int64_t mid = (lo + hi + 1) / 2;
+        s.members = mid;
+        const Schedule sch = choose_schedule(P, s);      // (k_tile<..., ENS> addresses member m's ring chunks and state positions in 32 bits)
+        if (sch.kernel == Kernel::Tile && mid * sch.chunks < (int64_t{1} << 32) && mid * P->tp.np < (int64_t{1} << 31)) lo = mid; else hi = mid - 1;
+    }
+    return lo;
+}
+
+int rr_plan_reserve_ensemble(rr_plan *P, int64_t members, int64_t T, int64_t nsub, int flags, int64_t info[9])
+{
+    int rc = need_device(P);
+    if (rc) return rc;
+    if (members < 1 || members > 65535 || T < 0 || nsub < 1) return fail(RR_E_INVALID, "rr_plan_reserve_ensemble: need 1 <= members <= 65535, T >= 0 and sub-steps >= 1");
+    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_plan_reserve_ensemble before rr_plan_set_coeffs");
+    if (P->ses.open) return fail(RR_E_STATE, "rr_plan_reserve_ensemble: a routing call is open");
+    if (info) for (int k = 0; k < 9; ++k) info[k] = 0;
+    if (P->h.n == 0 || T == 0) return RR_OK;
+    if (const char *why = ensemble_unsupported(P, T, nsub)) return fail(RR_E_UNSUPPORTED, std::string("rr_plan_reserve_ensemble: ") + why);
+    const CallShape shape = ensemble_shape(members, T, nsub, (flags & RR_ROWS_F32_IN) != 0, (flags & RR_ROWS_F32_OUT) != 0, 1);
+    const int64_t cap = ensemble_member_cap(P, shape);
+    if (info) info[8] = cap;
+    if (members > cap)
+        return fail(RR_E_UNSUPPORTED, "rr_plan_reserve_ensemble: the record rings of " + std::to_string(members) + " members do not fit the card at this shape; at most " +
+                                          std::to_string(cap) + " per call");
+    Schedule sch;
+    rc = reserve_core(P, shape, &sch);
+    if (rc) return rc;
+    if (P->ens_cap < members) {      // the members' carried state, np apart
+        for (double **p : {&P->d_esq, &P->d_ess, &P->d_esi}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        P->ens_cap = 0;
+        const int64_t count = members * P->tp.np;
+        rc = dev_alloc(&P->d_esq, count);
+        if (!rc) rc = dev_alloc(&P->d_ess, count);
+        if (!rc) rc = dev_alloc(&P->d_esi, count);
+        if (rc) return rc;
+        P->ens_cap = members;
+    }
+    if (info) {
+        info[0] = (int)sch.kernel; info[1] = sch.KC * kRec; info[2] = sch.chunks;
+        info[3] = (P->ring_cap + P->mrows_cap + P->stage_cap) * (int64_t)sizeof(double);
+        info[6] = P->h.depth - 1 + P->tp.n_levels * sch.KC * kRec;
+        info[7] = sch.ring * (int64_t)sizeof(double);
+        info[8] = cap;
     }
     return RR_OK;
 }
@@ -675,6 +752,49 @@ int rr_rapid_route_f32in_dev(rr_plan *P, double *q_t, const float *qlateral32, i
     if (P->h.n > 0 && T > 0 && (!q_t || !qlateral32 || ql_rows < 1 || !out))
         return fail(RR_E_INVALID, "rr_rapid_route_f32in_dev: null array, empty row count, or both or neither output");
     return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false, "rr_rapid_route_f32in_dev");
+}
+
+int rr_rapid_route_ensemble_dev(rr_plan *P, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
+                                int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                                int64_t factor, int64_t T, int64_t nsub, void *stream)
+{
+    int rc = check_route_args(P, true, T, nsub);
+    if (rc) return rc;
+    const int64_t n = P->h.n;
+    if (members < 1 || members > 65535) return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: need 1 <= members <= 65535");
+    if (n == 0 || T == 0) return RR_OK;
+    if (!q_t || !lateral || !discharge) return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: null array");
+    if (discharge_is_f32 && (factor < 1 || T % factor != 0))
+        return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: float32 output: the number of rows must be a multiple of factor >= 1");
+    const int64_t out_rows = discharge_is_f32 ? T / factor : T;
+    if (q_pitch < n || lateral_member_pitch < T * n || discharge_member_pitch < out_rows * n)
+        return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: a pitch is shorter than a member (q_pitch >= n, lateral pitch >= T n, discharge pitch >= rows x n)");
+    if (const char *why = ensemble_unsupported(P, T, nsub)) return fail(RR_E_UNSUPPORTED, std::string("rr_rapid_route_ensemble_dev: ") + why);
+    Rows io;
+    if (lateral_is_f32) io.dev_in32 = (const float *)lateral; else io.dev_in = (const double *)lateral;
+    io.rows_in = T;
+    if (discharge_is_f32) { io.dev_out32 = (float *)discharge; io.out_factor = factor; } else io.dev_out = (double *)discharge;
+    io.rows_out = out_rows;
+    io.members = members; io.in_pitch = lateral_member_pitch; io.out_pitch = discharge_member_pitch;
+    const CallShape shape = call_shape(Mode::Rapid, T, nsub, io);
+    if (members > ensemble_member_cap(P, shape))
+        return fail(RR_E_UNSUPPORTED, "rr_rapid_route_ensemble_dev: the record rings of " + std::to_string(members) + " members do not fit the card; route fewer per call "
+                                      "(rr_plan_reserve_ensemble's info[8])");
+    rc = prepare_call(P, shape, "rr_rapid_route_ensemble_dev");
+    if (rc) return rc;
+    if (P->ens_cap < members)
+        return fail(RR_E_STATE, "the carried state of " + std::to_string(members) + " members was not reserved: call rr_plan_reserve_ensemble(plan, " + std::to_string(members) +
+                                ", " + std::to_string(T) + ", " + std::to_string(nsub) + ", ...) first; rr_rapid_route_ensemble_dev only enqueues work");
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t np = P->tp.np;
+    hipLaunchKernelGGL(k_tile_state_in_ens, dim3((unsigned)((np + kBlock - 1) / kBlock), (unsigned)members), dim3(kBlock), 0, st, P->d_esq, P->d_ess, P->d_esi,
+                       (const double *)q_t, q_pitch, (const int32_t *)P->d_tperm, (const int4 *)P->d_pmeta, (int32_t)np);
+    rc = route_core(P, Mode::Rapid, T, nsub, io, st);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_tile_state_out_ens, dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)members), dim3(kBlock), 0, st, q_t, q_pitch,
+                       (const double *)P->d_esq, np, (const int32_t *)P->d_tinv, (int32_t)n);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
 }
 
 int rr_muskingum_route_f32_dev(rr_plan *P, double *q_t, float *discharge32, int64_t n_out, int64_t n_per_out, void *stream)

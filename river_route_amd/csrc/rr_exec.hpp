@@ -25,6 +25,9 @@ struct Rows {
     int64_t uh_nks = 0;
     // RapidMuskingum fed by gridded runoff: no lateral rows at all, the weights product runs in the in-pass (k_rec_in_runoff)
     const RunoffArgs *runoff = nullptr;
+    // an ensemble call (rr_rapid_route_ensemble_dev): `members` sets of rows, member m's at m * in_pitch / m * out_pitch elements from
+    // the first member's (0: a single-member call)
+    int64_t members = 0, in_pitch = 0, out_pitch = 0;
 };
 
 // What a route call hands over, as far as the choice of its kernel is concerned.  Built in two places only -- call_shape (from the
@@ -40,6 +43,7 @@ struct CallShape {
     bool uh = false;             // UnitMuskingum with the unit-hydrograph convolution fused in: the rows are runoff depths
     bool runoff = false;         // gridded runoff: no lateral rows, the in-pass makes them
     int64_t ring_in = 0, ring_out = 0;      // streaming calls (rr_stream_begin*): rows of the caller's cyclic lateral / discharge arrays
+    int64_t members = 0;         // ensemble calls: members routed together on the time-tiled kernel, one record ring each (0: a single-member call)
 };
 
 // streaming k_tick over rows, time-tiled k_tile over records, the direct row path (rr_plan_last_kernel, rr_plan_reserve's info[0])
@@ -51,7 +55,7 @@ struct Schedule {
     int64_t KC = 1;                   // record chunks per task (Tile); rows per task / 16 (Direct)
     int64_t KS = 1;                   // Direct: record chunks per task of the skeleton's launches
     int64_t chunks = 0;               // chunks of the record ring (Tile), of the skeleton's record ring (Direct)
-    int64_t ring = 0;                 // doubles of P->d_ring: record ring, or the work rows of the streaming kernel
+    int64_t ring = 0;                 // doubles of P->d_ring: record ring (an ensemble's: one per member), or the work rows of the streaming kernel
     int64_t mrows = 0, stage = 0;     // doubles of the intermediate rows (streaming permutation, convolved rows) / of the host staging rows
 };
 
@@ -89,6 +93,8 @@ struct Session {
     bool bracket_open = false;
     int64_t bracket_reaches = 0;
     size_t max_samples = 0;
+    int64_t members = 0;          // an ensemble call (Rows::members): member m's record ring at m * ring_stride doubles
+    int64_t ring_stride = 0;
 };
 
 // ---- host-pointer calls: PCIe pipeline around the time-tiled kernel ----
@@ -151,6 +157,7 @@ struct rr_plan {
     // time-tiled routing (k_tile): subtree tiles of rr::TilePlan
     rr::TilePlan tp;
     bool wave_enabled = true, wave_forced = false, weights_uniform = false;
+    bool ens_enabled = true;     // the member-batched k_tile forms got their LDS (rr_plan_create)
     int wave_threads = 512;
     int64_t wave_K = 0;          // ticks per task (multiple of 16); 0 = chosen per call
     Schedule sch;                // prepare_call: the schedule of the call about to start (or running, or just ended)
@@ -165,6 +172,8 @@ struct rr_plan {
     std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
     int32_t n_wide_tiles = 0;        // tiles with a reach of more than three upstream reaches: general kernel beside the LEAN one
     double *d_sq = nullptr, *d_ss = nullptr, *d_si = nullptr, *d_sqch = nullptr;
+    double *d_esq = nullptr, *d_ess = nullptr, *d_esi = nullptr;      // the carried state of an ensemble's members, np apart
+    int64_t ens_cap = 0;             // members they have room for (rr_plan_reserve_ensemble)
     double *d_full = nullptr, *d_chan = nullptr;   // UnitMuskingum state scattered to params order
     int2 *d_colmeta = nullptr;   // per params column {position, lag}
     int2 *d_ghostmeta = nullptr; // the same per boundary ghost (column of the ghost series)
@@ -488,6 +497,7 @@ CallShape call_shape(Mode mode, int64_t T, int64_t nsub, const Rows &io, bool st
     s.out32 = io.dev_out32 != nullptr; s.factor = io.out_factor;
     s.uh = io.uh_kernel != nullptr;
     s.runoff = io.runoff != nullptr;
+    s.members = io.members;
     if (stream) { s.ring_in = mode == Mode::Muskingum ? 0 : io.rows_in; s.ring_out = io.rows_out; }
     return s;
 }
@@ -529,7 +539,7 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
     // UnitMuskingum (float64 rows of convolved lateral inflow, no boundary reaches) takes it as well.
     const bool unit_direct = mode == Mode::Unit && nsub <= kDirectMaxSub && P->n_ghost == 0 && P->n_export == 0 && !P->unit_general && P->tp.ok &&
                              (!s.uh || (P->uh_rows_ok && (P->dev_total_bytes == 0 || T * n * 8 <= (int64_t)(P->dev_total_bytes / 3))));
-    if (s.dev_rows && P->direct_enabled && P->dp.ok && (mode != Mode::Unit || unit_direct) && nsub <= kDirectMaxSub && (nsub == 1 || P->n_ghost == 0) &&
+    if (s.members == 0 && s.dev_rows && P->direct_enabled && P->dp.ok && (mode != Mode::Unit || unit_direct) && nsub <= kDirectMaxSub && (nsub == 1 || P->n_ghost == 0) &&
         P->weights_uniform && P->wave_enabled && total >= 8 && n < (int64_t{1} << 29)) {
         int64_t K = pick_direct_K(P, T);
         const int64_t levels = P->dp.skel.n_levels, np = P->dp.skel.np;
@@ -561,7 +571,7 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
               !P->export_inside && P->kc_cap >= 1 && !(mode == Mode::Unit && P->unit_general);
     if (ok && !P->wave_forced) ok = total >= 32;
     if (ok) {
-        const int64_t np = P->tp.np, levels = P->tp.n_levels;
+        const int64_t np = P->tp.np, levels = P->tp.n_levels, members = std::max<int64_t>(1, s.members);      // an ensemble: the card's budget holds every member's ring
         const int64_t all_chunks = kRecBatch * ((total + 14) / kRecRows + 2) + (dmax >> 4) + 2;
         const int64_t slack = 4;      // room for the in-pass to run ahead of the routing: four batches of 128 tick-rows
         ok = false;
@@ -571,12 +581,12 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
         const int64_t kc_long = P->n_export > 0 && P->wave_K <= 0 ? 4 : (int64_t{1} << 20);
         for (int64_t KC = std::min(std::min(pick_KC(P, total + dmax), P->kc_cap), kc_long); KC >= 1; KC /= 2) {
             const int64_t chunks = std::min<int64_t>(all_chunks, (dmax + levels * KC * kRec) / kRec + slack * kRecBatch);
-            const int64_t bytes = chunks * kRec * np * (int64_t)sizeof(double);
+            const int64_t bytes = chunks * kRec * np * (int64_t)sizeof(double) * members;
             // five eighths of the card; the shortest tasks may take thirteen sixteenths: the streaming kernel, the only alternative,
             // keeps depth x n work rows itself (1M reaches 24k deep: 204 GB of records at K = 16 against 192 GB of rows)
             if (P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 16 * (KC == 1 ? 13 : 10))) continue;
             if (KC > 4 && P->wave_K <= 0 && P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 5)) continue;      // long tasks only while the ring stays under a fifth of the card
-            sch.kernel = Kernel::Tile; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np;
+            sch.kernel = Kernel::Tile; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np * members;
             ok = true;
             break;
         }
@@ -610,6 +620,7 @@ int reserve_core(rr_plan *P, const CallShape &s, Schedule *out)
         (void)hipGetLastError();
         if (sch.kernel == Kernel::Direct) return fail(RR_E_ALLOC, "route: the skeleton's record ring does not fit on the device");
         if (sch.kernel == Kernel::Tick) return fail(RR_E_ALLOC, "route: the work rows of the streaming kernel do not fit on the device");
+        if (s.members > 0) return fail(RR_E_ALLOC, "route: the record rings of " + std::to_string(s.members) + " ensemble members do not fit on the device");      // (kc_cap is the plan's: a smaller group is the remedy)
         P->kc_cap = sch.KC / 2;      // shorter tasks, a smaller ring; 0: this plan streams
     }
     int rc = ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows);
@@ -647,7 +658,8 @@ int prepare_call(rr_plan *P, const CallShape &s, const char *who)
     if (P->h.n > 0 && s.T > 0 && (sch.ring > P->ring_cap || sch.mrows > P->mrows_cap || sch.stage > P->stage_cap || !P->ev_first || P->ev.size() < 2 * samples ||
                                   (sch.kernel == Kernel::Tick && !P->perm_ready && sch.mrows > 0)))
         return fail(RR_E_STATE, "this call needs " + std::to_string((sch.ring + sch.mrows + sch.stage) * 8) + " bytes of work memory on the device (" +
-                                    std::to_string((P->ring_cap + P->mrows_cap + P->stage_cap) * 8) + " reserved): call rr_plan_reserve(plan, mode, " +
+                                    std::to_string((P->ring_cap + P->mrows_cap + P->stage_cap) * 8) + " reserved): call " +
+                                    (s.members > 0 ? "rr_plan_reserve_ensemble(plan, " + std::to_string(s.members) + ", " : std::string("rr_plan_reserve(plan, mode, ")) +
                                     std::to_string(s.T) + ", " + std::to_string(s.nsub) + ", ...) first; the *_dev entry points only enqueue work");
     P->sch = sch;
     return RR_OK;
@@ -667,6 +679,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     if (S.open) return fail(RR_E_STATE, "a routing call is already open on this plan (rr_stream_end it first)");
     S = Session();
     S.mode = mode; S.T = T; S.nsub = nsub; S.total = T * nsub; S.io = io; S.stream = stream;
+    S.members = io.members;
     S.ghost_series = ghost_series; S.export_series = export_series;
     const int64_t dmax = H.depth - 1;
     S.total_ticks = S.total + dmax;
@@ -682,7 +695,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     P->prof_launches = P->prof_samples = P->prof_brackets = 0;
     P->aux_kind.clear();
     for (int k = 0; k < rr_plan::kAuxKinds; ++k) P->aux_launches[k] = 0;
-    P->prof_reach_steps = n * S.total;
+    P->prof_reach_steps = n * S.total * std::max<int64_t>(1, S.members);
     P->ev_reaches.clear();
     P->last_stream = stream;
     S.open = true;
@@ -744,6 +757,11 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         w.tiles = P->d_tmeta; w.pos = P->d_pmeta; w.coef = P->d_coef;
         w.sq = P->d_sq; w.ss = P->d_ss; w.si = P->d_si; w.sqch = P->d_sqch;
         w.np = (int32_t)TP.np; w.KC = (int32_t)S.KC;
+        if (S.members > 0) {      // an ensemble: one ring per member, the members' carried state np apart (k_tile<..., ENS>)
+            if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->ring_cap) { S.open = false; return fail(RR_E_STATE, "route: the ensemble was not reserved"); }
+            S.ring_stride = S.rec_chunks * kRec * TP.np;
+            w.sq = P->d_esq; w.ss = P->d_ess; w.si = P->d_esi; w.sqch = nullptr;
+        }
     }
     if (S.kernel != Kernel::Tick) {      // the rest of the k_tile launches' arguments, the plan's tiles' or the skeleton's
         TileArgs &w = S.ta;
@@ -915,6 +933,29 @@ tile_kernel_t tile_kernel(bool unit, bool sub, bool lean = false, bool nolat = f
                 : (sub ? (tile_kernel_t)k_tile<T, false, true> : (lean ? (tile_kernel_t)k_tile<T, false, false, true> : (tile_kernel_t)k_tile<T, false, false>));
 }
 
+// RapidMuskingum's k_tile forms, member-batched: the general tick, with or without sub-steps.  (The short tick's member-batched form needs 72
+// bytes of scratch at 128 VGPRs -- the member's chunk and position offsets tip it over -- so an ensemble with one sub-step per row runs the
+// general tick on every tile, as RR_TILE_LEAN=0 does: the same multiply-adds on the same sums, which can differ only in the sign of a zero.)
+tile_kernel_t tile_ens_kernel(bool sub)
+{
+    constexpr int T = kTileThreads;
+    return sub ? (tile_kernel_t)k_tile<T, false, true, false, false, true> : (tile_kernel_t)k_tile<T, false, false, false, false, true>;
+}
+
+// An ensemble's launch (k_tile<..., ENS>): the tasks of every member, member on the grid's second dimension.  The workgroups of one member
+// walk its tiles as k_tile's do; together the members' take the slots one member's would (fewer tiles each: the card fills with
+// (tile, member) tasks however few tiles the network has).
+void launch_tile_diag_ens(rr_plan *P, const TileArgs &w, int64_t tiles)
+{
+    Session &S = P->ses;
+    const int64_t slots = (int64_t)P->cu_count * (1024 / kTileThreads);
+    const dim3 g((unsigned)std::min<int64_t>(tiles, std::max<int64_t>(1, (slots + S.members - 1) / S.members)), (unsigned)S.members);
+    const size_t lds_bytes = tile_lds_bytes(kTileThreads);
+    TileArgs e = w;      // (member m's ring: chunks [m C, (m + 1) C); its state: positions [m np, (m + 1) np))
+    e.tile_filter = 0; e.coef = P->d_coef;
+    hipLaunchKernelGGL(tile_ens_kernel(S.nsub > 1), g, dim3((unsigned)kTileThreads), lds_bytes, S.stream, e);
+}
+
 // Launch d of the time-tiled schedule: the tasks (tile, macro-chunk d - level) of every tile whose macro-chunk exists.
 // Tiles are stored by level, so they are one contiguous range; a tile with no active position returns at once.
 // TP / w / wide tiles: the plan's own tiles, or the skeleton of the direct row path (its levels start at 1).
@@ -947,12 +988,16 @@ int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_
     // the tiles the short tick does not take (a reach with more than three upstream reaches); RR_TILE_LEAN=0: the general one
     const bool unit = S.mode == Mode::Unit;
     const bool lean = S.nsub == 1 && P->lean_enabled;      // every router's default (dt_routing = dt_runoff); sub-steps keep the general tick
-    w.tile_filter = lean ? 1 : 0;
-    w.coef = (lean && unit) ? coef_unit : coef;
-    hipLaunchKernelGGL(tile_kernel(unit, S.nsub > 1, lean, S.mode == Mode::Muskingum), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
-    if (lean && n_wide > 0) {
-        w.tile_filter = 2; w.coef = coef;
-        hipLaunchKernelGGL(tile_kernel(unit, false, false), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
+    if (S.members > 0) {
+        launch_tile_diag_ens(P, w, t_hi - t_lo);
+    } else {
+        w.tile_filter = lean ? 1 : 0;
+        w.coef = (lean && unit) ? coef_unit : coef;
+        hipLaunchKernelGGL(tile_kernel(unit, S.nsub > 1, lean, S.mode == Mode::Muskingum), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
+        if (lean && n_wide > 0) {
+            w.tile_filter = 2; w.coef = coef;
+            hipLaunchKernelGGL(tile_kernel(unit, false, false), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
+        }
     }
     if (sample) {
         HIPCHK(hipEventRecord(P->ev[2 * P->prof_brackets + 1], S.stream));
@@ -964,7 +1009,7 @@ int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_
             if (m < 0 || m >= S.n_macro || m * K >= TP.tile_lag_hi[c] + S.total || (m + 1) * K <= TP.tile_lag_lo[c]) continue;
             moved += TP.tile_ptr[c + 1] - TP.tile_ptr[c];
         }
-        P->ev_reaches.push_back(moved * K);
+        P->ev_reaches.push_back(moved * K * std::max<int64_t>(1, S.members));
         P->prof_samples += K;
         ++P->prof_brackets;
     }
@@ -1057,7 +1102,26 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     const bool sub = S.nsub > 1;
     hipStream_t st = rec_stream(P);
     const int aux = aux_begin(P, in ? 0 : 1, st);
-    if (in && S.io.runoff) {
+    if (S.members > 0) {      // an ensemble: every member's rows in one launch, member on the grid's second dimension
+        const RecEnsArgs e{ra, S.ring_stride, in ? S.io.in_pitch : S.io.out_pitch};      // (in32 / out32 rows: the pitch counts float32 elements)
+        const dim3 ge((unsigned)((n + kRecInCols - 1) / kRecInCols), (unsigned)S.members);
+        if (in && ra.rows_in32) {
+            if (sub) hipLaunchKernelGGL((k_rec_in<true, true, true>), ge, dim3(kRecInThreads), 0, st, e);
+            else hipLaunchKernelGGL((k_rec_in<false, true, true>), ge, dim3(kRecInThreads), 0, st, e);
+        } else if (in) {
+            if (sub) hipLaunchKernelGGL((k_rec_in<true, false, true>), ge, dim3(kRecInThreads), 0, st, e);
+            else hipLaunchKernelGGL((k_rec_in<false, false, true>), ge, dim3(kRecInThreads), 0, st, e);
+        } else {
+            const dim3 go((unsigned)((n + kRecOutCols - 1) / kRecOutCols), (unsigned)S.members);
+            if (ra.rows32) {
+                if (sub) hipLaunchKernelGGL((k_rec_out<true, true, true>), go, dim3(kRecOutThreads), 0, st, e);
+                else hipLaunchKernelGGL((k_rec_out<false, true, true>), go, dim3(kRecOutThreads), 0, st, e);
+            } else {
+                if (sub) hipLaunchKernelGGL((k_rec_out<true, false, true>), go, dim3(kRecOutThreads), 0, st, e);
+                else hipLaunchKernelGGL((k_rec_out<false, false, true>), go, dim3(kRecOutThreads), 0, st, e);
+            }
+        }
+    } else if (in && S.io.runoff) {
         const dim3 gr((unsigned)((n + kRunoffInThreads - 1) / kRunoffInThreads), (unsigned)kRecBatch);
         if (S.io.runoff->is_f32) hipLaunchKernelGGL(k_rec_in_runoff<float>, gr, dim3(kRunoffInThreads), 0, st, ra, *S.io.runoff);
         else hipLaunchKernelGGL(k_rec_in_runoff<double>, gr, dim3(kRunoffInThreads), 0, st, ra, *S.io.runoff);

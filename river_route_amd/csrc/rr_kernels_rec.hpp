@@ -40,6 +40,24 @@ struct RecPermArgs {
     uint32_t in32_sel, out32_sel;   // byte selectors of the float32 rows (rr_plan_set_row_format): kSelNative, or kSelSwap for a big-endian file's rows
 };
 
+// Ensembles (rr_kernels_tile.hpp: member_chunk0): member blockIdx.y has its rows at m * row_pitch elements from the first member's and its record
+// ring at m * ring_stride doubles; the member-batched passes (ENS) are the single-member ones on those.
+struct RecEnsArgs : RecPermArgs {
+    int64_t ring_stride, row_pitch;
+};
+template <bool ENS> using RecArgsOf = typename std::conditional<ENS, RecEnsArgs, RecPermArgs>::type;
+__device__ __forceinline__ const RecPermArgs &member_args(const RecPermArgs &a) { return a; }
+__device__ __forceinline__ RecPermArgs member_args(const RecEnsArgs &e)      // the pass's rows: k_rec_in's source (float64 or float32), k_rec_out's destination
+{
+    RecPermArgs a = e;
+    const int64_t m = blockIdx.y;
+    a.rec += m * e.ring_stride;
+    a.rows.base += m * e.row_pitch;
+    if (a.rows_in32) a.rows_in32 += m * e.row_pitch;
+    if (a.rows32) a.rows32 += m * e.row_pitch;
+    return a;
+}
+
 constexpr int32_t kColHeadwater = 1 << 30;      // colmeta[].y: lag | this flag
 
 constexpr int kRecTileRows = 16 * kRecBatch + 15;      // tick-rows behind one batch of records
@@ -113,9 +131,10 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
 // scale travelling with the rows into LDS (no registers held across the stores).  The rows alone read in 186 us per 128 rows at 1M
 // reaches, the records alone store in 199 us, the pass takes 415: within 7 % of the two one after the other
 // (profiles/r03_rec_probe.txt, r03_alias_kernel_times.txt).
-template <bool SUB, bool IN32 = false>
-__global__ __launch_bounds__(kRecInThreads) void k_rec_in(const RecPermArgs a)
+template <bool SUB, bool IN32 = false, bool ENS = false>
+__global__ __launch_bounds__(kRecInThreads) void k_rec_in(const RecArgsOf<ENS> args)
 {
+    const RecPermArgs &a = member_args(args);
     constexpr int R = kRecTileRows;
     __shared__ double tile[R * (kRecInCols + 1)];
     __shared__ int2 smeta[kRecInCols];
@@ -297,9 +316,10 @@ __global__ __launch_bounds__(uh_threads(BATCHES)) void k_rec_in_uh(const RecPerm
 // OUT32: the router's post-processing fused in (TransformMuskingum.py:128-142): mean over `factor` consecutive rows
 // (sequential sum, one division, as numpy reduces a strided axis) and the float32 cast; 128 % (factor * nsub) == 0.
 // One column tile per workgroup, every record read of it in flight at once.
-template <bool SUB, bool OUT32>
-__global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecPermArgs a)
+template <bool SUB, bool OUT32, bool ENS = false>
+__global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS> args)
 {
+    const RecPermArgs &a = member_args(args);
     constexpr int S = 16 * (kRecBatch + 1);
     __shared__ double recs[kRecOutCols][S + 1];
     const int tid = threadIdx.x;

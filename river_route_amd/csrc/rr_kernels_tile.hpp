@@ -47,6 +47,19 @@ struct TileArgs {
     double inv_nsub;
 };
 
+// ---- ensembles: members routed together on one plan (rr_rapid_route_ensemble_dev) ----
+//
+// The members share every read-only array of the plan (tiles, positions, coefficients, lags) and nothing else.  Member m's record ring
+// is chunks [m C, (m + 1) C) of one ring of M C chunks (C = rec_chunks), its carried state positions [m np, (m + 1) np) of arrays of
+// M np.  The member-batched kernels (template flag ENS) take the member from blockIdx.y and run the single-member code on that
+// member's chunks, state and rows, operation for operation: a launch's tasks are (tile, member) pairs, and the tiles' constants, read
+// by every member, come from L2 / MALL after the first.  RapidMuskingum only: no exports, no UnitMuskingum state.  Both offsets are
+// 32-bit (rr_plan_reserve_ensemble caps M C below 2^32 and M np below 2^31) and uniform: they stay in scalar registers.  k_tile uses
+// them as (ENS ? index + offset : index): with a constant condition only the live arm is emitted, so the single-member kernels compile
+// to what they were before ensembles existed.
+__device__ __forceinline__ uint32_t member_chunk0(const TileArgs &a) { return blockIdx.y * a.rec_chunks.d; }
+__device__ __forceinline__ int32_t member_pos0(const TileArgs &a) { return (int32_t)blockIdx.y * a.np; }
+
 // LDS-only workgroup barrier: waits for this wave's LDS traffic, not for its global loads/stores, so record
 // prefetches stay in flight across ticks (__syncthreads() would drain vmcnt every tick).
 __device__ __forceinline__ void barrier_lds() { asm volatile("s_waitcnt lgkmcnt(0)\n\ts_barrier" ::: "memory"); }
@@ -127,7 +140,8 @@ constexpr size_t tile_lds_bytes(int threads)
 // one (the two do not fit one kernel: with the record buffers in 64 of 128 registers the allocator spills the records in flight).
 // NOLAT (short tick only): channel-only routing (Muskingum.py:262-290) -- no lateral rows were turned into records, so a record slot
 // holds whatever the ring held; only a ghost's slot means something (what its reach published).
-template <int TH, bool UNIT, bool SUB, bool LEAN = false, bool NOLAT = false>
+// ENS: an ensemble's member-batched form (see member_chunk0).
+template <int TH, bool UNIT, bool SUB, bool LEAN = false, bool NOLAT = false, bool ENS = false>
 __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 waves per CU: 1,024 / TH workgroups of 128 VGPRs
 {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -140,7 +154,7 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
     if (tid < 2) lds[tid * THP + TH] = 0.0;      // the zero slots; nothing else ever writes them (first barrier: before the first tick)
     auto ring = [&](int32_t chunk) {      // the records of one chunk as a buffer: position p at byte p * kPosBytes (np * kPosBytes < 2^32: choose_schedule)
         const uint32_t c = a.rec_chunks.mod((uint32_t)chunk);
-        return make_rsrc(a.rec + rec_elem(c, a.np, 0), (uint32_t)a.np * kPosBytes);
+        return make_rsrc(a.rec + rec_elem(ENS ? c + member_chunk0(a) : c, a.np, 0), (uint32_t)a.np * kPosBytes);
     };
 
     // A workgroup takes the tiles t_last - blockIdx.x - g * gridDim.x, g = 0, 1, ... of this launch (highest level first:
@@ -209,9 +223,9 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
             s.lg = pm.x; s.up = first_up | (int32_t)((cc & 0xFFFFu) << 16);
             s.xp = pm.z;
             if (UNIT) { s.uh = first_up + (int32_t)(cc >> 16); s.qch = a.sqch[p]; }
-            if (SUB) s.isum = a.si[p];
-            s.s_prev = a.ss[p];
-            s.q = a.sq[p]; s.c1 = a.coef[3 * (int64_t)p]; s.c2 = a.coef[3 * (int64_t)p + 1]; s.c3 = a.coef[3 * (int64_t)p + 2];
+            if (SUB) s.isum = a.si[ENS ? p + member_pos0(a) : p];
+            s.s_prev = a.ss[ENS ? p + member_pos0(a) : p];
+            s.q = a.sq[ENS ? p + member_pos0(a) : p]; s.c1 = a.coef[3 * (int64_t)p]; s.c2 = a.coef[3 * (int64_t)p + 1]; s.c3 = a.coef[3 * (int64_t)p + 2];
         }
     };
     // The first tile: state and coefficients are requested BEFORE the record: memory operations retire in order, so the
@@ -476,9 +490,9 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
         if ((LEAN ? the_lg() : lg) >= 0) {
             const int32_t p = b0 + tid;
             const double *aux = lds + 2 * THP + (TH / 64) * (kStageLanes * kStageStrideOut);
-            a.sq[p] = lds[(size_t)((tau_begin + K - 1) & 1) * THP + tid]; a.ss[p] = (LEAN && UNIT) ? aux[4 * TH + tid] : s_prev;
+            a.sq[ENS ? p + member_pos0(a) : p] = lds[(size_t)((tau_begin + K - 1) & 1) * THP + tid]; a.ss[ENS ? p + member_pos0(a) : p] = (LEAN && UNIT) ? aux[4 * TH + tid] : s_prev;
             if (UNIT) a.sqch[p] = (LEAN && UNIT) ? aux[3 * TH + tid] : qch;
-            if (SUB) a.si[p] = isum;
+            if (SUB) a.si[ENS ? p + member_pos0(a) : p] = isum;
         }
         if (LEAN && has_next) load_state(nxt, st);
         if (!has_next) break;
@@ -552,6 +566,28 @@ __global__ __launch_bounds__(kBlock) void k_tile_state_out(double *q_t, const do
 {
     const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (i < n) q_t[i] = sq[inv[i]];
+}
+
+// k_tile_state_in / k_tile_state_out of an ensemble: member blockIdx.y, its state in q_t at q_pitch doubles from the previous member's,
+// its carried state at np
+__global__ __launch_bounds__(kBlock) void k_tile_state_in_ens(double *sq, double *ss, double *si, const double *q_t, int64_t q_pitch,
+                                                              const int32_t *perm, const int4 *pos, int32_t np)
+{
+    const int32_t p = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (p >= np) return;
+    const int64_t m = blockIdx.y, o = m * np;
+    q_t += m * q_pitch;
+    double s = 0.0;
+    const int4 pm = pos[p];
+    const int32_t u0 = pm.y, u1 = u0 + (int32_t)((uint32_t)pm.w & 0xFFFFu);
+    for (int32_t u = u0; u < u1; ++u) s += q_t[perm[u]];
+    sq[o + p] = q_t[perm[p]]; ss[o + p] = s; si[o + p] = 0.0;
+}
+__global__ __launch_bounds__(kBlock) void k_tile_state_out_ens(double *q_t, int64_t q_pitch, const double *sq, int64_t np, const int32_t *inv, int32_t n)
+{
+    const int32_t i = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    const int64_t m = blockIdx.y;
+    if (i < n) q_t[m * q_pitch + i] = sq[m * np + inv[i]];
 }
 
 }  // namespace

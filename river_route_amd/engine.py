@@ -17,6 +17,7 @@ __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'runoff_to_qlate
 
 
 MODE_RAPID, MODE_MUSKINGUM, MODE_UNIT = 0, 1, 2      # include/rr_hip.h: RR_MODE_*
+REC_BATCH_ROWS = 128      # tick-rows of a record batch: float32 means fused into the out-pass need factor x sub-steps to divide it
 
 
 def _f64(a, name):
@@ -215,8 +216,9 @@ class Plan:
         return out
 
     def last_kernel(self) -> str:
-        """'tick' (streaming), 'tile' (time-tiled over records) or 'direct' (direct row path): what the last call ran."""
-        return ('tick', 'tile', 'direct')[int(_lib.lib().rr_plan_last_kernel(self._h))]
+        """'tick' (streaming), 'tile' (time-tiled over records), 'direct' (direct row path) or 'tile_ensemble' (time-tiled, members
+        batched: rapid_route_ensemble*): what the last call ran."""
+        return ('tick', 'tile', 'direct', 'tile_ensemble')[int(_lib.lib().rr_plan_last_kernel(self._h))]
 
     # -- device-pointer routing (enqueue only) --
     def rapid_route_dev(self, q_t, qlateral, ql_rows, discharge, out_rows, T, num_substeps, stream=None) -> None:
@@ -249,6 +251,75 @@ class Plan:
         self.reserve(MODE_RAPID, T, num_substeps, f32_out=discharge32 is not None)
         check(_lib.lib().rr_rapid_route_f32in_dev(self._h, ptr(q_t), ptr(qlateral32), int(ql_rows), ptr(discharge), int(out_rows),
                                                   ptr(discharge32), int(factor), int(T), int(num_substeps), stream))
+
+    # -- ensembles: members over the same period routed together on the time-tiled kernel (include/rr_hip.h) --
+    def reserve_ensemble(self, members: int, T: int, num_substeps: int = 1, f32_in: bool = False, f32_out: bool = False) -> dict:
+        """rr_plan_reserve_ensemble: work memory of rapid_route_ensemble_dev calls of up to `members` members; members_max is the largest
+        group whose record rings fit the card at this shape."""
+        info = np.zeros(9, dtype=np.int64)
+        check(_lib.lib().rr_plan_reserve_ensemble(self._h, int(members), int(T), int(num_substeps), (16 if f32_in else 0) | (4 if f32_out else 0), ptr(info)))
+        return dict(tiled=int(info[0]) == 1, ticks_per_launch=int(info[1]), ring_chunks=int(info[2]), work_bytes=int(info[3]),
+                    pipeline_ticks=int(info[6]), ring_bytes=int(info[7]), members_max=int(info[8]))
+
+    def rapid_route_ensemble_dev(self, members, q_t, q_pitch, lateral, lateral_is_f32, lateral_member_pitch, discharge, discharge_is_f32,
+                                 discharge_member_pitch, factor, T, num_substeps, stream=None) -> None:
+        """rr_rapid_route_ensemble_dev (enqueue only): member m's rows at m * pitch elements, its state at q_t + m * q_pitch."""
+        self.reserve_ensemble(members, T, num_substeps, f32_in=bool(lateral_is_f32), f32_out=bool(discharge_is_f32))
+        check(_lib.lib().rr_rapid_route_ensemble_dev(self._h, int(members), ptr(q_t), int(q_pitch), ptr(lateral), int(bool(lateral_is_f32)),
+                                                     int(lateral_member_pitch), ptr(discharge), int(bool(discharge_is_f32)), int(discharge_member_pitch),
+                                                     int(factor), int(T), int(num_substeps), stream))
+
+    def rapid_route_ensemble(self, q_t, qlateral, discharge, num_substeps: int, factor: int = 1) -> np.ndarray:
+        """Host arrays: qlateral (M, T, n) float64 or float32; q_t (n,) -- every member starts there -- or (M, n); discharge (M, T, n)
+        float64, or (M, T / factor, n) float32 (each row the mean of `factor` routed rows).  Returns the (M, n) final states.  The members
+        go to the device in groups of the size the reservation reports (members_max)."""
+        ql = np.asarray(qlateral)
+        if ql.dtype != np.float32:
+            ql = np.asarray(ql, dtype=np.float64)
+        if ql.ndim != 3 or ql.shape[2] != self.n:
+            raise ValueError(f'qlateral must have shape (M, T, {self.n})')
+        M, T, n = ql.shape
+        q0 = np.array(np.broadcast_to(np.asarray(q_t, dtype=np.float64), (M, n)), order='C')      # (a copy: returned as the final states)
+        f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
+        rows = T // int(factor) if f32_out else T
+        if not (isinstance(discharge, np.ndarray) and discharge.dtype in (np.float32, np.float64) and discharge.flags['C_CONTIGUOUS']
+                and discharge.flags['WRITEABLE'] and discharge.shape == (M, rows, n) and (f32_out or int(factor) == 1)):
+            raise ValueError(f'discharge must be a writeable C-contiguous float64 ({M}, {T}, {n}) array, or float32 ({M}, T / factor, {n})')
+        f32_in = ql.dtype == np.float32
+        nsub = int(num_substeps)
+        if M == 0 or T == 0 or n == 0:
+            return q0
+        group = min(M, self.reserve_ensemble(1, T, nsub, f32_in, f32_out)['members_max'])
+        if group < 1:
+            raise RRError(_lib.RR_E_UNSUPPORTED, 'the record ring of one member does not fit the card at this shape')
+        # members_max budgets the record rings only: the group's rows must fit beside them, so a group the device refuses is halved
+        lat_each, out_each = T * n * ql.itemsize, rows * n * discharge.itemsize
+        while True:
+            bufs = []
+            try:
+                for b in (lat_each, out_each, n * 8):
+                    bufs.append(DeviceBuffer(group * b, self.device))
+                self.reserve_ensemble(group, T, nsub, f32_in, f32_out)
+                break
+            except RRError as e:
+                for b in bufs:
+                    b.free()
+                if e.code != _lib.RR_E_ALLOC or group == 1:
+                    raise
+                group = (group + 1) // 2
+        d_ql, d_out, d_q = bufs
+        try:
+            for g0 in range(0, M, group):
+                m = min(group, M - g0)
+                d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
+                d_q.upload(q0[g0:g0 + m])
+                self.rapid_route_ensemble_dev(m, d_q, n, d_ql, f32_in, T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
+                discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
+                q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
+        finally:
+            for b in (d_ql, d_out, d_q):
+                b.free()
+        return q0
 
     def muskingum_route_f32_dev(self, q_t, discharge32, num_output_steps, num_routing_per_output, stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output, f32_out=True)

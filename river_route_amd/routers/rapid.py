@@ -24,6 +24,32 @@ class RapidMuskingum(TransformMuskingum):
 
     _engine_router = _router
 
+    def _route_ensemble_group(self, group: list) -> list | None:
+        """Ensemble members (dates, lateral, in file, out file) with the same dates, routed together on the device (Plan.rapid_route_ensemble):
+        [(final state, float32 discharge, seconds)] per member, each what _route_one_file gives for that member alone,
+        or None where the group call does not apply (the members then go through the loop)."""
+        import time
+        from .. import engine
+        from .._lib import RR_E_ALLOC, RR_E_UNSUPPORTED, RRError
+        T, n, nsub, per = self.num_runoff_steps, self.A.shape[0], self.num_routing_steps_per_runoff, self.num_runoff_steps_per_discharge
+        laterals = [item[1] for item in group]
+        f32_in = all(q.dtype == np.float32 for q in laterals)
+        ql = np.stack([np.asarray(q, dtype=np.float32 if f32_in else np.float64) for q in laterals])      # (float32 -> float64 is exact)
+        fused = engine.REC_BATCH_ROWS % (per * nsub) == 0
+        out = np.empty((len(group), T // per, n), np.float32) if fused else np.empty((len(group), T, n))
+        self._lateral_coefficient()
+        t0 = time.perf_counter()
+        try:
+            states = self._plan.rapid_route_ensemble(np.array(self.channel_state, dtype=np.float64), ql, out, nsub, factor=per if fused else 1)
+        except RRError as e:
+            if e.code not in (RR_E_UNSUPPORTED, RR_E_ALLOC):
+                raise
+            return None
+        if not fused:      # rr_resample_cast_dev's arithmetic, as _route_one_file's host form: sequential sum over `per` rows, one division
+            out = np.stack([(o.reshape((-1, per, n)).mean(axis=1) if per > 1 else o).astype(np.float32) for o in out])
+        seconds = (time.perf_counter() - t0) / len(group)
+        return [(states[k], out[k], seconds) for k in range(len(group))]
+
     def _router_device(self, qlateral: np.ndarray, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
         from .._lib import RR_E_UNSUPPORTED, RRError
         from ._device import Arena
