@@ -14,21 +14,25 @@ every routed row is read from and written to HBM, and the
 params-order <-> engine-order permutation passes are inside the timed region.  Inputs are resident in HBM
 when the timed region starts (the PCIe-inclusive host-pointer rate is noted in DESIGN.md, never here).
 
-The JSON line carries `roofline` for the dominant kernel (the time-tiled routing kernel, k_tile) from HIP events
-recorded by the engine around sampled launches on its own stream -- algorithmic bytes of the time-tiled step over the
-launch time, a fraction of the 8 TB/s peak by construction, with the measured device-copy rate beside it (DESIGN.md
-section 5) -- and `cpu_baseline`: the oracle (oracle/rr_oracle.c, -O3 -march=native -ffast-math, 1 thread -- the
-reference path is single-threaded by construction) timed on a bounded sample of the same workload on this box's host
-cores.  Before anything is timed the result of the SAME kernels (time-tiled kernel + record permutation passes, forced)
-is compared with the oracle's on every row of the forcing; a mismatch refuses to report.
+The result line is the last line of the output.  A plain run does only what its headline figure needs: it sets up, warms up,
+times the K steps, writes its outputs if `--dump-outputs` is given and prints the line.  The line carries `roofline` for the
+dominant kernel (the time-tiled routing kernel, k_tile) from HIP events recorded by the engine around sampled launches of the
+timed steps on its own stream -- algorithmic bytes of the time-tiled step over the launch time, a fraction of the 8 TB/s peak by
+construction.  `--dump-outputs DIR` writes what the last timed step returned (final state and discharge
+rows; a seeded sample of their columns where they exceed 64 MB) as DIR/<name>.npy: the inputs are the same from run to run, so
+two builds can be compared output for output.
 
-The result line is the last line of the output.  `--secondary` adds the other BASELINE configurations, each a JSON line of its
-own printed before it.  `--dump-outputs DIR` writes what the last timed step returned (final state and discharge rows; a seeded
-sample of their columns where they exceed 64 MB) as DIR/<name>.npy: the inputs are the same from run to run, so two builds can be
-compared output for output.
+`--full` adds what the headline figure does not need, and takes minutes: `cpu_baseline`, the oracle (oracle/rr_oracle.c, -O3
+-march=native -ffast-math, 1 thread -- the reference path is single-threaded by construction) timed on a bounded sample of the
+same workload on this box's host cores, with a sweep of independent replicas; the parity gate, which before anything is timed
+compares the result of the SAME kernels (time-tiled kernel + record permutation passes, forced) with the oracle's on every row
+of the forcing and refuses to report on a mismatch; the measured device-copy rate beside the roofline; and the `secondary`
+lines (the other BASELINE configurations, each a JSON line of its own printed before the result line; `--no-secondary` leaves
+them out).
 
 N > 1 (one rank per GPU, torch.distributed.run): BASELINE config 5 -- ONE network of 1.25M reaches per GPU (10M at
-N = 8) graph-partitioned over the GPUs, boundary discharge exchanged over RCCL (river_route_amd/multi_gpu.py).
+N = 8) graph-partitioned over the GPUs, boundary discharge exchanged over RCCL (river_route_amd/multi_gpu.py); with `--full` every
+rank's part is checked against the oracle before anything is timed.
 """
 import argparse
 import json
@@ -64,6 +68,9 @@ def parse_args():
                          "columns) lets the engine route straight from and to the rows (direct row path, DESIGN.md section 3d)")
     ap.add_argument('--sample-every', type=int, default=128)
     ap.add_argument('--chunk-rows', type=int, default=16)
+    ap.add_argument('--full', action='store_true',
+                    help='also everything the headline figure does not need: the CPU baselines, the oracle parity gates, the device copy probe '
+                         'and (N = 1, the headline workload) the secondary lines; a plain run sets up, warms up, times and prints the line')
     ap.add_argument('--cpu-baseline-steps', type=int, default=96)
     ap.add_argument('--cpu-baseline-seconds', type=float, default=12.0)
     ap.add_argument('--exchange-rows', type=int, default=128,
@@ -72,13 +79,14 @@ def parse_args():
                     help="'unit' = BASELINE config 4 (UnitMuskingum + 48-step UH kernel), 'rapid_f32' = the headline's year with float32 rows in and "
                          "hourly float32 means out; secondary lines, not the headline (run alone for the counter passes)")
     ap.add_argument('--uh-steps', type=int, default=48)
-    ap.add_argument('--no-cpu-baseline', action='store_true')
+    ap.add_argument('--no-cpu-baseline', action='store_true', help='--full without the CPU baselines and the oracle parity gates')
     ap.add_argument('--sequential-parts', type=int, default=0,
                     help='one GPU: the network of `--gpus P` (P x --reaches reaches, BASELINE config 5 at P = 8) cut into P parts that are routed '
                          'one after another on this card, boundary series handed from part to part (multi_gpu.run_sequential); per-part times in the line')
-    ap.add_argument('--secondary', action=argparse.BooleanOptionalAction, default=False,
-                    help="N = 1: also the `secondary` entries (BASELINE configs 2 and 4 and variants, each behind its own oracle gate; "
-                         "`--workload unit`: the year of ten calls), each printed as a JSON line of its own before the result line")
+    ap.add_argument('--secondary', action=argparse.BooleanOptionalAction, default=None,
+                    help="part of --full (on by default there): at N = 1 the `secondary` entries (BASELINE configs 2 and 4 and variants, each "
+                         "behind its own oracle gate; `--workload unit`: the year of ten calls), each printed as a JSON line of its own before "
+                         "the result line")
     ap.add_argument('--cpu-replicas', type=int, default=-1,
                     help="also time N independent oracle replicas on N cores (the only parallelism the reference endorses, "
                          "docs/references/parallelism.md:67-114); 0 = off, -1 = a sweep over 16 / 64 / 256 / all cores")
@@ -90,6 +98,12 @@ def parse_args():
         ap.error('--steps must be at least 1 and --warmup at least 0')
     if a.dump_outputs and (a.gpus > 1 or a.sequential_parts > 1 or a.workload == 'dropin'):
         ap.error('--dump-outputs: one GPU, --workload rapid / unit / rapid_f32')
+    if not a.full and (a.secondary or a.workload == 'dropin'):
+        ap.error('--secondary and --workload dropin: with --full')
+    if a.secondary is None:
+        a.secondary = a.full
+    if not a.full:      # a plain run: the headline figure alone, no oracle anywhere (neither CPU baseline nor parity gate)
+        a.no_cpu_baseline = True
     if a.reaches is None:
         a.reaches = 1_000_000 if a.gpus == 1 and int(os.environ.get('WORLD_SIZE', '1')) == 1 and a.sequential_parts < 2 else 1_250_000
     return a
@@ -304,7 +318,8 @@ def bench_unit(args, device_index):
         raise SystemExit('bench.py: the parity gate did not run the timed kernel; refusing to report a number')
     kern_name = plan.last_kernel()
     traffic = pmc_traffic(args.order, n, T, nsub, key='config4' if args.order == 'random' else 'config4_postorder') if n_ks == 48 else None
-    roofline = roofline_from_profile(prof, nsub, HBM_PEAK_GBS, copy_gbs=copy_bandwidth(device_index), unit=True, kernel=kern_name, traffic=traffic)
+    copy_gbs = copy_bandwidth(device_index) if args.full else None      # the copy probe is a run of its own
+    roofline = roofline_from_profile(prof, nsub, HBM_PEAK_GBS, copy_gbs=copy_gbs, unit=True, kernel=kern_name, traffic=traffic)
     whole_path(roofline, prof, aux, kern_name, float(n) * T * nsub * args.steps / elapsed, traffic)
     if roofline is not None and 'k_rec_in' in roofline['path']['kernels']:
         roofline['path']['kernels'][f'k_rec_in_uh (convolution fused, {n_ks} taps)'] = roofline['path']['kernels'].pop('k_rec_in')
@@ -931,7 +946,7 @@ def bench_rapid(args, local_rank, net, indptr, indices, c1, c2, c3, base):
         raise SystemExit('bench.py: the parity gate did not run the timed kernel; refusing to report a number')
     reach_steps = float(n) * T * nsub * args.steps
     from river_route_amd.measure import roofline_from_profile
-    copy_gbs = copy_bandwidth(local_rank)
+    copy_gbs = copy_bandwidth(local_rank) if args.full else None      # the copy probe is a run of its own
     traffic = pmc_traffic(args.order, n, T, nsub, key='config2' if n == 100_000 and args.order == 'random' else None)
     roofline = roofline_from_profile(prof, nsub, HBM_PEAK_GBS, copy_gbs=copy_gbs, kernel=kern, traffic=traffic)
     whole_path(roofline, prof, aux, kern, reach_steps / elapsed, traffic)

@@ -24,8 +24,8 @@ pmc)
   rm -rf $OUT/fetch $OUT/write
   ;;
 bench)
-  python3 bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
-  python3 bench.py --workload unit > $OUT/bench_unit_config4.log 2> $OUT/bench_unit_config4.err
+  python3 bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
+  python3 bench.py --workload unit --full > $OUT/bench_unit_config4.log 2> $OUT/bench_unit_config4.err
   ;;
 *) echo "usage: $0 stats|pmc|bench"; exit 2;;
 esac

@@ -44,7 +44,7 @@ pmc)
   esac
   ;;
 bench)
-  python3 bench.py > $OUT/bench_default.log 2> $OUT/bench_default.err
+  python3 bench.py --full > $OUT/bench_default.log 2> $OUT/bench_default.err
   ;;
 *) echo "usage: $0 stats|pmc|bench"; exit 2;;
 esac

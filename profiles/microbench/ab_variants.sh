@@ -10,7 +10,7 @@ for spec in "$@"; do
   lib=${spec%%:*}; envs=""; [[ "$spec" == *:* ]] && envs=${spec#*:}
   path=$PWD/gpurun_variants/librr_$lib.so; [ "$lib" = hip ] && path=$PWD/river_route_amd/librr_hip.so
   echo -n "$spec: "
-  gate="--no-cpu-baseline"; [ -n "$GATE" ] && gate="--cpu-baseline-seconds 1 --cpu-replicas 0"
+  gate="--no-cpu-baseline"; [ -n "$GATE" ] && gate="--full --cpu-baseline-seconds 1 --cpu-replicas 0"
   env RR_LIB_PATH=$path ${envs//,/ } timeout -k 10 300 python bench.py $BENCH_ARGS --steps 3 --warmup 1 --no-secondary $gate 2>/dev/null | python -c "
 import sys, json
 ls = [l for l in sys.stdin if l.startswith('{')]

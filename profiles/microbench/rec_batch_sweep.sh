@@ -5,7 +5,7 @@ for i in 1 2; do
 for lib in librr_hip.so librr_b16c32.so; do
   for args in "" "--forcing-rows 96 --sink-rows 96"; do
   echo -n "$lib $args: "
-  RR_LIB_PATH=$PWD/river_route_amd/$lib timeout -k 10 300 python bench.py $args --steps 3 --warmup 1 --cpu-replicas 0 --cpu-baseline-seconds 2 2>&1 | python -c "
+  RR_LIB_PATH=$PWD/river_route_amd/$lib timeout -k 10 300 python bench.py $args --steps 3 --warmup 1 --full --no-secondary --cpu-replicas 0 --cpu-baseline-seconds 2 2>&1 | python -c "
 import sys,json
 ls=[l for l in sys.stdin if l.startswith('{')]
 if not ls: print('FAILED')

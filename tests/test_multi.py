@@ -216,8 +216,8 @@ def test_rccl_call_sequence_on_one_rank():
 
 @pytest.mark.gpu
 def test_bench_launches_its_own_ranks_gloo_rehearsal():
-    """`python bench.py --gpus 4` with no launcher around it (how the driver starts the bench): the parent starts four ranks before
-    it touches the GPU, they share the card over gloo, every rank's part reproduces the oracle on its first 96 rows (the line's
+    """`python bench.py --gpus 4 --full` with no launcher around it (how the driver starts the bench): the parent starts four ranks
+    before it touches the GPU, they share the card over gloo, every rank's part reproduces the oracle on its first 96 rows (the line's
     parity gate) and rank 0's line comes back through the parent."""
     import json
     import subprocess
@@ -225,7 +225,7 @@ def test_bench_launches_its_own_ranks_gloo_rehearsal():
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'LOCAL_RANK', 'WORLD_SIZE', 'MASTER_ADDR', 'MASTER_PORT')}
     env.update(RR_DIST_BACKEND='gloo', RR_EXCHANGE_TIMEOUT='240', RR_BENCH_TIMEOUT='900')
     bench = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), 'bench.py')
-    r = subprocess.run([sys.executable, bench, '--gpus', '4', '--reaches', '100000', '--runoff-steps', '2000', '--steps', '1', '--warmup', '1'],
+    r = subprocess.run([sys.executable, bench, '--gpus', '4', '--reaches', '100000', '--runoff-steps', '2000', '--steps', '1', '--warmup', '1', '--full'],
                        env=env, capture_output=True, text=True, timeout=1000)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     line = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith('{')][-1])
