@@ -388,6 +388,28 @@ int rr_metrics_update_dev(int device, int64_t n, int64_t rows, const void *y_tru
                           void *work, int64_t work_bytes, void *stream);
 int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *out, void *stream);
 
+/* ---- catchment / grid-cell overlap areas (river_route/runoff.py:70-116) ----
+ * The area in m^2 of each catchment row clipped to each candidate cell of a regular lon/lat grid, measured as the reference
+ * measures it: intersected with straight edges in degrees, projected to the cylindrical equal-area projection (PROJ's
+ * +proj=cea on GRS80, lat_ts 0), shoelace area.  Cells are the rectangles [x_bounds[i], x_bounds[i+1]] x [y_bounds[j],
+ * y_bounds[j+1]], both bound arrays strictly ascending (nx + 1 and ny + 1 values, degrees; bounds past the poles are
+ * measured at the pole).  Row r has the rings row_rings[r] .. row_rings[r+1] - 1; ring g has the vertices
+ * ring_offsets[g] .. ring_offsets[g+1] - 1 of lon[] / lat[] (degrees; closed or not) and weight ring_weight[g]; row r's
+ * candidate cells are the row_cells[3r+2] (= ny_r) -major block starting at cell (row_cells[3r], row_cells[3r+1]):
+ * pair pair_offsets[r] + k is cell (row_cells[3r] + k / ny_r, row_cells[3r+1] + k % ny_r), and pair_offsets[n_rows] == n_pairs.
+ * area[p] (one float64 per pair, provided by the caller) = sum over the row's rings of ring_weight[g] times the ring's
+ * signed clipped area (positive counter-clockwise): +-1 by orientation and role turns exteriors positive and holes negative.
+ * Deterministic: no atomics, the same input gives the same bits.  rr_grid_overlap_area takes host arrays and checks every
+ * index; the _dev form takes device arrays, checks sizes only and only enqueues on `stream`. */
+int rr_grid_overlap_area(int device, int64_t n_rows, int64_t n_rings, int64_t n_vertices, int64_t nx, int64_t ny, int64_t n_pairs,
+                         const int64_t *row_rings, const int64_t *ring_offsets, const double *ring_weight, const double *lon,
+                         const double *lat, const double *x_bounds, const double *y_bounds, const int32_t *row_cells,
+                         const int64_t *pair_offsets, double *area);
+int rr_grid_overlap_area_dev(int device, int64_t n_rows, int64_t n_rings, int64_t n_vertices, int64_t nx, int64_t ny, int64_t n_pairs,
+                             const int64_t *row_rings, const int64_t *ring_offsets, const double *ring_weight, const double *lon,
+                             const double *lat, const double *x_bounds, const double *y_bounds, const int32_t *row_cells,
+                             const int64_t *pair_offsets, double *area, void *stream);
+
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);

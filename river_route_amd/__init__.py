@@ -5,7 +5,7 @@ MI355X-native Muskingum routing engine behind river-route's Router API.
     rr.RapidMuskingum('config.yaml').route()
 
 mirrors `import river_route as rr` of the reference for the routing hot path (river_route/__init__.py:11-29):
-Configs, Muskingum, RapidMuskingum, UnitMuskingum, uhkernels.UnitHydrograph, runoff.runoff_to_qlateral, tools.adjacency_matrix, metrics.  The compute
+Configs, Muskingum, RapidMuskingum, UnitMuskingum, uhkernels.UnitHydrograph, runoff.runoff_to_qlateral, runoff.grid_weights, tools.adjacency_matrix, metrics.  The compute
 runs in hand-written HIP kernels (csrc/, C ABI in include/rr_hip.h); there is no CPU fallback.
 """
 __version__ = '0.1.0'

@@ -134,6 +134,9 @@ _SIGNATURES = {
     'rr_metrics_work_bytes': (C.c_int, [_i64, _i64, C.POINTER(_i64)]),
     'rr_metrics_update_dev': (C.c_int, [C.c_int, _i64, _i64, _vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp]),
     'rr_metrics_finish_dev': (C.c_int, [C.c_int, _i64, _vp, _vp, _vp]),
+    'rr_grid_overlap_area': (C.c_int, [C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'rr_grid_overlap_area_dev': (C.c_int, [C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                           _vp]),
     'rr_dev_malloc': (C.c_int, [C.c_int, _i64, C.POINTER(_vp)]),
     'rr_dev_free': (C.c_int, [C.c_int, _vp]),
     'rr_dev_upload': (C.c_int, [C.c_int, _vp, _vp, _i64]),

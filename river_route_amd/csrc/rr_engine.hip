@@ -13,7 +13,8 @@
 // Layout: rr_plan.hpp.  No CPU fallback anywhere in this file.
 //
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
-// rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp (device code), rr_exec.hpp (plan object, executor), then the
+// rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
+// rr_kernels_overlap.hpp (device code), rr_exec.hpp (plan object, executor), then the
 // C ABI below.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
@@ -23,6 +24,7 @@
 #include "rr_kernels_runoff.hpp"
 #include "rr_kernels_direct.hpp"
 #include "rr_kernels_metrics.hpp"
+#include "rr_kernels_overlap.hpp"
 #include "rr_exec.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -1088,6 +1090,114 @@ int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *ou
     hipLaunchKernelGGL(k_metrics_finish, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, state, n, out);
     HIPCHK(hipGetLastError());
     return RR_OK;
+}
+
+// ---- catchment / grid-cell overlap areas (rr_kernels_overlap.hpp) ----
+
+namespace {
+
+int overlap_sizes(const char *fn, int64_t n_rows, int64_t n_rings, int64_t n_vertices, int64_t nx, int64_t ny, int64_t n_pairs)
+{
+    if (n_rows < 0 || n_rings < 0 || n_vertices < 0 || nx < 1 || ny < 1 || n_pairs < 0 || nx >= 0x7FFFFFFFLL ||
+        ny >= 0x7FFFFFFFLL || n_rows >= 0x7FFFFFFFLL || n_pairs > (int64_t)0xFFFFFFFFLL * kOverlapWaves)
+        return fail(RR_E_INVALID, std::string(fn) + ": sizes out of range");
+    return RR_OK;
+}
+
+}  // namespace
+
+int rr_grid_overlap_area_dev(int device, int64_t n_rows, int64_t n_rings, int64_t n_vertices, int64_t nx, int64_t ny, int64_t n_pairs,
+                             const int64_t *row_rings, const int64_t *ring_offsets, const double *ring_weight, const double *lon,
+                             const double *lat, const double *x_bounds, const double *y_bounds, const int32_t *row_cells,
+                             const int64_t *pair_offsets, double *area, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_grid_overlap_area_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    if (int rc = overlap_sizes("rr_grid_overlap_area_dev", n_rows, n_rings, n_vertices, nx, ny, n_pairs)) return rc;
+    if (n_pairs == 0) return RR_OK;
+    if (n_rows == 0) return fail(RR_E_INVALID, "rr_grid_overlap_area_dev: pairs without rows");
+    if (!row_rings || !ring_offsets || !ring_weight || !lon || !lat || !x_bounds || !y_bounds || !row_cells || !pair_offsets || !area)
+        return fail(RR_E_INVALID, "rr_grid_overlap_area_dev: null array");
+    const int64_t blocks = (n_pairs + kOverlapWaves - 1) / kOverlapWaves;
+    hipLaunchKernelGGL(k_overlap_area, dim3((unsigned)blocks), dim3(kBlock), 0, (hipStream_t)stream, n_rows, n_pairs, row_rings,
+                       ring_offsets, ring_weight, lon, lat, x_bounds, y_bounds, row_cells, pair_offsets, area);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_grid_overlap_area(int device, int64_t n_rows, int64_t n_rings, int64_t n_vertices, int64_t nx, int64_t ny, int64_t n_pairs,
+                         const int64_t *row_rings, const int64_t *ring_offsets, const double *ring_weight, const double *lon,
+                         const double *lat, const double *x_bounds, const double *y_bounds, const int32_t *row_cells,
+                         const int64_t *pair_offsets, double *area)
+{
+    const char *fn = "rr_grid_overlap_area";
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_grid_overlap_area: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    if (int rc = overlap_sizes(fn, n_rows, n_rings, n_vertices, nx, ny, n_pairs)) return rc;
+    if (n_pairs == 0) return RR_OK;
+    if (n_rows == 0) return fail(RR_E_INVALID, "rr_grid_overlap_area: pairs without rows");
+    if (!row_rings || !ring_offsets || !ring_weight || !lon || !lat || !x_bounds || !y_bounds || !row_cells || !pair_offsets || !area)
+        return fail(RR_E_INVALID, "rr_grid_overlap_area: null array");
+    // every index the kernel follows, checked here so the device reads stay inside the arrays
+    if (row_rings[0] != 0 || row_rings[n_rows] != n_rings || ring_offsets[0] != 0 || ring_offsets[n_rings] != n_vertices ||
+        pair_offsets[0] != 0 || pair_offsets[n_rows] != n_pairs)
+        return fail(RR_E_INVALID, "rr_grid_overlap_area: offsets must start at 0 and end at n_rings / n_vertices / n_pairs");
+    for (int64_t r = 0; r < n_rows; ++r) {
+        const int64_t cells = pair_offsets[r + 1] - pair_offsets[r];
+        if (row_rings[r + 1] < row_rings[r] || cells < 0)
+            return fail(RR_E_INVALID, "rr_grid_overlap_area: row " + std::to_string(r) + ": offsets decrease");
+        if (cells == 0) continue;
+        const int64_t cx = row_cells[3 * r], cy = row_cells[3 * r + 1], cny = row_cells[3 * r + 2];
+        if (cny < 1 || cells % cny != 0 || cx < 0 || cy < 0 || cx + cells / cny > nx || cy + cny > ny || cells > 0x7FFFFFFFLL)
+            return fail(RR_E_INVALID, "rr_grid_overlap_area: row " + std::to_string(r) + ": candidate cells outside the grid");
+    }
+    for (int64_t g = 0; g < n_rings; ++g)
+        if (ring_offsets[g + 1] < ring_offsets[g])
+            return fail(RR_E_INVALID, "rr_grid_overlap_area: ring " + std::to_string(g) + ": offsets decrease");
+    for (int64_t i = 0; i < nx; ++i)
+        if (!(x_bounds[i] < x_bounds[i + 1])) return fail(RR_E_INVALID, "rr_grid_overlap_area: x_bounds not strictly ascending");
+    for (int64_t j = 0; j < ny; ++j)
+        if (!(y_bounds[j] < y_bounds[j + 1])) return fail(RR_E_INVALID, "rr_grid_overlap_area: y_bounds not strictly ascending");
+
+    int64_t *d_rr = nullptr, *d_ro = nullptr, *d_po = nullptr;
+    double *d_w = nullptr, *d_lon = nullptr, *d_lat = nullptr, *d_xb = nullptr, *d_yb = nullptr, *d_out = nullptr;
+    int32_t *d_rc = nullptr;
+    int rc = dev_alloc(&d_rr, n_rows + 1);
+    if (!rc) rc = dev_alloc(&d_ro, n_rings + 1);
+    if (!rc) rc = dev_alloc(&d_po, n_rows + 1);
+    if (!rc) rc = dev_alloc(&d_w, n_rings);
+    if (!rc) rc = dev_alloc(&d_lon, n_vertices);
+    if (!rc) rc = dev_alloc(&d_lat, n_vertices);
+    if (!rc) rc = dev_alloc(&d_xb, nx + 1);
+    if (!rc) rc = dev_alloc(&d_yb, ny + 1);
+    if (!rc) rc = dev_alloc(&d_rc, 3 * n_rows);
+    if (!rc) rc = dev_alloc(&d_out, n_pairs);
+    auto release = [&]() {
+        (void)hipFree(d_rr); (void)hipFree(d_ro); (void)hipFree(d_po); (void)hipFree(d_w); (void)hipFree(d_lon);
+        (void)hipFree(d_lat); (void)hipFree(d_xb); (void)hipFree(d_yb); (void)hipFree(d_rc); (void)hipFree(d_out);
+    };
+    if (rc) { release(); return rc; }
+    auto up = [](void *dst, const void *src, int64_t bytes) {
+        return bytes > 0 ? hipMemcpy(dst, src, (size_t)bytes, hipMemcpyHostToDevice) : hipSuccess;
+    };
+    hipError_t e = up(d_rr, row_rings, (n_rows + 1) * 8);
+    if (e == hipSuccess) e = up(d_ro, ring_offsets, (n_rings + 1) * 8);
+    if (e == hipSuccess) e = up(d_po, pair_offsets, (n_rows + 1) * 8);
+    if (e == hipSuccess) e = up(d_w, ring_weight, n_rings * 8);
+    if (e == hipSuccess) e = up(d_lon, lon, n_vertices * 8);
+    if (e == hipSuccess) e = up(d_lat, lat, n_vertices * 8);
+    if (e == hipSuccess) e = up(d_xb, x_bounds, (nx + 1) * 8);
+    if (e == hipSuccess) e = up(d_yb, y_bounds, (ny + 1) * 8);
+    if (e == hipSuccess) e = up(d_rc, row_cells, 3 * n_rows * 4);
+    if (e != hipSuccess) { release(); return fail(RR_E_HIP, hipGetErrorString(e)); }
+    rc = rr_grid_overlap_area_dev(device, n_rows, n_rings, n_vertices, nx, ny, n_pairs, d_rr, d_ro, d_w, d_lon, d_lat, d_xb, d_yb,
+                                  d_rc, d_po, d_out, nullptr);
+    if (!rc) {
+        e = hipMemcpy(area, d_out, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
+        if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
+    }
+    release();
+    return rc;
 }
 
 // ---- device helpers ----

@@ -13,7 +13,7 @@ from ._lib import RRError, check, ptr
 
 __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
            'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
-           'metrics_update_dev', 'metrics_finish_dev']
+           'metrics_update_dev', 'metrics_finish_dev', 'grid_overlap_area', 'grid_overlap_area_dev']
 
 
 MODE_RAPID, MODE_MUSKINGUM, MODE_UNIT = 0, 1, 2      # include/rr_hip.h: RR_MODE_*
@@ -488,6 +488,33 @@ def metrics_update_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is
 def metrics_finish_dev(n, state, out, device: int = 0, stream=None) -> None:
     """rr_metrics_finish_dev: [9][n] state -> out[5][n] (me, mae, mse, pearson_r, kge2012); only enqueues."""
     check(_lib.lib().rr_metrics_finish_dev(int(device), int(n), ptr(state), ptr(out), stream))
+
+
+def grid_overlap_area(row_rings, ring_offsets, ring_weight, lon, lat, x_bounds, y_bounds, row_cells, pair_offsets,
+                      device: int = 0) -> np.ndarray:
+    """rr_grid_overlap_area: host arrays in, float64[n_pairs] clipped cea areas (m^2) out, one per (row, candidate cell) pair."""
+    row_rings = np.ascontiguousarray(row_rings, dtype=np.int64)
+    ring_offsets = np.ascontiguousarray(ring_offsets, dtype=np.int64)
+    pair_offsets = np.ascontiguousarray(pair_offsets, dtype=np.int64)
+    ring_weight, lon, lat, x_bounds, y_bounds = (np.ascontiguousarray(a, dtype=np.float64) for a in (ring_weight, lon, lat, x_bounds, y_bounds))
+    row_cells = np.ascontiguousarray(row_cells, dtype=np.int32)
+    n_rows, n_rings = row_rings.shape[0] - 1, ring_offsets.shape[0] - 1
+    if pair_offsets.shape[0] != n_rows + 1 or ring_weight.shape[0] != n_rings or lon.shape != lat.shape or row_cells.size != 3 * n_rows:
+        raise ValueError('grid_overlap_area: array lengths disagree')
+    n_pairs = int(pair_offsets[-1]) if n_rows >= 0 and pair_offsets.size else 0
+    out = np.zeros(n_pairs, dtype=np.float64)
+    check(_lib.lib().rr_grid_overlap_area(int(device), n_rows, n_rings, lon.shape[0], x_bounds.shape[0] - 1, y_bounds.shape[0] - 1,
+                                          n_pairs, ptr(row_rings), ptr(ring_offsets), ptr(ring_weight), ptr(lon), ptr(lat),
+                                          ptr(x_bounds), ptr(y_bounds), ptr(row_cells), ptr(pair_offsets), ptr(out)))
+    return out
+
+
+def grid_overlap_area_dev(n_rows, n_rings, n_vertices, nx, ny, n_pairs, row_rings, ring_offsets, ring_weight, lon, lat, x_bounds,
+                          y_bounds, row_cells, pair_offsets, area, device: int = 0, stream=None) -> None:
+    """rr_grid_overlap_area_dev: the same on device arrays; only enqueues."""
+    check(_lib.lib().rr_grid_overlap_area_dev(int(device), int(n_rows), int(n_rings), int(n_vertices), int(nx), int(ny), int(n_pairs),
+                                              ptr(row_rings), ptr(ring_offsets), ptr(ring_weight), ptr(lon), ptr(lat), ptr(x_bounds),
+                                              ptr(y_bounds), ptr(row_cells), ptr(pair_offsets), ptr(area), stream))
 
 
 class DeviceBuffer:
