@@ -410,6 +410,27 @@ int rr_grid_overlap_area_dev(int device, int64_t n_rows, int64_t n_rings, int64_
                              const double *lat, const double *x_bounds, const double *y_bounds, const int32_t *row_cells,
                              const int64_t *pair_offsets, double *area, void *stream);
 
+/* ---- adjoint of RapidMuskingum routing ----
+ * The gradient of a scalar loss L through one rr_rapid_route_dev call (T rows, nsub sub-steps, S = T * nsub) with the coefficients
+ * as last set by rr_plan_set_coeffs.  All rows are (time, reach) in params order on the plan's device:
+ *   q0[n]              the state the forward call started from;
+ *   lateral[lat_rows*n] its lateral rows (the first T are read; lat_rows >= T), or NULL for channel-only routing;
+ *   discharge[T*n]     its discharge (the clamp mask: a value <= 0 passes no gradient); needed with grad_out;
+ *   grad_out[T*n]      dL/d(discharge), or NULL;  grad_qfinal[n]  dL/d(final state), or NULL;
+ * and it writes what is asked for (NULL: not computed):
+ *   grad_lateral[T*n]  dL/d(lateral);  grad_q0[n]  dL/d(q0);
+ *   grad_coef[4*n]     dL/dc1, dL/dc2, dL/dc3, dL/dc4dt per reach, c1 being the reach's own (the -lhs_off_data of the edges into it).
+ * Work memory (caller-provided, rr_rapid_adjoint_work_bytes; the call allocates nothing and only enqueues on `stream`):
+ *   8 n (2 S + 2 T + 2 depth + min(T, 16) + 4 splits + 2) bytes, splits = min(S, ceil(2048 / ceil(n / 256))) sub-step ranges of
+ *   the reduction: the forward state tape and the adjoint tape (S + depth rows each), lateral and gradient rows in engine order.
+ * rr_rapid_adjoint_work_bytes also readies the plan for adjoint calls (uploads its permutation tables once): call it before the first.
+ * No atomics: the same inputs give the same bits.  RR_E_UNSUPPORTED for per-edge weights, a plan with boundary reaches
+ * (rr_plan_set_boundary) and a host-only plan; RR_E_INVALID for a null or short argument or too little work memory. */
+int rr_rapid_adjoint_work_bytes(rr_plan *plan, int64_t T, int64_t nsub, int64_t *bytes);
+int rr_rapid_adjoint_dev(rr_plan *plan, const double *q0, const double *lateral, int64_t lat_rows, const double *discharge,
+                         const double *grad_out, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef,
+                         void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream);
+
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);

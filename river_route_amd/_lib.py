@@ -137,6 +137,8 @@ _SIGNATURES = {
     'rr_grid_overlap_area': (C.c_int, [C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rr_grid_overlap_area_dev': (C.c_int, [C.c_int, _i64, _i64, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                            _vp]),
+    'rr_rapid_adjoint_work_bytes': (C.c_int, [_vp, _i64, _i64, C.POINTER(_i64)]),
+    'rr_rapid_adjoint_dev': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp]),
     'rr_dev_malloc': (C.c_int, [C.c_int, _i64, C.POINTER(_vp)]),
     'rr_dev_free': (C.c_int, [C.c_int, _vp]),
     'rr_dev_upload': (C.c_int, [C.c_int, _vp, _vp, _i64]),

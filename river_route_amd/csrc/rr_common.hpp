@@ -20,7 +20,7 @@
 #include "../../include/rr_hip.h"
 #include "rr_plan.hpp"
 
-#define RR_VERSION_NUM 220
+#define RR_VERSION_NUM 230
 
 namespace {
 

@@ -14,7 +14,7 @@
 //
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
-// rr_kernels_overlap.hpp (device code), rr_exec.hpp (plan object, executor), then the
+// rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp (device code), rr_exec.hpp (plan object, executor), then the
 // C ABI below.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
@@ -25,6 +25,7 @@
 #include "rr_kernels_direct.hpp"
 #include "rr_kernels_metrics.hpp"
 #include "rr_kernels_overlap.hpp"
+#include "rr_kernels_adjoint.hpp"
 #include "rr_exec.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -55,7 +56,7 @@ void rr_plan_destroy(rr_plan *P)
                         P->d_c3, P->d_c4, P->d_x, P->d_isum, P->d_qch, P->d_a2, P->d_c1own, P->d_z, P->d_ring, P->d_stage, P->d_mrows,
                         P->d_slot_a[0], P->d_slot_a[1], P->d_slot_b[0], P->d_slot_b[1], P->d_m_index[0], P->d_m_index[1],
                         P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef, P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch,
-                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi};
+                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi, P->d_adj_down};
         for (void *p : ptrs) if (p) (void)hipFree(p);
         P->pipe.destroy();
         for (hipEvent_t e : P->ev) (void)hipEventDestroy(e);
@@ -1088,6 +1089,197 @@ int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *ou
     if (n == 0) return RR_OK;
     if (!state || !out) return fail(RR_E_INVALID, "rr_metrics_finish_dev: null array");
     hipLaunchKernelGGL(k_metrics_finish, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, state, n, out);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// ---- adjoint of RapidMuskingum routing (rr_kernels_adjoint.hpp) ----
+
+namespace {
+
+constexpr int64_t kAdjPermRows = 16;          // rows per pass of the tiled permutation
+constexpr int64_t kAdjTargetBlocks = 2048;    // blocks of k_adj_reduce: column blocks x sub-step ranges
+
+// The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
+// (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
+// order), lateral rows and gradient rows in engine order (T rows each), the permutation's intermediate rows, the reduction slab
+// (4 x n per sub-step range), two scratch rows for k_tick.
+struct AdjointLayout {
+    int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
+    int64_t chunk, splits, steps_per_split;
+};
+
+AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub)
+{
+    AdjointLayout L{};
+    const int64_t S = T * nsub;
+    L.chunk = std::min<int64_t>(T, kAdjPermRows);
+    const int64_t col_blocks = (n + kBlock - 1) / kBlock;
+    const int64_t want = std::max<int64_t>(1, (kAdjTargetBlocks + col_blocks - 1) / col_blocks);
+    L.splits = std::max<int64_t>(1, std::min(want, S));
+    L.steps_per_split = (S + L.splits - 1) / L.splits;
+    L.splits = (S + L.steps_per_split - 1) / L.steps_per_split;
+    L.qtape = 0;
+    L.mtape = L.qtape + (S + depth + 1) * n;
+    L.lat = L.mtape + (S + depth - 1) * n;
+    L.grad = L.lat + T * n;
+    L.mrows = L.grad + T * n;
+    L.slab = L.mrows + L.chunk * n;
+    L.scratch = L.slab + L.splits * 4 * n;
+    L.total = L.scratch + 2 * n;
+    return L;
+}
+
+// Plan data the adjoint reads besides the streaming layout: the tiled permutation tables and the downstream position of each position.
+int adjoint_ready(rr_plan *P)
+{
+    if (!P->perm_ready) {
+        int rc = upload_tiled_permutations(P);
+        if (rc) return rc;
+    }
+    if (!P->d_adj_down) {
+        const rr::HostPlan &H = P->h;
+        std::vector<int32_t> down(H.n, -1);
+        for (int64_t p = 0; p < H.n; ++p)
+            for (int32_t u = H.child_ptr[p]; u < H.child_ptr[p + 1]; ++u) down[u] = (int32_t)p;
+        int32_t *d = nullptr;
+        int rc = dev_alloc(&d, H.n);
+        if (!rc) rc = dev_upload(d, down);
+        if (rc) { if (d) (void)hipFree(d); return rc; }
+        P->d_adj_down = d;
+    }
+    return RR_OK;
+}
+
+}  // namespace
+
+int rr_rapid_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
+{
+    if (!P || !bytes) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: null argument");
+    *bytes = 0;
+    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_work_bytes: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
+    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: need T >= 1 and sub-steps >= 1");
+    const rr::HostPlan &H = P->h;
+    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: too many sub-steps for one call: split the series into windows");
+    HIPCHK(hipSetDevice(P->device));
+    if (H.n == 0) return RR_OK;
+    if (int rc = adjoint_ready(P)) return rc;
+    *bytes = adjoint_layout(H.n, H.depth, T, nsub).total * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_rapid_adjoint_dev(rr_plan *P, const double *q0, const double *lateral, int64_t lat_rows, const double *discharge,
+                         const double *grad_out, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef,
+                         void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream)
+{
+    if (!P) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: null plan");
+    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
+    HIPCHK(hipSetDevice(P->device));
+    if (P->n_ghost > 0 || P->n_export > 0)
+        return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: the plan has boundary reaches (rr_plan_set_boundary): partitioned networks have no adjoint");
+    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_rapid_adjoint_dev called before rr_plan_set_coeffs");
+    if (!P->weights_uniform)
+        return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: per-edge weights (lhs_off_data not -c1 of the downstream reach): the adjoint needs one c1 per reach");
+    if (P->ses.open) return fail(RR_E_STATE, "rr_rapid_adjoint_dev: a routing call is open");
+    const rr::HostPlan &H = P->h;
+    const int64_t n = H.n;
+    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: need T >= 1 and sub-steps >= 1");
+    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: too many sub-steps for one call: split the series into windows");
+    if (n == 0 || (!grad_lateral && !grad_q0 && !grad_coef)) return RR_OK;
+    if (grad_coef && !q0) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: the coefficient gradients need q0");
+    if (lateral && lat_rows < T) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: fewer lateral rows than T");
+    if (lateral && !P->has_c4) return fail(RR_E_STATE, "rr_rapid_adjoint_dev: lateral rows but no c4_dt (rr_plan_set_coeffs got NULL)");
+    if (grad_out && !discharge) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: grad_out needs the discharge of the forward call (its clamp mask)");
+    if (grad_lateral && !lateral) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: grad_lateral of a channel-only call (lateral is NULL)");
+    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub);
+    const int64_t need = L.total * (int64_t)sizeof(double);
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: work memory smaller than rr_rapid_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    if (!P->perm_ready || !P->d_adj_down)
+        return fail(RR_E_STATE, "rr_rapid_adjoint_dev: call rr_rapid_adjoint_work_bytes first (it uploads the plan's permutation tables once)");
+
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t S = T * nsub, dmax = H.depth - 1, ticks = S + dmax;
+    double *const base = static_cast<double *>(work);
+    double *qtape = base + L.qtape, *mtape = base + L.mtape, *elat = base + L.lat, *egrad = base + L.grad, *mrows = base + L.mrows,
+           *slab = base + L.slab, *isum = base + L.scratch, *oscr = isum + n;
+    const bool one = nsub == 1;
+    auto rows_between = [&](int which, const double *src, double *dst) {      // T rows, params <-> engine order
+        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
+            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
+                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
+    };
+
+    // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        const int64_t count = T * n;
+        hipLaunchKernelGGL(k_adj_mask, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st, mtape, grad_out,
+                           discharge, count, 1.0 / (double)nsub);
+        rows_between(0, mtape, egrad);
+    }
+    // the forward again, into a tick-indexed tape: k_tick as the route calls run it, with its three rotating rows spread over the tape
+    if (grad_coef) {
+        if (lateral) rows_between(0, lateral, elat);
+        hipLaunchKernelGGL(k_adj_tape_init, grid1(n), dim3(kBlock), 0, st, qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
+        TickArgs a{};
+        a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c1row = P->d_c1row_h; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
+        a.isum = isum; a.bidx = P->d_bidx; a.ghost = nullptr; a.exports = nullptr; a.n_ghost = 0; a.n_export = 0;
+        a.in = lateral ? elat : nullptr; a.in_ld = n; a.in_rows = Div32((uint32_t)T);
+        a.out = oscr; a.out_ld = 0; a.out_rows = Div32(1u);      // discharge rows are not kept: every row lands on one scratch row
+        a.total_substeps = S; a.nsub = Div32((uint32_t)nsub); a.inv_nsub = 1.0 / (double)nsub;
+        for (int64_t tau = 0; tau < ticks; ++tau) {
+            const int64_t lag_lo = std::max<int64_t>(0, tau - S + 1), lag_hi = std::min<int64_t>(tau, dmax);
+            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
+            if (p_hi <= p_lo) continue;
+            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+            a.xc = qtape + (tau + 2) * n; a.xa = a.xc - n; a.xb = a.xc - 2 * n;
+            const dim3 g = grid1(p_hi - p_lo);
+            if (lateral) {
+                if (one) hipLaunchKernelGGL((k_tick<true, true>), g, dim3(kBlock), 0, st, a);
+                else hipLaunchKernelGGL((k_tick<true, false>), g, dim3(kBlock), 0, st, a);
+            } else {
+                if (one) hipLaunchKernelGGL((k_tick<false, true>), g, dim3(kBlock), 0, st, a);
+                else hipLaunchKernelGGL((k_tick<false, false>), g, dim3(kBlock), 0, st, a);
+            }
+        }
+    }
+    // reverse ticks: reach at lag l runs reverse step tau - (Dmax - l)
+    {
+        AdjTickArgs a{};
+        a.lag = P->d_lag; a.down = P->d_adj_down; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3;
+        a.g = grad_out ? egrad : nullptr; a.gf = grad_qfinal; a.perm = P->d_perm;
+        a.n = n; a.dmax = (int32_t)dmax; a.total_substeps = S; a.nsub = Div32((uint32_t)nsub);
+        for (int64_t tau = 0; tau < ticks; ++tau) {
+            const int64_t lag_lo = std::max<int64_t>(0, dmax - tau), lag_hi = std::min<int64_t>(dmax, dmax - tau + S - 1);
+            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
+            if (p_hi <= p_lo) continue;
+            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+            a.mc = mtape + tau * n;
+            a.ma = tau >= 1 ? a.mc - n : a.mc;      // never read at tick 0 (nothing runs r > 0 or has a downstream reach there)
+            a.mb = tau >= 2 ? a.mc - 2 * n : a.mc;  // read from tick 2 on only
+            const dim3 g = grid1(p_hi - p_lo);
+            if (one) hipLaunchKernelGGL(k_adj_tick<true>, g, dim3(kBlock), 0, st, a);
+            else hipLaunchKernelGGL(k_adj_tick<false>, g, dim3(kBlock), 0, st, a);
+        }
+    }
+    if (grad_coef) {
+        AdjReduceArgs r{};
+        r.lag = P->d_lag; r.child_ptr = P->d_child_ptr; r.qtape = qtape; r.mtape = mtape; r.lat = lateral ? elat : nullptr; r.slab = slab;
+        r.n = n; r.total_substeps = S; r.steps_per_split = L.steps_per_split; r.dmax = (int32_t)dmax; r.nsub = Div32((uint32_t)nsub);
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits);
+        if (one) hipLaunchKernelGGL(k_adj_reduce<true>, g, dim3(kBlock), 0, st, r);
+        else hipLaunchKernelGGL(k_adj_reduce<false>, g, dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef || grad_q0)
+        hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)slab, L.splits, (const double *)mtape,
+                           (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, S, (int32_t)dmax, lateral ? 1 : 0, grad_coef, grad_q0);
+    if (grad_lateral) {
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535));
+        hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, egrad, (const double *)mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
+                           T, nsub, S, (int32_t)dmax);
+        rows_between(1, egrad, grad_lateral);
+    }
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

@@ -211,6 +211,7 @@ struct rr_plan {
     bool lean_enabled = true;           // RR_TILE_LEAN=0 (tests): the general tick for every call
     bool uh_pairs = true;               // the fused convolution takes two record batches per launch where it can (RR_UH_PAIRS=0: tests)
     bool perm_ready = false;            // the streaming kernel's tiled permutations are on the device
+    int32_t *d_adj_down = nullptr;      // adjoint (rr_rapid_adjoint_dev): downstream engine position of each position, -1 at outlets
 
     // profile of the last route call: the routing kernel (ev, rr_plan_profile) and, sampled the same way, the kernels around it
     // (aux: 0 in-pass, 1 out-pass, 2 the skeleton's k_tile launches of the direct row path, 3 its out-pass over the holes)
@@ -812,8 +813,8 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     return RR_OK;
 }
 
-// params order <-> engine order through the two-phase tiled permutation (k_perm_a / k_perm_b)
-void permute_rows(rr_plan *P, int which, const RowView &src, const RowView &dst, int64_t t0, int nrows)
+// params order <-> engine order through the two-phase tiled permutation (k_perm_a / k_perm_b); mrows holds nrows x n intermediate values
+void permute_rows_via(rr_plan *P, int which, const RowView &src, const RowView &dst, int64_t t0, int nrows, double *mrows, hipStream_t stream)
 {
     const int64_t n = P->h.n;
     constexpr int E = kPermE;
@@ -821,11 +822,16 @@ void permute_rows(rr_plan *P, int which, const RowView &src, const RowView &dst,
     const int rpb = (int)std::max<int64_t>(1, P->perm_rows_per_block);
     dim3 g((unsigned)((n + tile - 1) / tile), (unsigned)((nrows + rpb - 1) / rpb));
     const size_t lds_bytes = (size_t)tile * sizeof(double);
-    hipStream_t stream = P->ses.stream;
-    hipLaunchKernelGGL(k_perm_a<E>, g, dim3(kPermThreads), lds_bytes, stream, src, P->d_mrows, n,
+    hipLaunchKernelGGL(k_perm_a<E>, g, dim3(kPermThreads), lds_bytes, stream, src, mrows, n,
                        (const uint16_t *)P->d_slot_a[which], (const int32_t *)P->d_m_index[which], t0, nrows, rpb);
-    hipLaunchKernelGGL(k_perm_b<E>, g, dim3(kPermThreads), lds_bytes, stream, dst, (const double *)P->d_mrows, n,
+    hipLaunchKernelGGL(k_perm_b<E>, g, dim3(kPermThreads), lds_bytes, stream, dst, (const double *)mrows, n,
                        (const uint16_t *)P->d_slot_b[which], t0, nrows, rpb);
+}
+
+// the same through the plan's work rows, on the open session's stream
+void permute_rows(rr_plan *P, int which, const RowView &src, const RowView &dst, int64_t t0, int nrows)
+{
+    permute_rows_via(P, which, src, dst, t0, nrows, P->d_mrows, P->ses.stream);
 }
 
 int session_load_rows(rr_plan *P, int64_t r0, int64_t r1)   // params order -> ring

@@ -226,6 +226,22 @@ class Plan:
         check(_lib.lib().rr_rapid_route_dev(self._h, ptr(q_t), ptr(qlateral), int(ql_rows), ptr(discharge),
                                             int(out_rows), int(T), int(num_substeps), stream))
 
+    # -- adjoint of rapid_route_dev (rr.grad) --
+    def rapid_adjoint_work_bytes(self, T: int, num_substeps: int = 1) -> int:
+        """rr_rapid_adjoint_work_bytes: bytes of work memory rapid_adjoint_dev needs for T rows x num_substeps sub-steps (readies
+        the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_rapid_adjoint_work_bytes(self._h, int(T), int(num_substeps), C.byref(out)))
+        return int(out.value)
+
+    def rapid_adjoint_dev(self, q0, lateral, lat_rows, discharge, grad_out, grad_qfinal, grad_lateral, grad_q0, grad_coef, work,
+                          work_bytes, T, num_substeps, stream=None) -> None:
+        """rr_rapid_adjoint_dev (enqueue only): gradients through one rapid_route_dev call with the coefficients last set; any of
+        lateral, grad_out, grad_qfinal and the three outputs may be None."""
+        check(_lib.lib().rr_rapid_adjoint_dev(self._h, ptr(q0), ptr(lateral), int(lat_rows), ptr(discharge), ptr(grad_out),
+                                              ptr(grad_qfinal), ptr(grad_lateral), ptr(grad_q0), ptr(grad_coef), ptr(work),
+                                              int(work_bytes), int(T), int(num_substeps), stream))
+
     def muskingum_route_dev(self, q_t, discharge, out_rows, num_output_steps, num_routing_per_output,
                             stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output)
