@@ -75,9 +75,11 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
     if (!P) return fail(RR_E_ALLOC, "rr_plan_create: out of memory");
     // Run-time switches, all for tests (each is exercised by tests/test_gpu_*.py): RR_WAVE=0 the streaming kernel for every call,
     // =1 the time-tiled one wherever it applies; RR_WAVE_K ticks per task; RR_TILE_BLOCK tile capacity (many small tiles);
-    // RR_TILE_LEAN=0 the general tick; RR_UH_PAIRS=0 one record batch per fused-convolution launch; RR_DIRECT=0 records also where the
+    // RR_TILE_LEAN=0 the general tick; RR_UH_PAIRS=0 one record batch per fused-convolution launch; RR_REC_BATCHES=N N record batches
+    // per launch of k_rec_in / k_rec_out in every call (1: one, as before multi-batch launches); RR_DIRECT=0 records also where the
     // params order would allow the direct row path; RR_VERBOSE=1 logs the schedule.
     if (const char *e = getenv("RR_WAVE")) { P->wave_enabled = atoi(e) != 0; P->wave_forced = atoi(e) == 1; }
+    if (const char *e = getenv("RR_REC_BATCHES")) { P->rec_batches = std::max(1, std::min(kRecMaxLaunchBatches, atoi(e))); P->rec_batches_forced = true; }
     if (const char *e = getenv("RR_WAVE_K")) P->wave_K = std::max(kRec, atoi(e) / kRec * kRec);
     std::string err;
     int rc = rr::build_host_plan(n, csc_indptr, csc_indices, P->h, err);

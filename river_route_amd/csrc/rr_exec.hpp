@@ -57,6 +57,7 @@ struct Schedule {
     int64_t chunks = 0;               // chunks of the record ring (Tile), of the skeleton's record ring (Direct)
     int64_t ring = 0;                 // doubles of P->d_ring: record ring (an ensemble's: one per member), or the work rows of the streaming kernel
     int64_t mrows = 0, stage = 0;     // doubles of the intermediate rows (streaming permutation, convolved rows) / of the host staging rows
+    int64_t rec_nb = 1;               // Tile: record batches per launch of k_rec_in / k_rec_out (the ring holds rec_nb - 1 more)
 };
 
 // One routing call in flight: rows enter (permutation in), ticks run, finished rows leave (permutation out).
@@ -78,6 +79,7 @@ struct Session {
     TickArgs a{};
     int64_t KC = 1;               // record chunks per task: K = 16 * KC ticks
     int64_t rec_chunks = 0, in_batches = 0, n_in_batches = 0, out_batches = 0, n_out_batches = 0;
+    int64_t rec_nb = 1;           // record batches per launch of the plain record passes (Schedule::rec_nb)
     int64_t ticks_stored = 0;     // tick-rows that have left the record ring
     int64_t out_limit = std::numeric_limits<int64_t>::max();   // rows the caller's output ring can take (host pipeline)
     int64_t diag = 0, n_diags = 0, n_macro = 0;
@@ -210,6 +212,8 @@ struct rr_plan {
     bool in32_big_endian = false, out32_big_endian = false;      // rr_plan_set_row_format: float32 rows as a big-endian file stores them
     bool lean_enabled = true;           // RR_TILE_LEAN=0 (tests): the general tick for every call
     bool uh_pairs = true;               // the fused convolution takes two record batches per launch where it can (RR_UH_PAIRS=0: tests)
+    int32_t rec_batches = kRecLaunchBatches;   // record batches per launch of k_rec_in / k_rec_out in long calls (RR_REC_BATCHES: tests, A/B)
+    bool rec_batches_forced = false;    // RR_REC_BATCHES was given: rec_batches in every call the time-tiled kernel takes
     bool perm_ready = false;            // the streaming kernel's tiled permutations are on the device
     int32_t *d_adj_down = nullptr;      // adjoint (rr_rapid_adjoint_dev): downstream engine position of each position, -1 at outlets
 
@@ -575,21 +579,27 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
         const int64_t np = P->tp.np, levels = P->tp.n_levels, members = std::max<int64_t>(1, s.members);      // an ensemble: the card's budget holds every member's ring
         const int64_t all_chunks = kRecBatch * ((total + 14) / kRecRows + 2) + (dmax >> 4) + 2;
         const int64_t slack = 4;      // room for the in-pass to run ahead of the routing: four batches of 128 tick-rows
+        // The plain record passes take nb batches per launch in long calls -- the call lengths of pick_KC's long tasks; a shorter call's
+        // ring stays as it was -- and the out-pass holds finished batches back until it has nb of them: nb - 1 more batches of ring.  The
+        // largest nb whose ring fits the bounds below at the longest task that fits (RR_REC_BATCHES: that many in every call).
+        const int64_t nb_max = P->rec_batches_forced || total >= 16384 ? std::max<int64_t>(1, P->rec_batches) : 1;
         ok = false;
         // a part of a cut network that feeds another GPU keeps to 64 ticks: every tile level delays its boundary series by one
         // task, and the GPU downstream waits for it (10M reaches on 8 GPUs: whole job 7.2 against 7.1 x 10^11 reach-steps/s in the
         // time-weighted simulation, profiles/r03_pipeline_sim_time.txt)
         const int64_t kc_long = P->n_export > 0 && P->wave_K <= 0 ? 4 : (int64_t{1} << 20);
-        for (int64_t KC = std::min(std::min(pick_KC(P, total + dmax), P->kc_cap), kc_long); KC >= 1; KC /= 2) {
-            const int64_t chunks = std::min<int64_t>(all_chunks, (dmax + levels * KC * kRec) / kRec + slack * kRecBatch);
-            const int64_t bytes = chunks * kRec * np * (int64_t)sizeof(double) * members;
-            // five eighths of the card; the shortest tasks may take thirteen sixteenths: the streaming kernel, the only alternative,
-            // keeps depth x n work rows itself (1M reaches 24k deep: 204 GB of records at K = 16 against 192 GB of rows)
-            if (P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 16 * (KC == 1 ? 13 : 10))) continue;
-            if (KC > 4 && P->wave_K <= 0 && P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 5)) continue;      // long tasks only while the ring stays under a fifth of the card
-            sch.kernel = Kernel::Tile; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np * members;
-            ok = true;
-            break;
+        for (int64_t KC = std::min(std::min(pick_KC(P, total + dmax), P->kc_cap), kc_long); KC >= 1 && !ok; KC /= 2) {
+            for (int64_t nb = nb_max; nb >= 1; --nb) {
+                const int64_t chunks = std::min<int64_t>(all_chunks, (dmax + levels * KC * kRec) / kRec + (slack + nb - 1) * kRecBatch);
+                const int64_t bytes = chunks * kRec * np * (int64_t)sizeof(double) * members;
+                // five eighths of the card; the shortest tasks may take thirteen sixteenths: the streaming kernel, the only alternative,
+                // keeps depth x n work rows itself (1M reaches 24k deep: 204 GB of records at K = 16 against 192 GB of rows)
+                if (P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 16 * (KC == 1 ? 13 : 10))) continue;
+                if (KC > 4 && P->wave_K <= 0 && P->dev_total_bytes > 0 && bytes > (int64_t)(P->dev_total_bytes / 5)) continue;      // long tasks only while the ring stays under a fifth of the card
+                sch.kernel = Kernel::Tile; sch.KC = KC; sch.chunks = chunks; sch.ring = chunks * kRec * np * members; sch.rec_nb = nb;
+                ok = true;
+                break;
+            }
         }
     }
     if (!ok) {      // streaming kernel: lateral rows come in, discharge rows overwrite them in place and stay until the outlet-most reaches have passed them
@@ -705,6 +715,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     if (P->n_export > 0 && !export_series) { S.open = false; return fail(RR_E_INVALID, "plan has export reaches but no export series was given"); }
 
     S.KC = P->sch.KC; S.KS = P->sch.KS; S.rec_chunks = P->sch.chunks;     // ring sized by choose_schedule, allocated by rr_plan_reserve
+    S.rec_nb = S.kernel == Kernel::Tile ? std::max<int64_t>(1, P->sch.rec_nb) : 1;
     if (S.kernel == Kernel::Direct) {
         if (io.uh_kernel || io.runoff || (!io.dev_out && !io.dev_out32) || (mode == Mode::Unit && (io.dev_in32 || P->n_ghost > 0 || P->n_export > 0)) || nsub > kDirectMaxSub ||
             (io.dev_out32 && (io.out_factor < 1 || (S.KC * kRec) % io.out_factor != 0 || T % io.out_factor != 0))) {
@@ -776,10 +787,10 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
                 (long long)n, (long long)T, (long long)(S.KC * kRec), P->dp.n_tiles, P->direct_window, (long long)P->dp.n_holes, (long long)P->dp.n_exports,
                 (long long)P->dp.skel.np, P->dp.skel.n_tiles, P->dp.skel.n_levels, (long long)S.rec_chunks, (double)S.rec_chunks * kRec * P->dp.skel.np * 8 / 1e9);
     else if (getenv("RR_VERBOSE"))
-        fprintf(stderr, "rr: n=%lld T=%lld nsub=%lld tiled=%d K=%lld tiles=%d levels=%d block=%d ghosts=%lld ring_chunks=%lld (%.1f GB) lds=%zu\n",
+        fprintf(stderr, "rr: n=%lld T=%lld nsub=%lld tiled=%d K=%lld tiles=%d levels=%d block=%d ghosts=%lld ring_chunks=%lld (%.1f GB) rec_batches=%lld lds=%zu\n",
                 (long long)n, (long long)T, (long long)nsub, (int)(S.kernel == Kernel::Tile), (long long)(S.KC * kRec), P->tp.n_tiles, P->tp.n_levels, P->tp.block,
                 (long long)P->tp.n_ghost, (long long)S.rec_chunks, S.kernel == Kernel::Tile ? (double)S.rec_chunks * kRec * P->tp.np * 8 / 1e9 : 0.0,
-                tile_lds_bytes(P->wave_threads));
+                (long long)S.rec_nb, tile_lds_bytes(P->wave_threads));
     if (S.kernel == Kernel::Tick) {
         // work ring in engine order: lateral rows come in, discharge rows overwrite them in place; rows stay until the
         // outlet-most reaches have passed them
@@ -1080,12 +1091,14 @@ void launch_rec_out(const RecPermArgs &ra, bool sub, int64_t cols, hipStream_t s
     }
 }
 
-// `count` batches from `batch` on: 1, or 2 for the fused convolution when its rows are there (session_advance_tile)
+// `count` batches from `batch` on (session_advance_tile): up to Session::rec_nb for k_rec_in / k_rec_out, up to 2 for the fused
+// convolution, 1 for gridded runoff
 void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
 {
     Session &S = P->ses;
     const int64_t n = P->h.n;
     RecPermArgs ra{};
+    ra.batches = count;
     ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
     ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = n; ra.np = P->tp.np; ra.T = S.T; ra.total = S.total; ra.batch = batch;
     ra.nsub = Div32((uint32_t)S.nsub);
@@ -1167,9 +1180,12 @@ int session_advance_tile(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, in
             return must_have_left <= 0 || S.ticks_stored >= std::min(S.total, must_have_left);
         };
         if (S.has_in && S.in_batches < S.n_in_batches && ticks_ready >= std::min(kRecRows * (S.in_batches + 1), S.total) && slot_free(S.in_batches)) {
-            // the fused convolution takes the next batch along when that one's rows and ring slots are there too (less to read per value)
-            const int count = (S.io.uh_kernel && !S.io.runoff && P->uh_pairs && S.in_batches + 2 <= S.n_in_batches &&
-                               ticks_ready >= std::min(kRecRows * (S.in_batches + 2), S.total) && slot_free(S.in_batches + 1)) ? 2 : 1;
+            // the next batches along while their rows and ring slots are there too (less to read per value): up to rec_nb for k_rec_in,
+            // two for the fused convolution, one batch a launch for gridded runoff
+            const int max_count = S.io.runoff ? 1 : (S.io.uh_kernel ? (P->uh_pairs ? 2 : 1) : (int)S.rec_nb);
+            int count = 1;
+            while (count < max_count && S.in_batches + count < S.n_in_batches &&
+                   ticks_ready >= std::min(kRecRows * (S.in_batches + count + 1), S.total) && slot_free(S.in_batches + count)) ++count;
             launch_rec_permute(P, true, S.in_batches, count);
             S.in_batches += count;
             progressed = true;
@@ -1206,10 +1222,18 @@ int session_advance_tile(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, in
         if (S.diag >= S.n_diags) done = S.total;
         else if (m_done >= 0) done = std::max<int64_t>(0, (m_done + 1) * K - dmax);
         done = std::min(done, S.total);
-        while (S.out_batches < S.n_out_batches && done >= std::min(kRecRows * (S.out_batches + 1), S.total) &&
-               (std::min(kRecRows * (S.out_batches + 1), S.total) + S.nsub - 1) / S.nsub <= S.out_limit) {
-            launch_rec_permute(P, false, S.out_batches);
-            ++S.out_batches;
+        // finished batches leave rec_nb at a time; fewer at the end of the call, and when nothing else can move -- so every call and every
+        // rr_stream_advance returns with all its finished batches out, as with one batch per launch (choose_schedule: the ring holds the rest)
+        auto out_ready = [&](int64_t j) {
+            const int64_t end = std::min(kRecRows * (j + 1), S.total);
+            return done >= end && (end + S.nsub - 1) / S.nsub <= S.out_limit;
+        };
+        while (S.out_batches < S.n_out_batches) {
+            int count = 0;
+            while (count < S.rec_nb && S.out_batches + count < S.n_out_batches && out_ready(S.out_batches + count)) ++count;
+            if (count == 0 || (count < S.rec_nb && S.out_batches + count < S.n_out_batches && progressed)) break;
+            launch_rec_permute(P, false, S.out_batches, count);
+            S.out_batches += count;
             S.ticks_stored = std::min(S.total, kRecRows * S.out_batches);
             progressed = true;
         }

@@ -14,7 +14,8 @@ namespace {
 // the tile's rows of the batch coalesced: the slot of a row's LAST sub-step holds the row's mean discharge.  B = 16 halves
 // the share of rows / records read twice at a batch's edge but needs 72 KB of LDS per workgroup: 1 % slower when every row
 // comes from HBM (380 vs 384 ms per year), faster only while a short cyclic forcing array is found in a cache
-// (profiles/r02_rec_batch.txt).
+// (profiles/r02_rec_batch.txt).  A workgroup walking several consecutive batches in the same LDS tile (a.batches) reads the
+// edge once per launch instead: DESIGN.md section 4.
 // Tile shapes, each the winner of an A/B on the GPU box: 256 threads (128 to 1,024: within 0.5 %, profiles/r03_rec_threads_ab.txt),
 // 32 columns (16 to 64: the same, r03_rec_tile_width_ab.txt), one tile per workgroup (persistent workgroups with the next tile's
 // loads in flight: 427 / 469 us per 128 rows against 419 / 434, r03_rec_persistent_ab.txt), 8 records per batch (r02_rec_batch.txt).
@@ -22,6 +23,9 @@ constexpr int kRecCols = 32, kRecBatch = 8, kRecThreads = 256;
 constexpr int kRecInThreads = kRecThreads, kRecOutThreads = kRecThreads;      // workgroup sizes of k_rec_in / k_rec_out
 constexpr int kRecInCols = kRecCols, kRecOutCols = kRecCols;                  // columns of a tile of k_rec_in / k_rec_out
 constexpr int kRecRows = 16 * kRecBatch;    // tick-rows of one batch
+// Batches one launch of k_rec_in / k_rec_out walks in a long call (rr_exec.hpp: choose_schedule, session_advance_tile): the rows and
+// records at a batch's edge are read once per launch instead of once per batch, in the same LDS tile.
+constexpr int kRecLaunchBatches = 4, kRecMaxLaunchBatches = 8;
 
 struct RecPermArgs {
     double *rec;
@@ -38,6 +42,7 @@ struct RecPermArgs {
     int32_t swizzle;          // column tiles in XCD-contiguous order (rr_common.hpp: xcd_swizzle)
     int32_t clamp;            // k_rec_out: 0 records hold final values (sub-steps), 1 clamp at zero, 2 clamp all but headwater columns (UnitMuskingum)
     uint32_t in32_sel, out32_sel;   // byte selectors of the float32 rows (rr_plan_set_row_format): kSelNative, or kSelSwap for a big-endian file's rows
+    int32_t batches;          // k_rec_in / k_rec_out: consecutive batches from `batch` on, walked by each workgroup (0 or 1: one)
 };
 
 // Ensembles (rr_kernels_tile.hpp: member_chunk0): member blockIdx.y has its rows at m * row_pitch elements from the first member's and its record
@@ -73,11 +78,11 @@ __device__ __forceinline__ uint32_t ring_chunk(const Div32 &chunks, uint32_t fir
 }
 
 // Second half of the in-pass: the LDS tile (row = runoff row - row_first, kRecTileLd doubles per row) becomes records.
-// BATCH records per column from tick-row kRecRows * a.batch - 15 on (the fused convolution takes two batches at a time).
+// BATCH records per column of batch `batch`, from tick-row kRecRows * batch - 15 on (the fused convolution takes two batches at a time).
 // smeta / sscale: the tile's column metadata and scale in LDS (k_rec_in keeps them there: loaded with the rows, no registers
 // held across the stores), or NULL: read from the plan's arrays.
 template <bool SUB, int THREADS = kRecThreads, int BATCH = kRecBatch, bool LDSMETA = false, int COLS = kRecCols>
-__device__ __forceinline__ void write_records(const RecPermArgs &a, const double *tile, int64_t col0, int64_t tick_first, int64_t row_first,
+__device__ __forceinline__ void write_records(const RecPermArgs &a, const double *tile, int64_t col0, int64_t batch, int64_t tick_first, int64_t row_first,
                                               const int2 *smeta = nullptr, const double *sscale = nullptr)
 {
     constexpr int R = 16 * BATCH + 15;
@@ -98,7 +103,7 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
             f[it] = (a.scale && i < a.n) ? a.scale[i] : 1.0;
         }
     }
-    const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)a.batch);
+    const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)batch);
 #pragma unroll(LDSMETA ? (SUB ? 2 : 4) : IT)
     for (int it = 0; it < IT; ++it) {
         const int piece = it * THREADS + tid;       // (column, record, 16-byte part): 8 consecutive lanes = one record
@@ -131,49 +136,92 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
 // scale travelling with the rows into LDS (no registers held across the stores).  The rows alone read in 186 us per 128 rows at 1M
 // reaches, the records alone store in 199 us, the pass takes 415: within 7 % of the two one after the other
 // (profiles/r03_rec_probe.txt, r03_alias_kernel_times.txt).
+// a.batches consecutive batches of the tile per workgroup (session_advance_tile: rr_plan::rec_batches where the rows and ring slots
+// are there): the 15 tick-rows before a later batch are the last 15 of the one before it, still in LDS -- moved to the tile's top,
+// not read from HBM again (131.75 rows read per 128 at four batches instead of 143).  A later batch's row loads are all in flight
+// before the previous batch's records leave; the column metadata and scale stay in LDS for the whole walk.
 template <bool SUB, bool IN32 = false, bool ENS = false>
-__global__ __launch_bounds__(kRecInThreads) void k_rec_in(const RecArgsOf<ENS> args)
+__global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS> args)
 {
     const RecPermArgs &a = member_args(args);
-    constexpr int R = kRecTileRows;
+    constexpr int R = kRecTileRows, G = kRecInThreads / kRecInCols;      // G rows of the tile loaded at once
     __shared__ double tile[R * (kRecInCols + 1)];
     __shared__ int2 smeta[kRecInCols];
     __shared__ double sscale[kRecInCols];
     const int tid = threadIdx.x;
-    const int64_t tick_first = kRecRows * a.batch - 15;                 // may be negative in the first batch
-    uint32_t sub_unused;
-    const int64_t row_first = SUB ? (int64_t)a.nsub.div((uint32_t)(tick_first < 0 ? 0 : tick_first), sub_unused) : tick_first;
-    constexpr int RPT = (R + kRecInThreads / kRecInCols - 1) / (kRecInThreads / kRecInCols);
+    auto first_row = [&](int64_t tick_first) -> int64_t {      // runoff row of the tile's first tick-row
+        uint32_t sub_unused;
+        return SUB ? (int64_t)a.nsub.div((uint32_t)(tick_first < 0 ? 0 : tick_first), sub_unused) : tick_first;
+    };
+    int64_t tick_first = kRecRows * a.batch - 15;                 // may be negative in the first batch
+    int64_t row_first = first_row(tick_first);
+    constexpr int RPT = (R + G - 1) / G;
     const int c = tid % kRecInCols, r0 = tid / kRecInCols;
     const int need = SUB ? (int)((uint32_t)(R - 1) / a.nsub.d) + 2 : R;     // runoff rows behind the batch's tick-rows
     const uint32_t n_tiles = (uint32_t)((a.n + kRecInCols - 1) / kRecInCols);
     if (blockIdx.x >= n_tiles) return;
     const int64_t col0 = (int64_t)(a.swizzle ? xcd_swizzle(blockIdx.x, n_tiles) : blockIdx.x) * kRecInCols;
-    double v[RPT];
-    int2 cm = make_int2(-1, 0);
-    double cs = 1.0;
-    {   // branch-free: out-of-range rows / columns are clamped here and zeroed on the way into LDS
-        const int64_t i = min(col0 + c, a.n - 1);
+    // branch-free: out-of-range rows / columns are clamped here and zeroed on the way into LDS
+    const int64_t i = min(col0 + c, a.n - 1);
+    const bool live = col0 + c < a.n;
+    auto load = [&](int64_t t) -> double {
+        const int64_t off = a.rows.offset(t < 0 ? 0 : (t >= a.T ? a.T - 1 : t)) + i;
+        return IN32 ? (double)f32_from_file(a.rows_in32[off], a.in32_sel) : a.rows.base[off];
+    };
+    {
+        double v[RPT];
+        int2 cm = make_int2(-1, 0);
+        double cs = 1.0;
         if (tid < kRecInCols) {
-            cm = col0 + c < a.n ? a.colmeta[i] : make_int2(-1, 0);
+            cm = live ? a.colmeta[i] : make_int2(-1, 0);
             cs = a.scale ? a.scale[i] : 1.0;
         }
 #pragma unroll
-        for (int q = 0; q < RPT; ++q) {
-            const int64_t t = row_first + min(r0 + q * (kRecInThreads / kRecInCols), need - 1);
-            const int64_t off = a.rows.offset(t < 0 ? 0 : (t >= a.T ? a.T - 1 : t)) + i;
-            v[q] = IN32 ? (double)f32_from_file(a.rows_in32[off], a.in32_sel) : a.rows.base[off];
-        }
-    }
+        for (int q = 0; q < RPT; ++q) v[q] = load(row_first + min(r0 + q * G, need - 1));
 #pragma unroll
-    for (int q = 0; q < RPT; ++q) {
-        const int r = r0 + q * (kRecInThreads / kRecInCols);
-        const int64_t row = row_first + r;
-        if (r < R) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && col0 + c < a.n) ? v[q] : 0.0;
+        for (int q = 0; q < RPT; ++q) {
+            const int r = r0 + q * G;
+            const int64_t row = row_first + r;
+            if (r < R) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && live) ? v[q] : 0.0;
+        }
+        if (tid < kRecInCols) { smeta[c] = cm; sscale[c] = cs; }
     }
-    if (tid < kRecInCols) { smeta[c] = cm; sscale[c] = cs; }
     __syncthreads();
-    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, tick_first, row_first, smeta, sscale);
+    const int nb = a.batches > 1 ? a.batches : 1;
+    for (int b = 1; b < nb; ++b) {
+        // the next batch's tile, rows [row_next, row_next + need): its first `keep` rows are this tile's last -- 15 without sub-steps, with
+        // them at most 17 (a tile spans 142 / nsub + 2 rows, the next starts at least 113 / nsub - 1 rows further: KPT * G = 24 is room enough)
+        constexpr int NPT = kRecRows / G, KPT = 3;      // new rows (at most 128) / kept rows per thread
+        const int64_t tick_next = tick_first + kRecRows, row_next = first_row(tick_next);
+        const int shift = (int)(row_next - row_first), keep = max(need - shift, 0);
+        double v[NPT], kv[KPT];
+#pragma unroll
+        for (int q = 0; q < NPT; ++q) {
+            const int r = keep + r0 + q * G;
+            if (r < need) v[q] = load(row_next + r);
+        }
+        write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, sscale);
+#pragma unroll
+        for (int q = 0; q < KPT; ++q) {
+            const int r = r0 + q * G;
+            if (r < keep) kv[q] = tile[(shift + r) * (kRecInCols + 1) + c];
+        }
+        __syncthreads();      // every record of the batch has been read out of the tile
+#pragma unroll
+        for (int q = 0; q < KPT; ++q) {
+            const int r = r0 + q * G;
+            if (r < keep) tile[r * (kRecInCols + 1) + c] = kv[q];
+        }
+#pragma unroll
+        for (int q = 0; q < NPT; ++q) {
+            const int r = keep + r0 + q * G;
+            const int64_t row = row_next + r;
+            if (r < need) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && live) ? v[q] : 0.0;
+        }
+        __syncthreads();
+        tick_first = tick_next; row_first = row_next;
+    }
+    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, sscale);
 }
 
 // The in-pass with the unit-hydrograph convolution fused in (UnitHydrograph.py:93-107, direct form): the tile is COMPUTED
@@ -310,85 +358,124 @@ __global__ __launch_bounds__(uh_threads(BATCHES)) void k_rec_in_uh(const RecPerm
         for (int j = 0; j < RP; ++j) op[j * kUhTileLd] = acc[j];      // rb + j < win_rows: the rows past the tile's end are written and never read
     }
     __syncthreads();
-    write_records<SUB, uh_threads(BATCHES), kRecBatch * BATCHES, false, kUhCols>(a, dt, col0, tick_first, row_first);
+    write_records<SUB, uh_threads(BATCHES), kRecBatch * BATCHES, false, kUhCols>(a, dt, col0, a.batch, tick_first, row_first);
 }
 
 // OUT32: the router's post-processing fused in (TransformMuskingum.py:128-142): mean over `factor` consecutive rows
 // (sequential sum, one division, as numpy reduces a strided axis) and the float32 cast; 128 % (factor * nsub) == 0.
 // One column tile per workgroup, every record read of it in flight at once.
+// a.batches consecutive batches per workgroup, as k_rec_in: a later batch reads its eight new records only -- its first is the one
+// before's ninth, still in LDS (moved to the front) -- 8.25 records read per batch at four batches instead of 9.  Its record loads
+// are all in flight before the previous batch's rows leave; the column metadata stays in LDS.
 template <bool SUB, bool OUT32, bool ENS = false>
 __global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS> args)
 {
     const RecPermArgs &a = member_args(args);
     constexpr int S = 16 * (kRecBatch + 1);
     __shared__ double recs[kRecOutCols][S + 1];
+    __shared__ int2 smeta[kRecOutCols];
     const int tid = threadIdx.x;
     static_assert(kRecOutCols * (kRecBatch + 1) * 8 % kRecOutThreads == 0, "record pieces of a tile must divide among the threads");
-    constexpr int IT = kRecOutCols * (kRecBatch + 1) * 8 / kRecOutThreads;
+    static_assert(kRecOutCols * 8 == kRecOutThreads, "one 16-byte piece of the records kept between batches per thread");
+    constexpr int IT = kRecOutCols * (kRecBatch + 1) * 8 / kRecOutThreads, ITN = kRecOutCols * kRecBatch * 8 / kRecOutThreads;
     const uint32_t n_tiles = (uint32_t)((a.n + kRecOutCols - 1) / kRecOutCols);
     if (blockIdx.x >= n_tiles) return;
     const int64_t col0 = (int64_t)(a.swizzle ? xcd_swizzle(blockIdx.x, n_tiles) : blockIdx.x) * kRecOutCols;
     typedef double d2 __attribute__((ext_vector_type(2)));
-    d2 v[IT];
-    const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)a.batch);
-    {   // a column past the end reads position 0 and is not written
-        int2 meta[IT];
+    {
+        d2 v[IT];
+        const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)a.batch);
+        {   // a column past the end reads position 0 and is not written
+            int2 meta[IT];
 #pragma unroll
-        for (int it = 0; it < IT; ++it) {      // every metadata load first: the record loads depend on them, one wait for all
-            const int64_t i = col0 + (it * kRecOutThreads + tid) / ((kRecBatch + 1) * 8);
-            meta[it] = i < a.n ? a.colmeta[i] : make_int2(0, 0);
+            for (int it = 0; it < IT; ++it) {      // every metadata load first: the record loads depend on them, one wait for all
+                const int64_t i = col0 + (it * kRecOutThreads + tid) / ((kRecBatch + 1) * 8);
+                meta[it] = i < a.n ? a.colmeta[i] : make_int2(0, 0);
+            }
+#pragma unroll
+            for (int it = 0; it < IT; ++it) {
+                const int piece = it * kRecOutThreads + tid;
+                const int k = (piece >> 3) % (kRecBatch + 1), part = piece & 7;
+                const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)((meta[it].y & kLagMask) >> 4) + k);
+                v[it] = reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, meta[it].x))[part];
+            }
         }
 #pragma unroll
         for (int it = 0; it < IT; ++it) {
             const int piece = it * kRecOutThreads + tid;
-            const int k = (piece >> 3) % (kRecBatch + 1), part = piece & 7;
-            const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)((meta[it].y & kLagMask) >> 4) + k);
-            v[it] = reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, meta[it].x))[part];
+            const int c = piece / ((kRecBatch + 1) * 8), k = (piece >> 3) % (kRecBatch + 1), part = piece & 7;
+            recs[c][16 * k + 2 * part] = v[it].x;
+            recs[c][16 * k + 2 * part + 1] = v[it].y;
         }
     }
-    const int64_t tick0 = kRecRows * a.batch;
-#pragma unroll
-    for (int it = 0; it < IT; ++it) {
-        const int piece = it * kRecOutThreads + tid;
-        const int c = piece / ((kRecBatch + 1) * 8), k = (piece >> 3) % (kRecBatch + 1), part = piece & 7;
-        recs[c][16 * k + 2 * part] = v[it].x;
-        recs[c][16 * k + 2 * part + 1] = v[it].y;
-    }
-    __syncthreads();
     const int c = tid % kRecOutCols;
     const int64_t i = col0 + c;
-    if (i >= a.n) return;
-    const int32_t my = a.colmeta[i].y;
+    const bool live = i < a.n;
+    const int2 cm = live ? a.colmeta[i] : make_int2(0, 0);
+    if (tid < kRecOutCols) smeta[c] = cm;
+    __syncthreads();
+    const int32_t my = cm.y;
     const int o = my & 15;
-    const int64_t io = a.cols ? a.cols[i] : i;      // destination column; the float32 rows' pitch is the float64 rows' (rows.ld)
+    const int64_t io = !live ? 0 : (a.cols ? a.cols[i] : i);      // destination column; the float32 rows' pitch is the float64 rows' (rows.ld)
     // single sub-step: the records hold the unclamped discharge (a ghost's record is a copy of its reach's); the reference's
     // clip at zero (_numba_kernels.py:80) happens here.  UnitMuskingum leaves its headwaters' lateral inflow as it is (:122-123).
     const bool clamp = !SUB && (a.clamp == 1 || (a.clamp == 2 && !(my & kColHeadwater)));
     auto out = [&](double x) { return clamp && !(x > 0.0) ? 0.0 : x; };
-    if (OUT32) {
-        // output row q averages runoff rows [q * factor, (q + 1) * factor), each the slot of its last sub-step
-        const int step = (int)(a.factor.d * (SUB ? a.nsub.d : 1u));          // tick-rows per output row, divides 128
-        const int64_t q0 = tick0 / step;
-        for (int q = tid / kRecOutCols; q < kRecRows / step; q += kRecOutThreads / kRecOutCols) {
-            if ((q0 + q + 1) * step > a.total) break;
-            const int nsub = SUB ? (int)a.nsub.d : 1;
-            double acc = out(recs[c][o + q * step + nsub - 1]);
-            for (int j = 1; j < (int)a.factor.d; ++j) acc += out(recs[c][o + q * step + j * nsub + nsub - 1]);
-            a.rows32[(q0 + q) * a.rows.ld + io] = f32_to_file((float)(a.factor.d > 1 ? acc / (double)a.factor.d : acc), a.out32_sel);
-        }
-    } else {
-        for (int r = tid / kRecOutCols; r < kRecRows; r += kRecOutThreads / kRecOutCols) {
-            const int64_t tick = tick0 + r;
-            if (tick >= a.total) break;
-            if (SUB) {
-                uint32_t sub;
-                const uint32_t row = a.nsub.div((uint32_t)tick, sub);
-                if (sub + 1 == a.nsub.d) a.rows.row(row)[io] = recs[c][o + r];
-            } else {
-                a.rows.row(tick)[io] = out(recs[c][o + r]);
+    auto write_rows = [&](int64_t tick0) {      // the tile's rows of the batch from tick-row tick0 on; a column past the end writes nothing
+        if (!live) return;
+        if (OUT32) {
+            // output row q averages runoff rows [q * factor, (q + 1) * factor), each the slot of its last sub-step
+            const int step = (int)(a.factor.d * (SUB ? a.nsub.d : 1u));          // tick-rows per output row, divides 128
+            const int64_t q0 = tick0 / step;
+            for (int q = tid / kRecOutCols; q < kRecRows / step; q += kRecOutThreads / kRecOutCols) {
+                if ((q0 + q + 1) * step > a.total) break;
+                const int nsub = SUB ? (int)a.nsub.d : 1;
+                double acc = out(recs[c][o + q * step + nsub - 1]);
+                for (int j = 1; j < (int)a.factor.d; ++j) acc += out(recs[c][o + q * step + j * nsub + nsub - 1]);
+                a.rows32[(q0 + q) * a.rows.ld + io] = f32_to_file((float)(a.factor.d > 1 ? acc / (double)a.factor.d : acc), a.out32_sel);
+            }
+        } else {
+            for (int r = tid / kRecOutCols; r < kRecRows; r += kRecOutThreads / kRecOutCols) {
+                const int64_t tick = tick0 + r;
+                if (tick >= a.total) break;
+                if (SUB) {
+                    uint32_t sub;
+                    const uint32_t row = a.nsub.div((uint32_t)tick, sub);
+                    if (sub + 1 == a.nsub.d) a.rows.row(row)[io] = recs[c][o + r];
+                } else {
+                    a.rows.row(tick)[io] = out(recs[c][o + r]);
+                }
             }
         }
+    };
+    const int nb = a.batches > 1 ? a.batches : 1;
+    for (int b = 1; b < nb; ++b) {
+        d2 v[ITN];
+        const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)(a.batch + b));
+#pragma unroll
+        for (int it = 0; it < ITN; ++it) {      // records 1 .. kRecBatch of the batch
+            const int piece = it * kRecOutThreads + tid;
+            const int2 m = smeta[piece / (kRecBatch * 8)];
+            const int k = 1 + (piece >> 3) % kRecBatch, part = piece & 7;
+            const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)((m.y & kLagMask) >> 4) + k);
+            v[it] = reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, m.x))[part];
+        }
+        write_rows(kRecRows * (a.batch + b - 1));
+        const int kc = tid >> 3, kp = tid & 7;      // the piece of the last record this thread moves to the front
+        const double k0 = recs[kc][16 * kRecBatch + 2 * kp], k1 = recs[kc][16 * kRecBatch + 2 * kp + 1];
+        __syncthreads();      // every row of the batch has been read out of the records
+        recs[kc][2 * kp] = k0;
+        recs[kc][2 * kp + 1] = k1;
+#pragma unroll
+        for (int it = 0; it < ITN; ++it) {
+            const int piece = it * kRecOutThreads + tid;
+            const int cc = piece / (kRecBatch * 8), k = 1 + (piece >> 3) % kRecBatch, part = piece & 7;
+            recs[cc][16 * k + 2 * part] = v[it].x;
+            recs[cc][16 * k + 2 * part + 1] = v[it].y;
+        }
+        __syncthreads();
     }
+    write_rows(kRecRows * (a.batch + nb - 1));
 }
 
 // Router post-processing on the device (TransformMuskingum.py:128-142): mean over `factor` consecutive rows
