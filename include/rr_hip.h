@@ -13,6 +13,8 @@
  *                          (call site river_route/routers/UnitMuskingum.py:82-92)
  *   rr_uh_convolve      <- UnitHydrograph.convolve  river_route/uhkernels/UnitHydrograph.py:77-107
  *                          (call site river_route/routers/UnitMuskingum.py:75)
+ *   rr_unit_adjoint_dev <- the gradient of a loss through unit_route (same lines), rr_uh_adjoint_dev <- through
+ *                          UnitHydrograph.convolve (same lines); rr_rapid_adjoint_dev <- through rapid_route
  *   rr_plan_create      <- the CSC structure the routers take from tools.adjacency_matrix
  *                          (river_route/tools.py:75-109; river_route/routers/Muskingum.py:189-192)
  *   rr_plan_set_coeffs  <- the coefficient vectors of Muskingum._set_muskingum_coefficients
@@ -430,6 +432,45 @@ int rr_rapid_adjoint_work_bytes(rr_plan *plan, int64_t T, int64_t nsub, int64_t 
 int rr_rapid_adjoint_dev(rr_plan *plan, const double *q0, const double *lateral, int64_t lat_rows, const double *discharge,
                          const double *grad_out, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef,
                          void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream);
+
+/* ---- adjoint of UnitMuskingum routing ----
+ * The gradient of a scalar loss L through one rr_unit_route_dev call (unit_route, river_route/routers/_numba_kernels.py:88-171, with
+ * the edge data of the reference's callers: a_inner_data = a_hw_data = 1, lhs_off_data = -c1 of the row) of T rows, nsub sub-steps,
+ * S = T * nsub, with the coefficients as last set by rr_plan_set_coeffs.  Rows are (time, reach) in params order, states are indexed
+ * by inner reach (ascending params order) as rr_unit_route_dev takes them, all on the plan's device:
+ *   q_ch0, q_full0[n_inner]  the states the forward call started from (needed with grad_coef);
+ *   lateral[lat_rows*n]      its convolved lateral rows (the first T are read; needed with grad_coef);
+ *   discharge[T*n]           its discharge (the clamp mask of the inner reaches); needed with grad_out;
+ *   grad_out[T*n]            dL/d(discharge), or NULL;  grad_qch_final, grad_qfull_final[n_inner]  dL/d(final states), or NULL;
+ * and it writes what is asked for (NULL: not computed):
+ *   grad_lateral[T*n];  grad_qch0, grad_qfull0[n_inner];
+ *   grad_coef[3*n]           dL/dc1, dL/dc2, dL/dc3 per reach in params order, 0 at headwaters (their coefficients are never read).
+ * Work memory (caller-provided, rr_unit_adjoint_work_bytes; the call allocates nothing and only enqueues on `stream`):
+ *   8 n (2 S + 2 T + 2 depth + min(T, 16) + 3 splits + 6) bytes, splits = min(S, ceil(2048 / ceil(n / 256))): the forward tape of
+ *   q_full (a headwater's slot holds its lateral inflow) and the adjoint tape of dL/dq_ch (S + depth rows each), lateral and gradient
+ *   rows in engine order, the reduction's partial sums, six scratch rows.
+ * rr_unit_adjoint_work_bytes also readies the plan for adjoint calls: call it before the first.  No atomics: the same inputs give the
+ * same bits.  RR_E_UNSUPPORTED for general edge data (rr_plan_set_unit_weights), per-edge weights, a plan with boundary reaches and a
+ * host-only plan; RR_E_INVALID for a null or short argument or too little work memory. */
+int rr_unit_adjoint_work_bytes(rr_plan *plan, int64_t T, int64_t nsub, int64_t *bytes);
+int rr_unit_adjoint_dev(rr_plan *plan, const double *q_ch0, const double *q_full0, const double *lateral, int64_t lat_rows,
+                        const double *discharge, const double *grad_out, const double *grad_qch_final, const double *grad_qfull_final,
+                        double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
+                        int64_t T, int64_t nsub, void *stream);
+
+/* ---- adjoint of the unit-hydrograph convolution ----
+ * The gradient through one rr_uh_convolve_dev call (UnitHydrograph.convolve, river_route/uhkernels/UnitHydrograph.py:93-107):
+ * buf = full convolution of depth[T*n] with kernel[n_ks*n] along time, buf[:n_ks] += state; convolved = buf[:T], the state it leaves
+ * is buf[T:] in its first n_ks - 1 rows and 0 in its last.  With G = dL/dbuf (grad_convolved below T, grad_state_out above):
+ *   grad_depth[t,i] = sum_j kernel[j,i] G[t+j,i];  grad_kernel[j,i] = sum_t depth[t,i] G[t+j,i];  grad_state[t',i] = G[t',i], t' < n_ks.
+ * grad_convolved[T*n] and grad_state_out[n_ks*n] may be NULL (no gradient arrives there); a NULL output is not computed; depth is
+ * needed with grad_kernel, kernel with grad_depth.  Work memory (rr_uh_adjoint_work_bytes): 8 n n_ks splits bytes, splits =
+ * min(T, ceil(2048 / (ceil(n / 256) ceil(n_ks / 16)))) row ranges of grad_kernel merged in order, or none when splits = 1.
+ * Enqueue only, no atomics.  RR_E_INVALID for a null or short argument. */
+int rr_uh_adjoint_work_bytes(int64_t T, int64_t n_ks, int64_t n, int64_t *bytes);
+int rr_uh_adjoint_dev(int device, const double *kernel, const double *depth, const double *grad_convolved, const double *grad_state_out,
+                      double *grad_depth, double *grad_kernel, double *grad_state, void *work, int64_t work_bytes, int64_t T,
+                      int64_t n_ks, int64_t n, void *stream);
 
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);

@@ -26,6 +26,7 @@
 #include "rr_kernels_metrics.hpp"
 #include "rr_kernels_overlap.hpp"
 #include "rr_kernels_adjoint.hpp"
+#include "rr_kernels_adjoint_unit.hpp"
 #include "rr_exec.hpp"
 
 // ------------------------------------------------------------------------------------------------
@@ -1281,6 +1282,228 @@ int rr_rapid_adjoint_dev(rr_plan *P, const double *q0, const double *lateral, in
         hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, egrad, (const double *)mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
                            T, nsub, S, (int32_t)dmax);
         rows_between(1, egrad, grad_lateral);
+    }
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// ---- adjoint of UnitMuskingum routing and of the unit-hydrograph convolution (rr_kernels_adjoint_unit.hpp) ----
+
+namespace {
+
+// The work memory of one UnitMuskingum adjoint call, in doubles, front to back: q_full tape and mu tape as in AdjointLayout, lateral
+// and gradient rows in engine order, the permutation's intermediate rows, the reduction slab (3 x n per sub-step range), six scratch
+// rows: k_tick_unit's running sum and its discarded discharge row, q_ch (updated in place), q_ch0, dL/d(q_ch final), dL/d(q_full final).
+AdjointLayout unit_adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub)
+{
+    AdjointLayout L = adjoint_layout(n, depth, T, nsub);
+    L.scratch = L.slab + L.splits * 3 * n;
+    L.total = L.scratch + 6 * n;
+    return L;
+}
+
+constexpr int kUhAdjRows = 16;      // rows per thread of k_uh_adjoint_depth
+constexpr int kUhAdjTaps = 16;      // taps per thread of k_uh_adjoint_kernel
+
+struct UhAdjointLayout { int64_t tap_blocks, splits, rows_per_split; };
+
+UhAdjointLayout uh_adjoint_layout(int64_t T, int64_t n_ks, int64_t n)
+{
+    UhAdjointLayout L{};
+    L.tap_blocks = (n_ks + kUhAdjTaps - 1) / kUhAdjTaps;
+    const int64_t blocks = std::max<int64_t>(1, ((n + kBlock - 1) / kBlock) * L.tap_blocks);
+    const int64_t want = std::max<int64_t>(1, (kAdjTargetBlocks + blocks - 1) / blocks);
+    L.splits = std::max<int64_t>(1, std::min(want, T));
+    L.rows_per_split = (T + L.splits - 1) / L.splits;
+    L.splits = (T + L.rows_per_split - 1) / L.rows_per_split;
+    return L;
+}
+
+}  // namespace
+
+int rr_unit_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
+{
+    if (!P || !bytes) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: null argument");
+    *bytes = 0;
+    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_work_bytes: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
+    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: need T >= 1 and sub-steps >= 1");
+    const rr::HostPlan &H = P->h;
+    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: too many sub-steps for one call: split the series into windows");
+    HIPCHK(hipSetDevice(P->device));
+    if (H.n == 0) return RR_OK;
+    if (int rc = adjoint_ready(P)) return rc;
+    *bytes = unit_adjoint_layout(H.n, H.depth, T, nsub).total * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_unit_adjoint_dev(rr_plan *P, const double *q_ch0, const double *q_full0, const double *lateral, int64_t lat_rows,
+                        const double *discharge, const double *grad_out, const double *grad_qch_final, const double *grad_qfull_final,
+                        double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
+                        int64_t T, int64_t nsub, void *stream)
+{
+    if (!P) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: null plan");
+    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
+    HIPCHK(hipSetDevice(P->device));
+    if (P->n_ghost > 0 || P->n_export > 0)
+        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: the plan has boundary reaches (rr_plan_set_boundary): partitioned networks have no adjoint");
+    if (P->unit_general)
+        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: general edge data (rr_plan_set_unit_weights): the adjoint is that of the reference callers' unit weights");
+    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_unit_adjoint_dev called before rr_plan_set_coeffs");
+    if (!P->weights_uniform)
+        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: per-edge weights (lhs_off_data not -c1 of the downstream reach): the adjoint needs one c1 per reach");
+    if (P->ses.open) return fail(RR_E_STATE, "rr_unit_adjoint_dev: a routing call is open");
+    const rr::HostPlan &H = P->h;
+    const int64_t n = H.n, ni = (int64_t)H.inner_pos.size();
+    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: need T >= 1 and sub-steps >= 1");
+    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: too many sub-steps for one call: split the series into windows");
+    if (ni == 0) { grad_qch0 = nullptr; grad_qfull0 = nullptr; }      // no inner reach: the state vectors are empty
+    if (n == 0 || (!grad_lateral && !grad_qch0 && !grad_qfull0 && !grad_coef)) return RR_OK;
+    if (grad_coef && ni > 0 && (!q_ch0 || !q_full0 || !lateral))
+        return fail(RR_E_INVALID, "rr_unit_adjoint_dev: the coefficient gradients need q_ch0, q_full0 and the lateral rows");
+    if (lateral && lat_rows < T) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: fewer lateral rows than T");
+    if (grad_out && !discharge) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: grad_out needs the discharge of the forward call (its clamp mask)");
+    const AdjointLayout L = unit_adjoint_layout(n, H.depth, T, nsub);
+    const int64_t need = L.total * (int64_t)sizeof(double);
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_unit_adjoint_dev: work memory smaller than rr_unit_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    if (!P->perm_ready || !P->d_adj_down)
+        return fail(RR_E_STATE, "rr_unit_adjoint_dev: call rr_unit_adjoint_work_bytes first (it uploads the plan's permutation tables once)");
+
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t S = T * nsub, dmax = H.depth - 1, ticks = S + dmax;
+    double *const base = static_cast<double *>(work);
+    double *qtape = base + L.qtape, *mtape = base + L.mtape, *elat = base + L.lat, *egrad = base + L.grad, *mrows = base + L.mrows,
+           *slab = base + L.slab, *isum = base + L.scratch, *oscr = isum + n, *qch = oscr + n, *qch0e = qch + n, *gcf = qch0e + n, *gff = gcf + n;
+    const bool one = nsub == 1, tape = grad_coef && ni > 0;
+    const unsigned row_blocks = (unsigned)std::min<int64_t>(T, 65535);
+    auto rows_between = [&](int which, const double *src, double *dst) {      // T rows, params <-> engine order
+        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
+            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
+                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
+    };
+
+    // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        hipLaunchKernelGGL(k_adj_mask_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, mtape, grad_out, discharge,
+                           (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
+        rows_between(0, mtape, egrad);
+    }
+    if (ni > 0 && (tape || grad_qch_final || grad_qfull_final))
+        hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff, grad_qch_final,
+                           grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
+    // the forward again, into a tick-indexed tape: k_tick_unit on its one-weight branch, its three rotating rows spread over the tape
+    if (tape) {
+        rows_between(0, lateral, elat);
+        UnitTickArgs ua{};
+        TickArgs &a = ua.t;
+        a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c1row = P->d_c1row_h; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
+        a.isum = isum; a.bidx = P->d_bidx; a.ghost = nullptr; a.exports = nullptr; a.n_ghost = 0; a.n_export = 0;
+        a.in = elat; a.in_ld = n; a.in_rows = Div32((uint32_t)T);
+        a.out = oscr; a.out_ld = 0; a.out_rows = Div32(1u);      // discharge rows are not kept: every row lands on one scratch row
+        a.total_substeps = S; a.nsub = Div32((uint32_t)nsub); a.inv_nsub = 1.0 / (double)nsub;
+        ua.hw_children = P->d_hwc; ua.qch = qch; ua.a2 = nullptr; ua.c1own = nullptr; ua.zc = nullptr; ua.za = nullptr;
+        for (int64_t tau = 0; tau < ticks; ++tau) {
+            const int64_t lag_lo = std::max<int64_t>(0, tau - S + 1), lag_hi = std::min<int64_t>(tau, dmax);
+            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
+            if (p_hi <= p_lo) continue;
+            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+            a.xc = qtape + (tau + 2) * n; a.xa = a.xc - n; a.xb = a.xc - 2 * n;
+            const dim3 g = grid1(p_hi - p_lo);
+            if (one) hipLaunchKernelGGL(k_tick_unit<true>, g, dim3(kBlock), 0, st, ua);
+            else hipLaunchKernelGGL(k_tick_unit<false>, g, dim3(kBlock), 0, st, ua);
+        }
+    }
+    // reverse ticks: reach at lag l runs reverse step tau - (Dmax - l); with no inner reach there is no state and no tick
+    if (ni > 0) {
+        UnitAdjTickArgs a{};
+        a.lag = P->d_lag; a.child_ptr = P->d_child_ptr; a.down = P->d_adj_down; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3;
+        a.g = grad_out ? egrad : nullptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
+        a.n = n; a.dmax = (int32_t)dmax; a.total_substeps = S; a.nsub = Div32((uint32_t)nsub);
+        for (int64_t tau = 0; tau < ticks; ++tau) {
+            const int64_t lag_lo = std::max<int64_t>(0, dmax - tau), lag_hi = std::min<int64_t>(dmax, dmax - tau + S - 1);
+            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
+            if (p_hi <= p_lo) continue;
+            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+            a.mc = mtape + tau * n;
+            a.ma = tau >= 1 ? a.mc - n : a.mc;      // never read at tick 0 (nothing runs r > 0 or has a downstream reach there)
+            a.mb = tau >= 2 ? a.mc - 2 * n : a.mc;  // read from tick 2 on only
+            const dim3 g = grid1(p_hi - p_lo);
+            if (one) hipLaunchKernelGGL(k_adj_tick_unit<true>, g, dim3(kBlock), 0, st, a);
+            else hipLaunchKernelGGL(k_adj_tick_unit<false>, g, dim3(kBlock), 0, st, a);
+        }
+    }
+    if (tape) {
+        UnitAdjReduceArgs r{};
+        r.lag = P->d_lag; r.child_ptr = P->d_child_ptr; r.hw_children = P->d_hwc; r.qtape = qtape; r.mtape = mtape; r.lat = elat; r.qch0 = qch0e;
+        r.slab = slab; r.n = n; r.total_substeps = S; r.steps_per_split = L.steps_per_split; r.dmax = (int32_t)dmax; r.nsub = Div32((uint32_t)nsub);
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits);
+        if (one) hipLaunchKernelGGL(k_adj_reduce_unit<true>, g, dim3(kBlock), 0, st, r);
+        else hipLaunchKernelGGL(k_adj_reduce_unit<false>, g, dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef)
+        hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)slab, L.splits, (const int32_t *)P->d_child_ptr,
+                           (const int32_t *)P->d_perm, n, grad_coef);
+    if (grad_qch0 || grad_qfull0)
+        hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)mtape,
+                           (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)dmax);
+    if (grad_lateral) {
+        hipLaunchKernelGGL(k_adj_rows_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, egrad,
+                           grad_out ? (const double *)egrad : nullptr, grad_qfull_final ? (const double *)gff : nullptr, (const double *)mtape,
+                           (const int32_t *)P->d_lag, (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w,
+                           (const double *)P->d_c2, n, T, nsub, S, (int32_t)dmax);
+        rows_between(1, egrad, grad_lateral);
+    }
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_uh_adjoint_work_bytes(int64_t T, int64_t n_ks, int64_t n, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, "rr_uh_adjoint_work_bytes: null argument");
+    *bytes = 0;
+    if (T < 1 || n_ks < 1 || n < 0 || n_ks > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_uh_adjoint_work_bytes: need T >= 1, n_ks >= 1, n >= 0");
+    const UhAdjointLayout L = uh_adjoint_layout(T, n_ks, n);
+    if (L.splits > 1) *bytes = L.splits * n_ks * n * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_uh_adjoint_dev(int device, const double *kernel, const double *depth, const double *grad_convolved, const double *grad_state_out,
+                      double *grad_depth, double *grad_kernel, double *grad_state, void *work, int64_t work_bytes, int64_t T,
+                      int64_t n_ks, int64_t n, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_uh_adjoint_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    if (T < 1 || n_ks < 1 || n < 0 || n_ks > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_uh_adjoint_dev: need T >= 1, n_ks >= 1, n >= 0");
+    if (n == 0 || (!grad_depth && !grad_kernel && !grad_state)) return RR_OK;
+    if (grad_depth && !kernel) return fail(RR_E_INVALID, "rr_uh_adjoint_dev: grad_depth needs the kernel");
+    if (grad_kernel && !depth) return fail(RR_E_INVALID, "rr_uh_adjoint_dev: grad_kernel needs the depth rows");
+    const UhAdjointLayout L = uh_adjoint_layout(T, n_ks, n);
+    const int64_t need = L.splits > 1 ? L.splits * n_ks * n * (int64_t)sizeof(double) : 0;
+    if (grad_kernel && need > 0 && (!work || work_bytes < need))
+        return fail(RR_E_INVALID, "rr_uh_adjoint_dev: work memory smaller than rr_uh_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    const hipStream_t st = (hipStream_t)stream;
+    const UhGrad G{grad_convolved, grad_state_out, T, n, T + n_ks - 1};
+    const unsigned col_blocks = (unsigned)((n + kBlock - 1) / kBlock);
+    if (grad_depth) {
+        const int64_t row_blocks = (T + kUhAdjRows - 1) / kUhAdjRows;
+        if (row_blocks > 65535) return fail(RR_E_INVALID, "rr_uh_adjoint_dev: too many rows for one call: split the series into windows");
+        hipLaunchKernelGGL(k_uh_adjoint_depth<kUhAdjRows>, dim3(col_blocks, (unsigned)row_blocks), dim3(kBlock), 0, st, kernel, G, grad_depth, (int32_t)n_ks);
+    }
+    if (grad_kernel) {
+        if (L.tap_blocks > 65535) return fail(RR_E_INVALID, "rr_uh_adjoint_dev: too many kernel steps");
+        double *slab = L.splits > 1 ? static_cast<double *>(work) : grad_kernel;
+        hipLaunchKernelGGL(k_uh_adjoint_kernel<kUhAdjTaps>, dim3(col_blocks, (unsigned)L.splits, (unsigned)L.tap_blocks), dim3(kBlock), 0, st, depth, G,
+                           slab, (int32_t)n_ks, L.rows_per_split);
+        if (L.splits > 1) {
+            const int64_t count = n_ks * n;
+            hipLaunchKernelGGL(k_uh_adjoint_merge, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st,
+                               (const double *)slab, L.splits, count, grad_kernel);
+        }
+    }
+    if (grad_state) {
+        const int64_t count = n_ks * n;
+        hipLaunchKernelGGL(k_uh_adjoint_state, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st, G, grad_state, n_ks);
     }
     HIPCHK(hipGetLastError());
     return RR_OK;

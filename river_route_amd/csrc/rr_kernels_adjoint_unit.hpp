@@ -1,0 +1,301 @@
+// rr_kernels_adjoint_unit.hpp -- the adjoint of UnitMuskingum routing (rr_unit_adjoint_dev) and of the unit-hydrograph convolution
+// (rr_uh_adjoint_dev), DESIGN.md section 12.  Part of the one translation unit rr_engine.hip builds (included from there, after
+// rr_kernels_adjoint.hpp; not a stand-alone header).
+//
+// Forward (river_route/routers/_numba_kernels.py:114-171 with the callers' unit edge weights), inner reach i with headwater
+// tributaries H(i) and inner tributaries U(i), equation s = 1..S, row t = (s - 1) / nsub:
+//   q_ch[s,i]   = c1[i] (sum_H l[t,h] + sum_U q_full[s,u]) + c2[i] (sum_H l[t,h] + sum_U q_full[s-1,u]) + c3[i] q_ch[s-1,i]
+//   q_full[s,i] = q_ch[s,i] + l[t,i]
+//   out[t,i]    = max(mean of q_full over the row's sub-steps, 0);      out[t,h] = l[t,h] (no clamp, no mean)
+// Adjoint, backward from s = S, d = down(i) (an inner reach), g[s,i] = [out[t,i] > 0] dL/dout[t,i] / nsub, mu[S+1] = 0:
+//   phi[s,i] = g[s,i] + [s=S] dL/dq_full_final[i] + c1[d] mu[s,d] + c2[d] mu[s+1,d]            (dL/dq_full[s,i])
+//   mu[s,i]  = phi[s,i] + [s=S] dL/dq_ch_final[i] + c3[i] mu[s+1,i]                            (dL/dq_ch[s,i])
+// Only mu is taped: phi reads nothing of reach i but g, so the row pass builds it again from the downstream reach's mu (two
+// loads) where a phi tape would cost a second S x n array, and mu - c3 mu[s+1] would cancel.  Tick indexing as in
+// rr_kernels_adjoint.hpp: reach at lag l runs forward sub-step ts at tick ts + l and reverse step r = S - 1 - ts at reverse tick
+// r + Dmax - l; a headwater has the lag its position in the tree gives it and takes no part in the reverse ticks.
+#pragma once
+
+namespace {
+
+struct UnitAdjTickArgs {
+    const int32_t *lag, *child_ptr, *down;
+    const double *w;           // [n] c1 of the downstream reach, stored at the upstream position
+    const double *c2, *c3;     // [n] engine order
+    const double *g;           // [T, n] engine order: masked dL/d(discharge) (NULL: none)
+    const double *gcf, *gff;   // [n] engine order: dL/d(q_ch final), dL/d(q_full final) at inner positions (NULL: none)
+    const double *ma, *mb;     // mu written one / two ticks ago
+    double *mc;                // this tick's mu
+    int64_t n;
+    int32_t p_lo, p_hi, dmax;
+    int64_t tau, total_substeps;
+    Div32 nsub;
+};
+
+// One reverse tick: mu of every active inner position (k_adj_tick with the two-state recurrence).
+template <bool SINGLE_SUBSTEP>
+__global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgs a)
+{
+    const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (p >= a.p_hi) return;
+    if (a.child_ptr[p] == a.child_ptr[p + 1]) return;             // headwater: no state
+    const int32_t lag = a.lag[p] & kLagMask;
+    const int64_t r = a.tau - (int64_t)(a.dmax - lag);
+    if (r < 0 || r >= a.total_substeps) return;
+    const uint32_t ts = (uint32_t)(a.total_substeps - 1 - r);
+    uint32_t t;
+    if (SINGLE_SUBSTEP) t = ts;
+    else { uint32_t rem; t = a.nsub.div(ts, rem); }
+
+    double m = a.g ? a.g[(int64_t)t * a.n + p] : 0.0;
+    if (r == 0) {
+        if (a.gff) m += a.gff[p];
+        if (a.gcf) m += a.gcf[p];
+    }
+    const int32_t d = a.down[p];
+    if (d >= 0) {
+        m = __builtin_fma(a.w[p], a.ma[d], m);
+        if (r > 0) m = __builtin_fma(a.c2[d], a.mb[d], m);
+    }
+    if (r > 0) m = __builtin_fma(a.c3[p], a.ma[p], m);
+    a.mc[p] = m;
+}
+
+// dL/d(discharge) in params order with the forward's output rule applied: an inner reach's row is max(mean, 0), a headwater's is
+// its lateral inflow as it is.  One column per lane, rows strided over blockIdx.y.
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
+                                                          const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= n) return;
+    const int32_t p = inv[i];
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const int64_t k = t * n + i;
+        const double g = grad_out[k];
+        dst[k] = hw ? g : (discharge[k] > 0.0 ? g * inv_nsub : 0.0);
+    }
+}
+
+// Inner-indexed vectors to engine positions: the tape's first rows (q_full0 where the reach below reads its "old" value), the
+// q_ch row k_tick_unit updates in place and a copy of q_ch0 that stays (the c3 gradient's first term); the final-state gradients.
+__global__ __launch_bounds__(kBlock) void k_adj_unit_in(double *qtape, double *qch, double *qch0, const double *q_full0, const double *q_ch0,
+                                                        double *gcf, double *gff, const double *grad_qch_final, const double *grad_qfull_final,
+                                                        const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner)
+{
+    const int32_t k = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (k >= n_inner) return;
+    const int32_t p = inner_pos[k];
+    if (q_full0) {
+        qtape[(int64_t)((lag[p] & kLagMask) + 1) * n + p] = q_full0[k];
+        const double v = q_ch0[k];
+        qch[p] = v; qch0[p] = v;
+    }
+    if (grad_qch_final) gcf[p] = grad_qch_final[k];
+    if (grad_qfull_final) gff[p] = grad_qfull_final[k];
+}
+
+struct UnitAdjReduceArgs {
+    const int32_t *lag, *child_ptr;
+    const uint16_t *hw_children;
+    const double *qtape;       // storage row tau + 2 = what every position published at forward tick tau
+    const double *mtape;       // row tau = mu written at reverse tick tau
+    const double *lat;         // [T, n] lateral rows in engine order
+    const double *qch0;        // [n] q_ch0 at inner positions
+    double *slab;              // [splits][3][n] partial sums
+    int64_t n, total_substeps, steps_per_split;
+    int32_t dmax;
+    Div32 nsub;
+};
+
+// Partial sums over one range of sub-steps per inner reach (blockIdx.y = range):
+//   sum_s mu[s,i] * {sum_H l + sum_U q_full[s,u],  sum_H l + sum_U q_full[s-1,u],  q_ch[s-1,i]}
+// with q_ch[s-1,i] = q_full[s-1,i] - l[t(s-1),i] from the tape (q_ch0 at s = 1).  Merged in order by k_adj_merge_unit.
+template <bool SINGLE_SUBSTEP>
+__global__ __launch_bounds__(kBlock) void k_adj_reduce_unit(const UnitAdjReduceArgs a)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= a.n) return;
+    const int32_t u0 = a.child_ptr[p], u1 = a.child_ptr[p + 1];
+    if (u0 == u1) return;                                         // headwater: k_adj_merge_unit writes its zeros
+    const int64_t n = a.n;
+    const int32_t lag = a.lag[p] & kLagMask;
+    const int32_t uh = u0 + (int32_t)a.hw_children[p];
+    const int64_t s0 = (int64_t)blockIdx.y * a.steps_per_split, s1 = min(a.total_substeps, s0 + a.steps_per_split);
+    double g1 = 0.0, g2 = 0.0, g3 = 0.0;
+    for (int64_t ts = s0; ts < s1; ++ts) {
+        const double *q1 = a.qtape + (ts + lag + 1) * n, *q2 = q1 - n;
+        const double mu = a.mtape[(a.total_substeps - 1 - ts + a.dmax - lag) * n + p];
+        double s_hw = 0.0, s_new = 0.0, s_old = 0.0;
+        for (int32_t u = u0; u < uh; ++u) s_hw += q1[u];
+        for (int32_t u = uh; u < u1; ++u) { s_new += q1[u]; s_old += q2[u]; }
+        double prev;
+        if (ts == 0) prev = a.qch0[p];
+        else {
+            uint32_t t;
+            if (SINGLE_SUBSTEP) t = (uint32_t)(ts - 1);
+            else { uint32_t rem; t = a.nsub.div((uint32_t)(ts - 1), rem); }
+            prev = q1[p] - a.lat[(int64_t)t * n + p];
+        }
+        g1 = __builtin_fma(mu, s_hw + s_new, g1);
+        g2 = __builtin_fma(mu, s_hw + s_old, g2);
+        g3 = __builtin_fma(mu, prev, g3);
+    }
+    double *out = a.slab + (int64_t)blockIdx.y * 3 * n + p;
+    out[0] = g1; out[n] = g2; out[2 * n] = g3;
+}
+
+// Merge of the ranges in order, scattered to params order; zeros on headwaters (their coefficients are never read).
+__global__ __launch_bounds__(kBlock) void k_adj_merge_unit(const double *slab, int64_t splits, const int32_t *child_ptr, const int32_t *perm,
+                                                           int64_t n, double *grad_coef)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int32_t i = perm[p];
+    double g[3] = {0.0, 0.0, 0.0};
+    if (child_ptr[p] != child_ptr[p + 1])
+        for (int64_t k = 0; k < splits; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[c] += slab[(k * 3 + c) * n + p];
+    grad_coef[i] = g[0]; grad_coef[n + i] = g[1]; grad_coef[2 * n + i] = g[2];
+}
+
+// dL/dq_ch0[i] = c3[i] mu[1,i], dL/dq_full0[i] = c2[d] mu[1,d], inner order.
+__global__ __launch_bounds__(kBlock) void k_adj_state_unit(double *grad_qch0, double *grad_qfull0, const double *mtape, const int32_t *inner_pos,
+                                                           const int32_t *lag, const int32_t *down, const double *c2, const double *c3, int64_t n,
+                                                           int32_t n_inner, int64_t total_substeps, int32_t dmax)
+{
+    const int32_t k = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
+    if (k >= n_inner) return;
+    const int32_t p = inner_pos[k];
+    const int64_t tau = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // reverse tick of s = 1
+    if (grad_qch0) grad_qch0[k] = c3[p] * mtape[tau * n + p];
+    if (grad_qfull0) {
+        const int32_t d = down[p];
+        grad_qfull0[k] = d >= 0 ? c2[d] * mtape[(tau - 1) * n + d] : 0.0;
+    }
+}
+
+// dL/dl[t, p] in engine order (g and dst may be the same rows: a lane reads its own element before it writes it):
+//   inner      sum over the row's sub-steps of phi[s,p] = g[t,p] + [s=S] gff[p] + c1[d] mu[s,d] + c2[d] mu[s+1,d]
+//   headwater  dL/dout[t,p] + (c1[d] + c2[d]) * sum over the row's sub-steps of mu[s,d]
+// The downstream reach ran sub-step ts one reverse tick before this position's slot for ts, and ts + 1 two ticks before.
+__global__ __launch_bounds__(kBlock) void k_adj_rows_unit(double *dst, const double *g, const double *gff, const double *mtape, const int32_t *lag,
+                                                          const int32_t *child_ptr, const int32_t *down, const double *w, const double *c2,
+                                                          int64_t n, int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    const int32_t d = down[p];
+    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
+    const double *md = mtape + (d >= 0 ? d : 0);
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const double gv = g ? g[t * n + p] : 0.0;
+        double v;
+        if (hw) {
+            double m = 0.0;
+            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
+            v = __builtin_fma(c1d + c2d, m, gv);
+        } else {
+            v = 0.0;
+            for (int64_t k = 0; k < nsub; ++k) {
+                const int64_t ts = t * nsub + k;
+                double phi = gv;
+                if (ts == total_substeps - 1 && gff) phi += gff[p];
+                if (d >= 0) {
+                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
+                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
+                }
+                v += phi;
+            }
+        }
+        dst[t * n + p] = v;
+    }
+}
+
+// ---- adjoint of the unit-hydrograph convolution (UnitHydrograph.py:93-107) ----
+// buf[t'] = sum_j kernel[j] depth[t' - j] + [t' < n_ks] state[t'] for t' < T + n_ks - 1; convolved = buf[:T], state_out[:n_ks-1] =
+// buf[T:], state_out[n_ks-1] = 0.  G[t'] = dL/dbuf[t']: dL/dconvolved[t'] below T, dL/dstate_out[t' - T] from T to T + n_ks - 2, else 0.
+struct UhGrad {
+    const double *gconv, *gstate;      // either may be NULL
+    int64_t T, n, top;                 // top = T + n_ks - 1
+    __device__ __forceinline__ double at(int64_t tp, int64_t i) const
+    {
+        if (tp < T) return gconv ? gconv[tp * n + i] : 0.0;
+        return (gstate && tp < top) ? gstate[(tp - T) * n + i] : 0.0;
+    }
+};
+
+// dL/ddepth[t, i] = sum_j kernel[j, i] G[t + j, i]: k_uh_convolve's sliding register window run the other way.  One reach per
+// lane, TB consecutive rows per thread.
+template <int TB>
+__global__ __launch_bounds__(kBlock) void k_uh_adjoint_depth(const double *__restrict__ kernel, const UhGrad G, double *__restrict__ grad_depth,
+                                                             int32_t n_ks)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= G.n) return;
+    const int64_t t0 = (int64_t)blockIdx.y * TB;
+    double acc[TB], win[TB];
+#pragma unroll
+    for (int j = 0; j < TB; ++j) { acc[j] = 0.0; win[j] = G.at(t0 + j, i); }
+    for (int32_t s = 0; s < n_ks; ++s) {
+        const double kv = kernel[(int64_t)s * G.n + i];
+#pragma unroll
+        for (int j = 0; j < TB; ++j) acc[j] = __builtin_fma(kv, win[j], acc[j]);
+#pragma unroll
+        for (int j = 0; j < TB - 1; ++j) win[j] = win[j + 1];
+        win[TB - 1] = G.at(t0 + TB + s, i);
+    }
+#pragma unroll
+    for (int j = 0; j < TB; ++j)
+        if (t0 + j < G.T) grad_depth[(t0 + j) * G.n + i] = acc[j];
+}
+
+// Partial dL/dkernel[j, i] = sum_t depth[t, i] G[t + j, i] over one range of rows (blockIdx.y) for JB taps (blockIdx.z): the G
+// window of the tap block slides in registers, one new value and one depth value per row.  slab[split][j][i]; with one range the
+// slab is the result itself.
+template <int JB>
+__global__ __launch_bounds__(kBlock) void k_uh_adjoint_kernel(const double *__restrict__ depth, const UhGrad G, double *__restrict__ slab,
+                                                              int32_t n_ks, int64_t rows_per_split)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i >= G.n) return;
+    const int64_t t0 = (int64_t)blockIdx.y * rows_per_split, t1 = min(G.T, t0 + rows_per_split);
+    const int32_t j0 = (int32_t)blockIdx.z * JB;
+    double acc[JB], win[JB];
+#pragma unroll
+    for (int j = 0; j < JB; ++j) { acc[j] = 0.0; win[j] = G.at(t0 + j0 + j, i); }
+    for (int64_t t = t0; t < t1; ++t) {
+        const double dv = depth[t * G.n + i];
+#pragma unroll
+        for (int j = 0; j < JB; ++j) acc[j] = __builtin_fma(dv, win[j], acc[j]);
+#pragma unroll
+        for (int j = 0; j < JB - 1; ++j) win[j] = win[j + 1];
+        win[JB - 1] = G.at(t + 1 + j0 + JB - 1, i);
+    }
+    double *out = slab + ((int64_t)blockIdx.y * n_ks + j0) * G.n + i;
+#pragma unroll
+    for (int j = 0; j < JB; ++j)
+        if (j0 + j < n_ks) out[(int64_t)j * G.n] = acc[j];
+}
+
+// The row ranges merged in order.
+__global__ __launch_bounds__(kBlock) void k_uh_adjoint_merge(const double *slab, int64_t splits, int64_t count, double *grad_kernel)
+{
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (int64_t)gridDim.x * kBlock) {
+        double v = 0.0;
+        for (int64_t s = 0; s < splits; ++s) v += slab[s * count + k];
+        grad_kernel[k] = v;
+    }
+}
+
+// dL/dstate[t', i] = G[t', i] for t' < n_ks.
+__global__ __launch_bounds__(kBlock) void k_uh_adjoint_state(const UhGrad G, double *grad_state, int64_t n_ks)
+{
+    for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < n_ks * G.n; k += (int64_t)gridDim.x * kBlock)
+        grad_state[k] = G.at(k / G.n, k % G.n);
+}
+
+}  // namespace

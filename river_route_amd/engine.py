@@ -11,7 +11,7 @@ import numpy as np
 from . import _lib
 from ._lib import RRError, check, ptr
 
-__all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
+__all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'uh_adjoint_work_bytes', 'uh_adjoint_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
            'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
            'metrics_update_dev', 'metrics_finish_dev', 'grid_overlap_area', 'grid_overlap_area_dev']
 
@@ -242,6 +242,22 @@ class Plan:
                                               ptr(grad_qfinal), ptr(grad_lateral), ptr(grad_q0), ptr(grad_coef), ptr(work),
                                               int(work_bytes), int(T), int(num_substeps), stream))
 
+    # -- adjoint of unit_route_dev (rr.grad) --
+    def unit_adjoint_work_bytes(self, T: int, num_substeps: int = 1) -> int:
+        """rr_unit_adjoint_work_bytes: bytes of work memory unit_adjoint_dev needs for T rows x num_substeps sub-steps (readies
+        the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_unit_adjoint_work_bytes(self._h, int(T), int(num_substeps), C.byref(out)))
+        return int(out.value)
+
+    def unit_adjoint_dev(self, q_ch0, q_full0, lateral, lat_rows, discharge, grad_out, grad_qch_final, grad_qfull_final, grad_lateral,
+                         grad_qch0, grad_qfull0, grad_coef, work, work_bytes, T, num_substeps, stream=None) -> None:
+        """rr_unit_adjoint_dev (enqueue only): gradients through one unit_route_dev call with the coefficients last set; any of the
+        three incoming gradients and the four outputs may be None."""
+        check(_lib.lib().rr_unit_adjoint_dev(self._h, ptr(q_ch0), ptr(q_full0), ptr(lateral), int(lat_rows), ptr(discharge), ptr(grad_out),
+                                             ptr(grad_qch_final), ptr(grad_qfull_final), ptr(grad_lateral), ptr(grad_qch0), ptr(grad_qfull0),
+                                             ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps), stream))
+
     def muskingum_route_dev(self, q_t, discharge, out_rows, num_output_steps, num_routing_per_output,
                             stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output)
@@ -435,6 +451,21 @@ def uh_convolve(kernel, state, lateral, device: int = 0) -> np.ndarray:
 def uh_convolve_dev(kernel, state, lateral, out, T, n_ks, n, device: int = 0, stream=None) -> None:
     check(_lib.lib().rr_uh_convolve_dev(int(device), ptr(kernel), ptr(state), ptr(lateral), ptr(out), int(T),
                                         int(n_ks), int(n), stream))
+
+
+def uh_adjoint_work_bytes(T, n_ks, n) -> int:
+    """rr_uh_adjoint_work_bytes: bytes of work memory uh_adjoint_dev needs for its kernel gradient (0: none)."""
+    out = C.c_int64(0)
+    check(_lib.lib().rr_uh_adjoint_work_bytes(int(T), int(n_ks), int(n), C.byref(out)))
+    return int(out.value)
+
+
+def uh_adjoint_dev(kernel, depth, grad_convolved, grad_state_out, grad_depth, grad_kernel, grad_state, work, work_bytes, T, n_ks, n,
+                   device: int = 0, stream=None) -> None:
+    """rr_uh_adjoint_dev (enqueue only): gradients through one uh_convolve_dev call; either incoming gradient and any output may be
+    None."""
+    check(_lib.lib().rr_uh_adjoint_dev(int(device), ptr(kernel), ptr(depth), ptr(grad_convolved), ptr(grad_state_out), ptr(grad_depth),
+                                       ptr(grad_kernel), ptr(grad_state), ptr(work), int(work_bytes), int(T), int(n_ks), int(n), stream))
 
 
 RUNOFF_CUMULATIVE, RUNOFF_FORCE_POSITIVE, RUNOFF_KEEP_NAN = 1, 2, 4

@@ -1,5 +1,5 @@
 """
-Differentiable RapidMuskingum routing: torch autograd through the HIP engine.
+Differentiable routing: torch autograd through the HIP engine.
 
     import river_route_amd as rr
     k = torch.tensor(k0, dtype=torch.float64, requires_grad=True)
@@ -12,16 +12,25 @@ Plan.rapid_route computes, bit for bit.  The backward is rr_rapid_adjoint_dev: i
 runs the adjoint recurrence from the outlets upward and backward in time, then reduces the coefficient gradients per reach.
 Torch chains from the coefficients to k and x (muskingum_coefficients), so any loss written in torch can sit on top.
 
-RapidMuskingum only, float64 rows, one plan on one GPU: UnitMuskingum, float32 rows, ensembles and partitioned plans are refused.
+UnitMuskingum has the same three layers: uh_convolve (UnitHydrograph.convolve; gradients to the kernel columns, the carried state
+and the runoff depths), unit_route (unit_route on a convolved lateral; gradients to q_ch0, q_full0, the lateral rows, k and x) and
+unit_muskingum, the two chained as the router chains them, in windows if asked:
+
+    Q, q_ch, q_full, uh_state = rr.grad.unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state0, k, x, 900.0, 3600.0)
+
+Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, ensembles, partitioned plans and plans
+with set_unit_weights edge data are refused.
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
+from . import engine
 from .engine import Plan
 
-__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route']
+__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
+           'unit_muskingum']
 
 
 def muskingum_coefficients(k, x, dt_routing):
@@ -171,3 +180,203 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
         d, q = RapidRoute.apply(plan, nsub, t1 - t0, q, ql, c1, c2, c3, c4dt)
         parts.append(d)
     return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q
+
+
+# ---- UnitMuskingum ----
+
+class UhConvolve(torch.autograd.Function):
+    """(convolved[T, n], state_out[n_ks, n]) = UnitHydrograph.convolve of depth[T, n] with kernel[n_ks, n] from the carried state.
+    Forward: rr_uh_convolve_dev on a copy of the state; backward: rr_uh_adjoint_dev."""
+
+    @staticmethod
+    def forward(ctx, kernel, state, depth):
+        dev = depth.device.index
+        n_ks, n = kernel.shape
+        T = int(depth.shape[0])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        state_out = state.detach().clone()
+        convolved = torch.empty((T, n), dtype=torch.float64, device=depth.device)
+        engine.uh_convolve_dev(kernel.detach(), state_out, depth.detach(), convolved, T, n_ks, n, dev, stream)
+        ctx.save_for_backward(kernel, depth)
+        ctx.set_materialize_grads(False)
+        return convolved, state_out
+
+    @staticmethod
+    def backward(ctx, grad_convolved, grad_state_out):
+        kernel, depth = ctx.saved_tensors
+        need = ctx.needs_input_grad      # kernel, state, depth
+        if (grad_convolved is None and grad_state_out is None) or not any(need):
+            return None, None, None
+        dev = depth.device.index
+        n_ks, n = kernel.shape
+        T = int(depth.shape[0])
+        f64 = dict(dtype=torch.float64, device=depth.device)
+        g_c = None if grad_convolved is None else grad_convolved.to(**f64).contiguous()
+        g_s = None if grad_state_out is None else grad_state_out.to(**f64).contiguous()
+        g_kernel = torch.empty((n_ks, n), **f64) if need[0] else None
+        g_state = torch.empty((n_ks, n), **f64) if need[1] else None
+        g_depth = torch.empty((T, n), **f64) if need[2] else None
+        nbytes = engine.uh_adjoint_work_bytes(T, n_ks, n) if need[0] else 0
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=depth.device)
+        engine.uh_adjoint_dev(kernel.detach(), depth.detach(), g_c, g_s, g_depth, g_kernel, g_state, work, nbytes, T, n_ks, n, dev,
+                              torch.cuda.current_stream(dev).cuda_stream)
+        return g_kernel, g_state, g_depth
+
+
+class UnitRoute(torch.autograd.Function):
+    """(discharge[T, n], q_ch[n_inner], q_full[n_inner]) = UnitMuskingum routing of T rows of convolved lateral inflow from q_ch0,
+    q_full0 with nsub sub-steps per row and per-reach coefficients c1, c2, c3.  Forward: rr_unit_route_dev; backward:
+    rr_unit_adjoint_dev, which rebuilds the state tape, so only references to the inputs and the discharge are kept between the two."""
+
+    @staticmethod
+    def forward(ctx, plan, nsub, q_ch0, q_full0, lateral, c1, c2, c3):
+        dev = plan.device
+        T = int(lateral.shape[0])
+        _set_coeffs(plan, c1, c2, c3, None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        q_ch, q_full = q_ch0.detach().clone(), q_full0.detach().clone()
+        discharge = torch.empty((T, plan.n), dtype=torch.float64, device=lateral.device)
+        plan.unit_route_dev(q_ch, q_full, lateral.detach(), T, discharge, T, T, nsub, stream)
+        ctx.plan, ctx.nsub = plan, int(nsub)
+        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach())
+        ctx.save_for_backward(q_ch0, q_full0, lateral, discharge)
+        ctx.set_materialize_grads(False)
+        return discharge, q_ch, q_full
+
+    @staticmethod
+    def backward(ctx, grad_discharge, grad_qch, grad_qfull):
+        plan, nsub = ctx.plan, ctx.nsub
+        q_ch0, q_full0, lateral, discharge = ctx.saved_tensors
+        T = int(lateral.shape[0])
+        need = ctx.needs_input_grad      # plan, nsub, q_ch0, q_full0, lateral, c1, c2, c3
+        want_coef = any(need[5:8])
+        none = (None,) * 8
+        if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[2:5]) or want_coef):
+            return none
+        dev = plan.device
+        c1, c2, c3 = ctx.coeffs
+        _set_coeffs(plan, c1, c2, c3, None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        f64 = dict(dtype=torch.float64, device=lateral.device)
+        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
+        g_qch0 = torch.empty(plan.n_inner, **f64) if need[2] else None
+        g_qfull0 = torch.empty(plan.n_inner, **f64) if need[3] else None
+        g_lat = torch.empty((T, plan.n), **f64) if need[4] else None
+        g_coef = torch.empty((3, plan.n), **f64) if want_coef else None
+        nbytes = plan.unit_adjoint_work_bytes(T, nsub)
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=lateral.device)       # torch's allocator owns the tapes
+        plan.unit_adjoint_dev(q_ch0.detach(), q_full0.detach(), lateral.detach(), T, discharge, g_out, g_c, g_f, g_lat, g_qch0, g_qfull0,
+                              g_coef, work, nbytes, T, nsub, stream)
+        coef = [None] * 3
+        if g_coef is not None:
+            for j, c in enumerate((c1, c2, c3)):
+                if need[5 + j]:
+                    coef[j] = g_coef[j].to(c.device)
+        return (None, None, g_qch0, g_qfull0, g_lat, *coef)
+
+
+def _check_rows(t, name, n):
+    if not isinstance(t, torch.Tensor) or t.ndim != 2:
+        raise ValueError(f'{name} must be a 2-D (T, n) tensor (ensembles have no adjoint: route members one by one)')
+    T = int(t.shape[0])
+    if T < 1:
+        raise ValueError(f'{name} has no rows')
+    _check_tensor(t, name, (T, n))
+    return T
+
+
+def _check_cuda(pairs, device):
+    for t, name in pairs:
+        if t.device.type != 'cuda' or t.device.index != device:
+            raise ValueError(f'{name} must be on cuda:{device} (it is on {t.device})')
+
+
+def _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window):
+    """The checks unit_route and unit_muskingum share; returns nsub."""
+    if not isinstance(plan, Plan):
+        raise TypeError('plan must be a river_route_amd.engine.Plan (one GPU; partitioned plans have no adjoint)')
+    if not (float(dt_routing) > 0 and float(dt_runoff) > 0):
+        raise ValueError('dt_routing and dt_runoff must be positive')
+    nsub = int(round(float(dt_runoff) / float(dt_routing)))
+    if nsub < 1 or nsub * float(dt_routing) != float(dt_runoff):
+        raise ValueError(f'dt_runoff ({dt_runoff}) must be a whole number of routing steps ({dt_routing})')
+    _check_tensor(q_ch0, 'q_ch0', (plan.n_inner,))
+    _check_tensor(q_full0, 'q_full0', (plan.n_inner,))
+    for t, name in ((k, 'k'), (x, 'x')):
+        _check_tensor(t, name, (plan.n,))
+    if rows_per_window is not None and int(rows_per_window) < 1:
+        raise ValueError('rows_per_window must be >= 1')
+    return nsub
+
+
+def _check_unit_device(plan, tensors):
+    if plan.device < 0:
+        raise ValueError('plan is host-only (RR_DEVICE_NONE): the adjoint runs on the GPU only')
+    _check_cuda(tensors, plan.device)
+
+
+def uh_convolve(kernel, state, depth):
+    """Differentiable UnitHydrograph.convolve (river_route/uhkernels/UnitHydrograph.py:77-107): (convolved[T, n], state_out[n_ks, n])
+    from kernel[n_ks, n], the carried state[n_ks, n] and depth[T, n], float64 tensors on one GPU.  The inputs are not modified;
+    convolved is the array engine.uh_convolve_dev computes, bit for bit.  Gradients reach kernel, state and depth."""
+    if not isinstance(kernel, torch.Tensor) or kernel.ndim != 2:
+        raise ValueError('kernel must be a 2-D (n_ks, n) tensor')
+    n_ks, n = (int(v) for v in kernel.shape)
+    if n_ks < 1:
+        raise ValueError('kernel has no steps')
+    _check_tensor(kernel, 'kernel', (n_ks, n))
+    _check_tensor(state, 'state', (n_ks, n))
+    _check_rows(depth, 'depth', n)
+    if depth.device.type != 'cuda':
+        raise ValueError(f'depth must be on a GPU (it is on {depth.device})')
+    _check_cuda(((kernel, 'kernel'), (state, 'state')), depth.device.index)
+    return UhConvolve.apply(kernel, state, depth)
+
+
+def _coefficients_and_window(k, x, dt_routing, T, rows_per_window):
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    return c1, c2, c3, (T if rows_per_window is None else min(T, int(rows_per_window)))
+
+
+def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None):
+    """Differentiable unit_route (river_route/routers/_numba_kernels.py:88-171) on an already convolved lateral:
+    (discharge[T, n], q_ch[n_inner], q_full[n_inner]) as torch tensors on the plan's device.
+
+    q_ch0 and q_full0 (one value per reach with upstream reaches, ascending params order) and lateral[T, n] are float64 tensors on
+    the plan's GPU; k and x are float64 tensors of n values on any device.  c1, c2, c3 come from muskingum_coefficients(k, x,
+    dt_routing) and go onto the plan without c4; the forward is Plan.unit_route_dev, bit for bit.  Gradients reach q_ch0, q_full0,
+    lateral, k and x (a headwater's k and x get 0: its coefficients are never read).  rows_per_window routes the series in windows
+    chained through the states, so the tape memory of the backward pass is one window's.  Every argument is checked before the GPU
+    is touched."""
+    nsub = _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window)
+    T = _check_rows(lateral, 'lateral', plan.n)
+    _check_unit_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
+    c1, c2, c3, R = _coefficients_and_window(k, x, dt_routing, T, rows_per_window)
+    q_ch, q_full, parts = q_ch0, q_full0, []
+    for t0 in range(0, T, R):
+        d, q_ch, q_full = UnitRoute.apply(plan, nsub, q_ch, q_full, lateral[t0:min(T, t0 + R)], c1, c2, c3)
+        parts.append(d)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q_ch, q_full
+
+
+def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None):
+    """Differentiable UnitMuskingum (the router's _router, river_route/routers/UnitMuskingum.py:72-98): the runoff depths are
+    convolved with the unit-hydrograph kernel (uh_convolve) and the result is routed (unit_route).  Returns (discharge[T, n],
+    q_ch[n_inner], q_full[n_inner], uh_state_out[n_ks, n]); gradients reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x.
+    With rows_per_window each window convolves its own rows and hands q_ch, q_full and the convolution's state to the next, as the
+    router does from file to file."""
+    nsub = _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window)
+    T = _check_rows(depth, 'depth', plan.n)
+    if not isinstance(uh_kernel, torch.Tensor) or uh_kernel.ndim != 2 or int(uh_kernel.shape[0]) < 1:
+        raise ValueError('uh_kernel must be a 2-D (n_ks, n) tensor')
+    n_ks = int(uh_kernel.shape[0])
+    _check_tensor(uh_kernel, 'uh_kernel', (n_ks, plan.n))
+    _check_tensor(uh_state, 'uh_state', (n_ks, plan.n))
+    _check_unit_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
+    c1, c2, c3, R = _coefficients_and_window(k, x, dt_routing, T, rows_per_window)
+    q_ch, q_full, state, parts = q_ch0, q_full0, uh_state, []
+    for t0 in range(0, T, R):
+        lateral, state = UhConvolve.apply(uh_kernel, state, depth[t0:min(T, t0 + R)])
+        d, q_ch, q_full = UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3)
+        parts.append(d)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q_ch, q_full, state
