@@ -1,0 +1,334 @@
+// rr_adjoint.hpp -- the host side of the routing adjoints (rr_rapid_adjoint_*, rr_unit_adjoint_*): one driver
+// (refusals, work-memory layout, forward replay, reverse sweep) and, per router, the kernels plugged into it and a few checks of its own.
+// Part of the one translation unit rr_engine.hip builds (included from there, after rr_exec.hpp; not a stand-alone header).
+#pragma once
+
+namespace {
+
+constexpr int64_t kAdjPermRows = 16;          // rows per pass of the tiled permutation
+constexpr int64_t kAdjTargetBlocks = 2048;    // blocks of a split reduction: column blocks x sub-step ranges
+
+// What differs between the two routers outside the kernels: the name of the sizing entry point (the errors name it) and two row counts
+// of the work memory: sums per reach in the reduction (c1..c4 / c1..c3) and scratch rows (the tick's running sum and its discarded
+// discharge row; Unit adds q_ch, updated in place, q_ch0, dL/d(q_ch final) and dL/d(q_full final) in engine order).
+struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; };
+constexpr AdjointKind kRapidAdjoint{"rr_rapid_adjoint_work_bytes", 4, 2};
+constexpr AdjointKind kUnitAdjoint{"rr_unit_adjoint_work_bytes", 3, 6};
+
+// The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
+// (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
+// order), lateral rows and gradient rows in engine order (T rows each), the permutation's intermediate rows, the reduction slab
+// (slab_rows x n per sub-step range), the scratch rows.
+struct AdjointLayout {
+    int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
+    int64_t chunk, splits, steps_per_split;
+};
+
+AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, const AdjointKind &K)
+{
+    AdjointLayout L{};
+    const int64_t S = T * nsub;
+    L.chunk = std::min<int64_t>(T, kAdjPermRows);
+    const int64_t col_blocks = (n + kBlock - 1) / kBlock;
+    const int64_t want = std::max<int64_t>(1, (kAdjTargetBlocks + col_blocks - 1) / col_blocks);
+    L.splits = std::max<int64_t>(1, std::min(want, S));
+    L.steps_per_split = (S + L.splits - 1) / L.splits;
+    L.splits = (S + L.steps_per_split - 1) / L.steps_per_split;
+    L.qtape = 0;
+    L.mtape = L.qtape + (S + depth + 1) * n;
+    L.lat = L.mtape + (S + depth - 1) * n;
+    L.grad = L.lat + T * n;
+    L.mrows = L.grad + T * n;
+    L.slab = L.mrows + L.chunk * n;
+    L.scratch = L.slab + L.splits * K.slab_rows * n;
+    L.total = L.scratch + K.scratch_rows * n;
+    return L;
+}
+
+// Plan data the adjoint reads besides the streaming layout: the tiled permutation tables and the downstream position of each position.
+int adjoint_ready(rr_plan *P)
+{
+    if (!P->perm_ready) {
+        int rc = upload_tiled_permutations(P);
+        if (rc) return rc;
+    }
+    if (!P->d_adj_down) {
+        const rr::HostPlan &H = P->h;
+        std::vector<int32_t> down(H.n, -1);
+        for (int64_t p = 0; p < H.n; ++p)
+            for (int32_t u = H.child_ptr[p]; u < H.child_ptr[p + 1]; ++u) down[u] = (int32_t)p;
+        int32_t *d = nullptr;
+        int rc = dev_alloc(&d, H.n);
+        if (!rc) rc = dev_upload(d, down);
+        if (rc) { if (d) (void)hipFree(d); return rc; }
+        P->d_adj_down = d;
+    }
+    return RR_OK;
+}
+
+// One adjoint call: the arguments every *_adjoint_dev entry point has, and, once adjoint_check has passed, the sizes and the tapes.
+struct AdjointCall {
+    rr_plan *P;
+    const double *lateral; int64_t lat_rows;
+    const double *discharge, *grad_out;
+    void *work; int64_t work_bytes;
+    int64_t T, nsub;
+    hipStream_t st;
+    // set by adjoint_check
+    int64_t n, S, dmax, ticks;
+    bool one;                                                       // nsub == 1: the kernels' SINGLE_SUBSTEP forms
+    AdjointLayout L;
+    double *qtape, *mtape, *elat, *egrad, *mrows, *slab, *scratch;
+
+    void rows_between(int which, const double *src, double *dst) const      // T rows, params <-> engine order
+    {
+        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
+            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
+                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
+    }
+    const double *egrad_out() const { return grad_out ? egrad : nullptr; }      // masked dL/d(discharge) in engine order
+    dim3 reduce_grid() const { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits); }
+};
+
+// A check that is an entry point's own: after which shared ones it is tested (the plan's boundary check, the sizes, the lateral rows,
+// grad_out), whether it is hit, its status and text.  kAdjNothing is no refusal: no gradient is asked for, the call returns RR_OK.
+enum class AdjOwn { Plan, Wanted, Lateral, GradOut };
+constexpr int kAdjNothing = 1;
+struct OwnCheck { AdjOwn at; bool hit; int code; const char *what; };
+
+// The refusals of the four entry points, in the order they are tested; `who` names the entry point in the errors.  With `bytes`, a
+// sizing call (reads c.P, c.T, c.nsub; uploads the plan's tables); without, a *_dev call, whose context is filled in at the end.
+int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t *bytes, std::initializer_list<OwnCheck> own_checks)
+{
+    const auto no = [who](int code, const char *what) { return code > 0 ? code : fail(code, std::string(who) + what); };
+    const auto own = [&](AdjOwn at) {
+        for (const OwnCheck &o : own_checks)
+            if (o.at == at && o.hit) return no(o.code, o.what);
+        return RR_OK;
+    };
+    rr_plan *P = c.P;
+    const bool sizing = bytes != nullptr;
+    if (!P) return no(RR_E_INVALID, sizing ? ": null argument" : ": null plan");
+    if (sizing) *bytes = 0;
+    if (P->device < 0) return no(RR_E_UNSUPPORTED, ": host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
+    if (!sizing) {
+        HIPCHK(hipSetDevice(P->device));
+        if (P->n_ghost > 0 || P->n_export > 0)
+            return no(RR_E_UNSUPPORTED, ": the plan has boundary reaches (rr_plan_set_boundary): partitioned networks have no adjoint");
+        if (int rc = own(AdjOwn::Plan)) return rc;
+        if (!P->coeffs_set) return no(RR_E_STATE, " called before rr_plan_set_coeffs");
+        if (!P->weights_uniform)
+            return no(RR_E_UNSUPPORTED, ": per-edge weights (lhs_off_data not -c1 of the downstream reach): the adjoint needs one c1 per reach");
+        if (P->ses.open) return no(RR_E_STATE, ": a routing call is open");
+    }
+    const rr::HostPlan &H = P->h;
+    const int64_t n = H.n, T = c.T, nsub = c.nsub;
+    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return no(RR_E_INVALID, ": need T >= 1 and sub-steps >= 1");
+    if (T * nsub + H.depth > 0x7FFFFFFFLL) return no(RR_E_INVALID, ": too many sub-steps for one call: split the series into windows");
+    if (sizing) {
+        HIPCHK(hipSetDevice(P->device));
+        if (n == 0) return RR_OK;
+        if (int rc = adjoint_ready(P)) return rc;
+        *bytes = adjoint_layout(n, H.depth, T, nsub, K).total * (int64_t)sizeof(double);
+        return RR_OK;
+    }
+    if (int rc = own(AdjOwn::Wanted)) return rc;
+    if (c.lateral && c.lat_rows < T) return no(RR_E_INVALID, ": fewer lateral rows than T");
+    if (int rc = own(AdjOwn::Lateral)) return rc;
+    if (c.grad_out && !c.discharge) return no(RR_E_INVALID, ": grad_out needs the discharge of the forward call (its clamp mask)");
+    if (int rc = own(AdjOwn::GradOut)) return rc;
+    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K);
+    const int64_t need = L.total * (int64_t)sizeof(double);
+    if (!c.work || c.work_bytes < need)
+        return fail(RR_E_INVALID, std::string(who) + ": work memory smaller than " + K.sizer + " (" + std::to_string(need) + " bytes)");
+    if (!P->perm_ready || !P->d_adj_down)
+        return fail(RR_E_STATE, std::string(who) + ": call " + K.sizer + " first (it uploads the plan's permutation tables once)");
+
+    c.n = n; c.S = T * nsub; c.dmax = H.depth - 1; c.ticks = c.S + c.dmax; c.one = nsub == 1; c.L = L;
+    double *const base = static_cast<double *>(c.work);
+    c.qtape = base + L.qtape; c.mtape = base + L.mtape; c.elat = base + L.lat; c.egrad = base + L.grad; c.mrows = base + L.mrows;
+    c.slab = base + L.slab; c.scratch = base + L.scratch;
+    return RR_OK;
+}
+
+int adjoint_work_bytes(const AdjointKind &K, rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, std::string(K.sizer) + ": null argument");
+    AdjointCall c{};
+    c.P = P; c.T = T; c.nsub = nsub;
+    return adjoint_check(K.sizer, K, c, bytes, {});
+}
+
+// The forward again, into a tick-indexed tape: the tick kernel as the route calls run it, with its three rotating rows spread over the
+// q tape.  Fills `a` (the TickArgs of the call, or the one inside a UnitTickArgs) and calls launch(grid) for every tick with work.
+template <class Launch>
+void adjoint_replay(const AdjointCall &c, TickArgs &a, Launch launch)
+{
+    const rr_plan *P = c.P;
+    const int64_t n = c.n;
+    a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c1row = P->d_c1row_h; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
+    a.isum = c.scratch; a.bidx = P->d_bidx; a.ghost = nullptr; a.exports = nullptr; a.n_ghost = 0; a.n_export = 0;
+    a.in = c.lateral ? c.elat : nullptr; a.in_ld = n; a.in_rows = Div32((uint32_t)c.T);
+    a.out = c.scratch + n; a.out_ld = 0; a.out_rows = Div32(1u);      // discharge rows are not kept: every row lands on one scratch row
+    a.total_substeps = c.S; a.nsub = Div32((uint32_t)c.nsub); a.inv_nsub = 1.0 / (double)c.nsub;
+    for (int64_t tau = 0; tau < c.ticks; ++tau) {
+        int64_t p_lo, p_hi;
+        if (!tick_window(P->h, tau, c.S, p_lo, p_hi)) continue;
+        a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+        a.xc = c.qtape + (tau + 2) * n; a.xa = a.xc - n; a.xb = a.xc - 2 * n;
+        launch(grid1(p_hi - p_lo));
+    }
+}
+
+// The reverse ticks: the reach at lag l runs reverse step tau - (Dmax - l), so the window of active lags is the forward's mirrored.
+// Fills the fields AdjTickArgs and UnitAdjTickArgs share and calls launch(grid) for every tick with work.
+template <class Args, class Launch>
+void adjoint_reverse(const AdjointCall &c, Args &a, Launch launch)
+{
+    const rr_plan *P = c.P;
+    const rr::HostPlan &H = P->h;
+    const int64_t n = c.n, S = c.S, dmax = c.dmax;
+    a.lag = P->d_lag; a.down = P->d_adj_down; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3; a.g = c.egrad_out();
+    a.n = n; a.dmax = (int32_t)dmax; a.total_substeps = S; a.nsub = Div32((uint32_t)c.nsub);
+    for (int64_t tau = 0; tau < c.ticks; ++tau) {
+        const int64_t lag_lo = std::max<int64_t>(0, dmax - tau), lag_hi = std::min<int64_t>(dmax, dmax - tau + S - 1);
+        const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
+        if (p_hi <= p_lo) continue;
+        a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
+        a.mc = c.mtape + tau * n;
+        a.ma = tau >= 1 ? a.mc - n : a.mc;      // never read at tick 0 (nothing runs r > 0 or has a downstream reach there)
+        a.mb = tau >= 2 ? a.mc - 2 * n : a.mc;  // read from tick 2 on only
+        launch(grid1(p_hi - p_lo));
+    }
+}
+
+// The fields AdjReduceArgs and UnitAdjReduceArgs share; the reduction runs on c.reduce_grid().
+template <class Args>
+void adjoint_reduce_args(const AdjointCall &c, Args &r)
+{
+    const rr_plan *P = c.P;
+    r.lag = P->d_lag; r.child_ptr = P->d_child_ptr; r.qtape = c.qtape; r.mtape = c.mtape; r.lat = c.lateral ? c.elat : nullptr; r.slab = c.slab;
+    r.n = c.n; r.total_substeps = c.S; r.steps_per_split = c.L.steps_per_split; r.dmax = (int32_t)c.dmax; r.nsub = Div32((uint32_t)c.nsub);
+}
+
+// ---- RapidMuskingum ----
+
+int rapid_adjoint(const char *who, AdjointCall &c, const double *q0, const double *grad_qfinal, double *grad_lateral, double *grad_q0,
+                  double *grad_coef)
+{
+    rr_plan *const P = c.P;
+    const double *const lateral = c.lateral, *const discharge = c.discharge, *const grad_out = c.grad_out;
+    const int64_t T = c.T, nsub = c.nsub;
+    const hipStream_t st = c.st;
+    const int rc = adjoint_check(who, kRapidAdjoint, c, nullptr, {
+        {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_q0 && !grad_coef)), kAdjNothing, ""},
+        {AdjOwn::Wanted, grad_coef && !q0, RR_E_INVALID, ": the coefficient gradients need q0"},
+        {AdjOwn::Lateral, P && lateral && !P->has_c4, RR_E_STATE, ": lateral rows but no c4_dt (rr_plan_set_coeffs got NULL)"},
+        {AdjOwn::GradOut, grad_lateral && !lateral, RR_E_INVALID, ": grad_lateral of a channel-only call (lateral is NULL)"}});
+    if (rc) return rc == kAdjNothing ? RR_OK : rc;
+
+    const int64_t n = c.n, S = c.S;
+    // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        const int64_t count = T * n;
+        hipLaunchKernelGGL(k_adj_mask, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st, c.mtape, grad_out,
+                           discharge, count, 1.0 / (double)nsub);
+        c.rows_between(0, c.mtape, c.egrad);
+    }
+    if (grad_coef) {
+        if (lateral) c.rows_between(0, lateral, c.elat);
+        hipLaunchKernelGGL(k_adj_tape_init, grid1(n), dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
+        TickArgs a{};
+        const auto tick = lateral ? (c.one ? k_tick<true, true> : k_tick<true, false>) : (c.one ? k_tick<false, true> : k_tick<false, false>);
+        adjoint_replay(c, a, [&](dim3 g) { hipLaunchKernelGGL(tick, g, dim3(kBlock), 0, st, a); });
+    }
+    AdjTickArgs ra{};
+    ra.gf = grad_qfinal; ra.perm = P->d_perm;
+    adjoint_reverse(c, ra, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_adj_tick<true> : k_adj_tick<false>), g, dim3(kBlock), 0, st, ra); });
+    if (grad_coef) {
+        AdjReduceArgs r{};
+        adjoint_reduce_args(c, r);
+        hipLaunchKernelGGL((c.one ? k_adj_reduce<true> : k_adj_reduce<false>), c.reduce_grid(), dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef || grad_q0)
+        hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, c.L.splits, (const double *)c.mtape,
+                           (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, S, (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0);
+    if (grad_lateral) {
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535));
+        hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
+                           T, nsub, S, (int32_t)c.dmax);
+        c.rows_between(1, c.egrad, grad_lateral);
+    }
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+// ---- UnitMuskingum ----
+
+int unit_adjoint(const char *who, AdjointCall &c, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
+                 const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef)
+{
+    rr_plan *const P = c.P;
+    const double *const lateral = c.lateral, *const discharge = c.discharge, *const grad_out = c.grad_out;
+    const int64_t T = c.T, nsub = c.nsub;
+    const hipStream_t st = c.st;
+    const int64_t ni = P ? (int64_t)P->h.inner_pos.size() : 0;
+    if (ni == 0) { grad_qch0 = nullptr; grad_qfull0 = nullptr; }      // no inner reach: the state vectors are empty
+    const int rc = adjoint_check(who, kUnitAdjoint, c, nullptr, {
+        {AdjOwn::Plan, P && P->unit_general, RR_E_UNSUPPORTED,
+         ": general edge data (rr_plan_set_unit_weights): the adjoint is that of the reference callers' unit weights"},
+        {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_qch0 && !grad_qfull0 && !grad_coef)), kAdjNothing, ""},
+        {AdjOwn::Wanted, grad_coef && ni > 0 && (!q_ch0 || !q_full0 || !lateral), RR_E_INVALID,
+         ": the coefficient gradients need q_ch0, q_full0 and the lateral rows"}});
+    if (rc) return rc == kAdjNothing ? RR_OK : rc;
+
+    const int64_t n = c.n, S = c.S;
+    double *const qch = c.scratch + 2 * n, *const qch0e = qch + n, *const gcf = qch0e + n, *const gff = gcf + n;
+    const bool tape = grad_coef && ni > 0;
+    const unsigned row_blocks = (unsigned)std::min<int64_t>(T, 65535);
+    // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        hipLaunchKernelGGL(k_adj_mask_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
+                           (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
+        c.rows_between(0, c.mtape, c.egrad);
+    }
+    if (ni > 0 && (tape || grad_qch_final || grad_qfull_final))
+        hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff, grad_qch_final,
+                           grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
+    if (tape) {      // k_tick_unit on its one-weight branch
+        c.rows_between(0, lateral, c.elat);
+        UnitTickArgs ua{};
+        ua.hw_children = P->d_hwc; ua.qch = qch; ua.a2 = nullptr; ua.c1own = nullptr; ua.zc = nullptr; ua.za = nullptr;
+        adjoint_replay(c, ua.t, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_tick_unit<true> : k_tick_unit<false>), g, dim3(kBlock), 0, st, ua); });
+    }
+    if (ni > 0) {      // with no inner reach there is no state and no tick
+        UnitAdjTickArgs a{};
+        a.child_ptr = P->d_child_ptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
+        adjoint_reverse(c, a, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_adj_tick_unit<true> : k_adj_tick_unit<false>), g, dim3(kBlock), 0, st, a); });
+    }
+    if (tape) {
+        UnitAdjReduceArgs r{};
+        adjoint_reduce_args(c, r);
+        r.hw_children = P->d_hwc; r.qch0 = qch0e;
+        hipLaunchKernelGGL((c.one ? k_adj_reduce_unit<true> : k_adj_reduce_unit<false>), c.reduce_grid(), dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef)
+        hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, c.L.splits, (const int32_t *)P->d_child_ptr,
+                           (const int32_t *)P->d_perm, n, grad_coef);
+    if (grad_qch0 || grad_qfull0)
+        hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
+                           (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax);
+    if (grad_lateral) {
+        hipLaunchKernelGGL(k_adj_rows_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
+                           grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                           (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T, nsub,
+                           S, (int32_t)c.dmax);
+        c.rows_between(1, c.egrad, grad_lateral);
+    }
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+}  // namespace

@@ -14,8 +14,8 @@
 //
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
-// rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp (device code), rr_exec.hpp (plan object, executor), then the
-// C ABI below.
+// rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp, rr_kernels_adjoint_unit.hpp (device code), rr_exec.hpp (plan object, executor),
+// then the C ABI below; rr_adjoint.hpp (the adjoints' host side) is included where its entry points are.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
 #include "rr_kernels_tile.hpp"
@@ -1096,211 +1096,38 @@ int rr_metrics_finish_dev(int device, int64_t n, const double *state, double *ou
     return RR_OK;
 }
 
-// ---- adjoint of RapidMuskingum routing (rr_kernels_adjoint.hpp) ----
+// ---- adjoints of RapidMuskingum and UnitMuskingum routing (rr_adjoint.hpp) ----
 
-namespace {
+}  // extern "C"
 
-constexpr int64_t kAdjPermRows = 16;          // rows per pass of the tiled permutation
-constexpr int64_t kAdjTargetBlocks = 2048;    // blocks of k_adj_reduce: column blocks x sub-step ranges
+#include "rr_adjoint.hpp"      // here, not at the top: templated kernels land in the code object in the order of their first launch
 
-// The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
-// (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
-// order), lateral rows and gradient rows in engine order (T rows each), the permutation's intermediate rows, the reduction slab
-// (4 x n per sub-step range), two scratch rows for k_tick.
-struct AdjointLayout {
-    int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
-    int64_t chunk, splits, steps_per_split;
-};
+extern "C" {
 
-AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub)
-{
-    AdjointLayout L{};
-    const int64_t S = T * nsub;
-    L.chunk = std::min<int64_t>(T, kAdjPermRows);
-    const int64_t col_blocks = (n + kBlock - 1) / kBlock;
-    const int64_t want = std::max<int64_t>(1, (kAdjTargetBlocks + col_blocks - 1) / col_blocks);
-    L.splits = std::max<int64_t>(1, std::min(want, S));
-    L.steps_per_split = (S + L.splits - 1) / L.splits;
-    L.splits = (S + L.steps_per_split - 1) / L.steps_per_split;
-    L.qtape = 0;
-    L.mtape = L.qtape + (S + depth + 1) * n;
-    L.lat = L.mtape + (S + depth - 1) * n;
-    L.grad = L.lat + T * n;
-    L.mrows = L.grad + T * n;
-    L.slab = L.mrows + L.chunk * n;
-    L.scratch = L.slab + L.splits * 4 * n;
-    L.total = L.scratch + 2 * n;
-    return L;
-}
-
-// Plan data the adjoint reads besides the streaming layout: the tiled permutation tables and the downstream position of each position.
-int adjoint_ready(rr_plan *P)
-{
-    if (!P->perm_ready) {
-        int rc = upload_tiled_permutations(P);
-        if (rc) return rc;
-    }
-    if (!P->d_adj_down) {
-        const rr::HostPlan &H = P->h;
-        std::vector<int32_t> down(H.n, -1);
-        for (int64_t p = 0; p < H.n; ++p)
-            for (int32_t u = H.child_ptr[p]; u < H.child_ptr[p + 1]; ++u) down[u] = (int32_t)p;
-        int32_t *d = nullptr;
-        int rc = dev_alloc(&d, H.n);
-        if (!rc) rc = dev_upload(d, down);
-        if (rc) { if (d) (void)hipFree(d); return rc; }
-        P->d_adj_down = d;
-    }
-    return RR_OK;
-}
-
-}  // namespace
-
-int rr_rapid_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
-{
-    if (!P || !bytes) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: null argument");
-    *bytes = 0;
-    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_work_bytes: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
-    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: need T >= 1 and sub-steps >= 1");
-    const rr::HostPlan &H = P->h;
-    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_rapid_adjoint_work_bytes: too many sub-steps for one call: split the series into windows");
-    HIPCHK(hipSetDevice(P->device));
-    if (H.n == 0) return RR_OK;
-    if (int rc = adjoint_ready(P)) return rc;
-    *bytes = adjoint_layout(H.n, H.depth, T, nsub).total * (int64_t)sizeof(double);
-    return RR_OK;
-}
+int rr_rapid_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes) { return adjoint_work_bytes(kRapidAdjoint, P, T, nsub, bytes); }
 
 int rr_rapid_adjoint_dev(rr_plan *P, const double *q0, const double *lateral, int64_t lat_rows, const double *discharge,
                          const double *grad_out, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef,
                          void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream)
 {
-    if (!P) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: null plan");
-    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
-    HIPCHK(hipSetDevice(P->device));
-    if (P->n_ghost > 0 || P->n_export > 0)
-        return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: the plan has boundary reaches (rr_plan_set_boundary): partitioned networks have no adjoint");
-    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_rapid_adjoint_dev called before rr_plan_set_coeffs");
-    if (!P->weights_uniform)
-        return fail(RR_E_UNSUPPORTED, "rr_rapid_adjoint_dev: per-edge weights (lhs_off_data not -c1 of the downstream reach): the adjoint needs one c1 per reach");
-    if (P->ses.open) return fail(RR_E_STATE, "rr_rapid_adjoint_dev: a routing call is open");
-    const rr::HostPlan &H = P->h;
-    const int64_t n = H.n;
-    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: need T >= 1 and sub-steps >= 1");
-    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: too many sub-steps for one call: split the series into windows");
-    if (n == 0 || (!grad_lateral && !grad_q0 && !grad_coef)) return RR_OK;
-    if (grad_coef && !q0) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: the coefficient gradients need q0");
-    if (lateral && lat_rows < T) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: fewer lateral rows than T");
-    if (lateral && !P->has_c4) return fail(RR_E_STATE, "rr_rapid_adjoint_dev: lateral rows but no c4_dt (rr_plan_set_coeffs got NULL)");
-    if (grad_out && !discharge) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: grad_out needs the discharge of the forward call (its clamp mask)");
-    if (grad_lateral && !lateral) return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: grad_lateral of a channel-only call (lateral is NULL)");
-    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub);
-    const int64_t need = L.total * (int64_t)sizeof(double);
-    if (!work || work_bytes < need)
-        return fail(RR_E_INVALID, "rr_rapid_adjoint_dev: work memory smaller than rr_rapid_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
-    if (!P->perm_ready || !P->d_adj_down)
-        return fail(RR_E_STATE, "rr_rapid_adjoint_dev: call rr_rapid_adjoint_work_bytes first (it uploads the plan's permutation tables once)");
-
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t S = T * nsub, dmax = H.depth - 1, ticks = S + dmax;
-    double *const base = static_cast<double *>(work);
-    double *qtape = base + L.qtape, *mtape = base + L.mtape, *elat = base + L.lat, *egrad = base + L.grad, *mrows = base + L.mrows,
-           *slab = base + L.slab, *isum = base + L.scratch, *oscr = isum + n;
-    const bool one = nsub == 1;
-    auto rows_between = [&](int which, const double *src, double *dst) {      // T rows, params <-> engine order
-        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
-            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
-                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
-    };
-
-    // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
-        const int64_t count = T * n;
-        hipLaunchKernelGGL(k_adj_mask, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st, mtape, grad_out,
-                           discharge, count, 1.0 / (double)nsub);
-        rows_between(0, mtape, egrad);
-    }
-    // the forward again, into a tick-indexed tape: k_tick as the route calls run it, with its three rotating rows spread over the tape
-    if (grad_coef) {
-        if (lateral) rows_between(0, lateral, elat);
-        hipLaunchKernelGGL(k_adj_tape_init, grid1(n), dim3(kBlock), 0, st, qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
-        TickArgs a{};
-        a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c1row = P->d_c1row_h; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
-        a.isum = isum; a.bidx = P->d_bidx; a.ghost = nullptr; a.exports = nullptr; a.n_ghost = 0; a.n_export = 0;
-        a.in = lateral ? elat : nullptr; a.in_ld = n; a.in_rows = Div32((uint32_t)T);
-        a.out = oscr; a.out_ld = 0; a.out_rows = Div32(1u);      // discharge rows are not kept: every row lands on one scratch row
-        a.total_substeps = S; a.nsub = Div32((uint32_t)nsub); a.inv_nsub = 1.0 / (double)nsub;
-        for (int64_t tau = 0; tau < ticks; ++tau) {
-            const int64_t lag_lo = std::max<int64_t>(0, tau - S + 1), lag_hi = std::min<int64_t>(tau, dmax);
-            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
-            if (p_hi <= p_lo) continue;
-            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
-            a.xc = qtape + (tau + 2) * n; a.xa = a.xc - n; a.xb = a.xc - 2 * n;
-            const dim3 g = grid1(p_hi - p_lo);
-            if (lateral) {
-                if (one) hipLaunchKernelGGL((k_tick<true, true>), g, dim3(kBlock), 0, st, a);
-                else hipLaunchKernelGGL((k_tick<true, false>), g, dim3(kBlock), 0, st, a);
-            } else {
-                if (one) hipLaunchKernelGGL((k_tick<false, true>), g, dim3(kBlock), 0, st, a);
-                else hipLaunchKernelGGL((k_tick<false, false>), g, dim3(kBlock), 0, st, a);
-            }
-        }
-    }
-    // reverse ticks: reach at lag l runs reverse step tau - (Dmax - l)
-    {
-        AdjTickArgs a{};
-        a.lag = P->d_lag; a.down = P->d_adj_down; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3;
-        a.g = grad_out ? egrad : nullptr; a.gf = grad_qfinal; a.perm = P->d_perm;
-        a.n = n; a.dmax = (int32_t)dmax; a.total_substeps = S; a.nsub = Div32((uint32_t)nsub);
-        for (int64_t tau = 0; tau < ticks; ++tau) {
-            const int64_t lag_lo = std::max<int64_t>(0, dmax - tau), lag_hi = std::min<int64_t>(dmax, dmax - tau + S - 1);
-            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
-            if (p_hi <= p_lo) continue;
-            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
-            a.mc = mtape + tau * n;
-            a.ma = tau >= 1 ? a.mc - n : a.mc;      // never read at tick 0 (nothing runs r > 0 or has a downstream reach there)
-            a.mb = tau >= 2 ? a.mc - 2 * n : a.mc;  // read from tick 2 on only
-            const dim3 g = grid1(p_hi - p_lo);
-            if (one) hipLaunchKernelGGL(k_adj_tick<true>, g, dim3(kBlock), 0, st, a);
-            else hipLaunchKernelGGL(k_adj_tick<false>, g, dim3(kBlock), 0, st, a);
-        }
-    }
-    if (grad_coef) {
-        AdjReduceArgs r{};
-        r.lag = P->d_lag; r.child_ptr = P->d_child_ptr; r.qtape = qtape; r.mtape = mtape; r.lat = lateral ? elat : nullptr; r.slab = slab;
-        r.n = n; r.total_substeps = S; r.steps_per_split = L.steps_per_split; r.dmax = (int32_t)dmax; r.nsub = Div32((uint32_t)nsub);
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits);
-        if (one) hipLaunchKernelGGL(k_adj_reduce<true>, g, dim3(kBlock), 0, st, r);
-        else hipLaunchKernelGGL(k_adj_reduce<false>, g, dim3(kBlock), 0, st, r);
-    }
-    if (grad_coef || grad_q0)
-        hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)slab, L.splits, (const double *)mtape,
-                           (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
-                           (const double *)P->d_c3, n, S, (int32_t)dmax, lateral ? 1 : 0, grad_coef, grad_q0);
-    if (grad_lateral) {
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535));
-        hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, egrad, (const double *)mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
-                           T, nsub, S, (int32_t)dmax);
-        rows_between(1, egrad, grad_lateral);
-    }
-    HIPCHK(hipGetLastError());
-    return RR_OK;
+    AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream};
+    return rapid_adjoint("rr_rapid_adjoint_dev", c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
 }
 
-// ---- adjoint of UnitMuskingum routing and of the unit-hydrograph convolution (rr_kernels_adjoint_unit.hpp) ----
+int rr_unit_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes) { return adjoint_work_bytes(kUnitAdjoint, P, T, nsub, bytes); }
+
+int rr_unit_adjoint_dev(rr_plan *P, const double *q_ch0, const double *q_full0, const double *lateral, int64_t lat_rows,
+                        const double *discharge, const double *grad_out, const double *grad_qch_final, const double *grad_qfull_final,
+                        double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
+                        int64_t T, int64_t nsub, void *stream)
+{
+    AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream};
+    return unit_adjoint("rr_unit_adjoint_dev", c, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+}
+
+// ---- adjoint of the unit-hydrograph convolution (rr_kernels_adjoint_unit.hpp) ----
 
 namespace {
-
-// The work memory of one UnitMuskingum adjoint call, in doubles, front to back: q_full tape and mu tape as in AdjointLayout, lateral
-// and gradient rows in engine order, the permutation's intermediate rows, the reduction slab (3 x n per sub-step range), six scratch
-// rows: k_tick_unit's running sum and its discarded discharge row, q_ch (updated in place), q_ch0, dL/d(q_ch final), dL/d(q_full final).
-AdjointLayout unit_adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub)
-{
-    AdjointLayout L = adjoint_layout(n, depth, T, nsub);
-    L.scratch = L.slab + L.splits * 3 * n;
-    L.total = L.scratch + 6 * n;
-    return L;
-}
 
 constexpr int kUhAdjRows = 16;      // rows per thread of k_uh_adjoint_depth
 constexpr int kUhAdjTaps = 16;      // taps per thread of k_uh_adjoint_kernel
@@ -1320,143 +1147,6 @@ UhAdjointLayout uh_adjoint_layout(int64_t T, int64_t n_ks, int64_t n)
 }
 
 }  // namespace
-
-int rr_unit_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
-{
-    if (!P || !bytes) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: null argument");
-    *bytes = 0;
-    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_work_bytes: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
-    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: need T >= 1 and sub-steps >= 1");
-    const rr::HostPlan &H = P->h;
-    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_unit_adjoint_work_bytes: too many sub-steps for one call: split the series into windows");
-    HIPCHK(hipSetDevice(P->device));
-    if (H.n == 0) return RR_OK;
-    if (int rc = adjoint_ready(P)) return rc;
-    *bytes = unit_adjoint_layout(H.n, H.depth, T, nsub).total * (int64_t)sizeof(double);
-    return RR_OK;
-}
-
-int rr_unit_adjoint_dev(rr_plan *P, const double *q_ch0, const double *q_full0, const double *lateral, int64_t lat_rows,
-                        const double *discharge, const double *grad_out, const double *grad_qch_final, const double *grad_qfull_final,
-                        double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
-                        int64_t T, int64_t nsub, void *stream)
-{
-    if (!P) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: null plan");
-    if (P->device < 0) return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: host-only plan (RR_DEVICE_NONE): the adjoint runs on the GPU only");
-    HIPCHK(hipSetDevice(P->device));
-    if (P->n_ghost > 0 || P->n_export > 0)
-        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: the plan has boundary reaches (rr_plan_set_boundary): partitioned networks have no adjoint");
-    if (P->unit_general)
-        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: general edge data (rr_plan_set_unit_weights): the adjoint is that of the reference callers' unit weights");
-    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_unit_adjoint_dev called before rr_plan_set_coeffs");
-    if (!P->weights_uniform)
-        return fail(RR_E_UNSUPPORTED, "rr_unit_adjoint_dev: per-edge weights (lhs_off_data not -c1 of the downstream reach): the adjoint needs one c1 per reach");
-    if (P->ses.open) return fail(RR_E_STATE, "rr_unit_adjoint_dev: a routing call is open");
-    const rr::HostPlan &H = P->h;
-    const int64_t n = H.n, ni = (int64_t)H.inner_pos.size();
-    if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: need T >= 1 and sub-steps >= 1");
-    if (T * nsub + H.depth > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: too many sub-steps for one call: split the series into windows");
-    if (ni == 0) { grad_qch0 = nullptr; grad_qfull0 = nullptr; }      // no inner reach: the state vectors are empty
-    if (n == 0 || (!grad_lateral && !grad_qch0 && !grad_qfull0 && !grad_coef)) return RR_OK;
-    if (grad_coef && ni > 0 && (!q_ch0 || !q_full0 || !lateral))
-        return fail(RR_E_INVALID, "rr_unit_adjoint_dev: the coefficient gradients need q_ch0, q_full0 and the lateral rows");
-    if (lateral && lat_rows < T) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: fewer lateral rows than T");
-    if (grad_out && !discharge) return fail(RR_E_INVALID, "rr_unit_adjoint_dev: grad_out needs the discharge of the forward call (its clamp mask)");
-    const AdjointLayout L = unit_adjoint_layout(n, H.depth, T, nsub);
-    const int64_t need = L.total * (int64_t)sizeof(double);
-    if (!work || work_bytes < need)
-        return fail(RR_E_INVALID, "rr_unit_adjoint_dev: work memory smaller than rr_unit_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
-    if (!P->perm_ready || !P->d_adj_down)
-        return fail(RR_E_STATE, "rr_unit_adjoint_dev: call rr_unit_adjoint_work_bytes first (it uploads the plan's permutation tables once)");
-
-    const hipStream_t st = (hipStream_t)stream;
-    const int64_t S = T * nsub, dmax = H.depth - 1, ticks = S + dmax;
-    double *const base = static_cast<double *>(work);
-    double *qtape = base + L.qtape, *mtape = base + L.mtape, *elat = base + L.lat, *egrad = base + L.grad, *mrows = base + L.mrows,
-           *slab = base + L.slab, *isum = base + L.scratch, *oscr = isum + n, *qch = oscr + n, *qch0e = qch + n, *gcf = qch0e + n, *gff = gcf + n;
-    const bool one = nsub == 1, tape = grad_coef && ni > 0;
-    const unsigned row_blocks = (unsigned)std::min<int64_t>(T, 65535);
-    auto rows_between = [&](int which, const double *src, double *dst) {      // T rows, params <-> engine order
-        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
-            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
-                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
-    };
-
-    // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
-        hipLaunchKernelGGL(k_adj_mask_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, mtape, grad_out, discharge,
-                           (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
-        rows_between(0, mtape, egrad);
-    }
-    if (ni > 0 && (tape || grad_qch_final || grad_qfull_final))
-        hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff, grad_qch_final,
-                           grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
-    // the forward again, into a tick-indexed tape: k_tick_unit on its one-weight branch, its three rotating rows spread over the tape
-    if (tape) {
-        rows_between(0, lateral, elat);
-        UnitTickArgs ua{};
-        TickArgs &a = ua.t;
-        a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c1row = P->d_c1row_h; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
-        a.isum = isum; a.bidx = P->d_bidx; a.ghost = nullptr; a.exports = nullptr; a.n_ghost = 0; a.n_export = 0;
-        a.in = elat; a.in_ld = n; a.in_rows = Div32((uint32_t)T);
-        a.out = oscr; a.out_ld = 0; a.out_rows = Div32(1u);      // discharge rows are not kept: every row lands on one scratch row
-        a.total_substeps = S; a.nsub = Div32((uint32_t)nsub); a.inv_nsub = 1.0 / (double)nsub;
-        ua.hw_children = P->d_hwc; ua.qch = qch; ua.a2 = nullptr; ua.c1own = nullptr; ua.zc = nullptr; ua.za = nullptr;
-        for (int64_t tau = 0; tau < ticks; ++tau) {
-            const int64_t lag_lo = std::max<int64_t>(0, tau - S + 1), lag_hi = std::min<int64_t>(tau, dmax);
-            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
-            if (p_hi <= p_lo) continue;
-            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
-            a.xc = qtape + (tau + 2) * n; a.xa = a.xc - n; a.xb = a.xc - 2 * n;
-            const dim3 g = grid1(p_hi - p_lo);
-            if (one) hipLaunchKernelGGL(k_tick_unit<true>, g, dim3(kBlock), 0, st, ua);
-            else hipLaunchKernelGGL(k_tick_unit<false>, g, dim3(kBlock), 0, st, ua);
-        }
-    }
-    // reverse ticks: reach at lag l runs reverse step tau - (Dmax - l); with no inner reach there is no state and no tick
-    if (ni > 0) {
-        UnitAdjTickArgs a{};
-        a.lag = P->d_lag; a.child_ptr = P->d_child_ptr; a.down = P->d_adj_down; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3;
-        a.g = grad_out ? egrad : nullptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
-        a.n = n; a.dmax = (int32_t)dmax; a.total_substeps = S; a.nsub = Div32((uint32_t)nsub);
-        for (int64_t tau = 0; tau < ticks; ++tau) {
-            const int64_t lag_lo = std::max<int64_t>(0, dmax - tau), lag_hi = std::min<int64_t>(dmax, dmax - tau + S - 1);
-            const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
-            if (p_hi <= p_lo) continue;
-            a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
-            a.mc = mtape + tau * n;
-            a.ma = tau >= 1 ? a.mc - n : a.mc;      // never read at tick 0 (nothing runs r > 0 or has a downstream reach there)
-            a.mb = tau >= 2 ? a.mc - 2 * n : a.mc;  // read from tick 2 on only
-            const dim3 g = grid1(p_hi - p_lo);
-            if (one) hipLaunchKernelGGL(k_adj_tick_unit<true>, g, dim3(kBlock), 0, st, a);
-            else hipLaunchKernelGGL(k_adj_tick_unit<false>, g, dim3(kBlock), 0, st, a);
-        }
-    }
-    if (tape) {
-        UnitAdjReduceArgs r{};
-        r.lag = P->d_lag; r.child_ptr = P->d_child_ptr; r.hw_children = P->d_hwc; r.qtape = qtape; r.mtape = mtape; r.lat = elat; r.qch0 = qch0e;
-        r.slab = slab; r.n = n; r.total_substeps = S; r.steps_per_split = L.steps_per_split; r.dmax = (int32_t)dmax; r.nsub = Div32((uint32_t)nsub);
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits);
-        if (one) hipLaunchKernelGGL(k_adj_reduce_unit<true>, g, dim3(kBlock), 0, st, r);
-        else hipLaunchKernelGGL(k_adj_reduce_unit<false>, g, dim3(kBlock), 0, st, r);
-    }
-    if (grad_coef)
-        hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)slab, L.splits, (const int32_t *)P->d_child_ptr,
-                           (const int32_t *)P->d_perm, n, grad_coef);
-    if (grad_qch0 || grad_qfull0)
-        hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)mtape,
-                           (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
-                           (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)dmax);
-    if (grad_lateral) {
-        hipLaunchKernelGGL(k_adj_rows_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, egrad,
-                           grad_out ? (const double *)egrad : nullptr, grad_qfull_final ? (const double *)gff : nullptr, (const double *)mtape,
-                           (const int32_t *)P->d_lag, (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w,
-                           (const double *)P->d_c2, n, T, nsub, S, (int32_t)dmax);
-        rows_between(1, egrad, grad_lateral);
-    }
-    HIPCHK(hipGetLastError());
-    return RR_OK;
-}
 
 int rr_uh_adjoint_work_bytes(int64_t T, int64_t n_ks, int64_t n, int64_t *bytes)
 {

@@ -883,15 +883,21 @@ int session_store_rows(rr_plan *P, int64_t r0, int64_t r1)   // ring -> params o
     return RR_OK;
 }
 
+// The engine positions [p_lo, p_hi) with work at tick tau of a call of `total` sub-steps: the lags with tau - total < lag <= tau.
+// False when there is none.
+inline bool tick_window(const rr::HostPlan &H, int64_t tau, int64_t total, int64_t &p_lo, int64_t &p_hi)
+{
+    p_lo = H.lag_start[std::max<int64_t>(0, tau - total + 1)];
+    p_hi = H.lag_start[std::min<int64_t>(tau, H.depth - 1) + 1];
+    return p_hi > p_lo;
+}
+
 int session_launch_tick(rr_plan *P, int64_t tau)
 {
     Session &S = P->ses;
-    const rr::HostPlan &H = P->h;
-    const int64_t n = H.n, dmax = H.depth - 1;
-    // active lags: tau - total < lag <= tau
-    const int64_t lag_lo = std::max<int64_t>(0, tau - S.total + 1), lag_hi = std::min<int64_t>(tau, dmax);
-    const int64_t p_lo = H.lag_start[lag_lo], p_hi = H.lag_start[lag_hi + 1];
-    if (p_hi <= p_lo) return RR_OK;
+    const int64_t n = P->h.n;
+    int64_t p_lo, p_hi;
+    if (!tick_window(P->h, tau, S.total, p_lo, p_hi)) return RR_OK;
     TickArgs &a = S.a;
     a.p_lo = (int32_t)p_lo; a.p_hi = (int32_t)p_hi; a.tau = tau;
     a.xc = P->d_x + (tau % 3) * n;

@@ -1,5 +1,6 @@
 // rr_kernels_adjoint.hpp -- the adjoint of RapidMuskingum routing (rr_rapid_adjoint_dev): the reverse routing
-// tick, the per-column reduction of the coefficient gradients and the row pass of the lateral-inflow gradient.
+// tick, the per-column reduction of the coefficient gradients and the row pass of the lateral-inflow gradient.  The host side that
+// launches them is rapid_adjoint in rr_adjoint.hpp.
 // Part of the one translation unit rr_engine.hip builds (included from there, in order; not a stand-alone header).
 //
 // Forward, equation s = 1..S of reach i (S = T * nsub, sub-step s - 1 of row t = (s - 1) / nsub):

@@ -1,6 +1,7 @@
 // rr_kernels_adjoint_unit.hpp -- the adjoint of UnitMuskingum routing (rr_unit_adjoint_dev) and of the unit-hydrograph convolution
-// (rr_uh_adjoint_dev), DESIGN.md section 12.  Part of the one translation unit rr_engine.hip builds (included from there, after
-// rr_kernels_adjoint.hpp; not a stand-alone header).
+// (rr_uh_adjoint_dev), DESIGN.md section 12.  The host side that launches them: unit_adjoint in rr_adjoint.hpp, which shares its
+// driver with the Rapid adjoint; rr_uh_adjoint_dev in rr_engine.hip.  Part of the one translation unit rr_engine.hip builds (included
+// from there, after rr_kernels_adjoint.hpp; not a stand-alone header).
 //
 // Forward (river_route/routers/_numba_kernels.py:114-171 with the callers' unit edge weights), inner reach i with headwater
 // tributaries H(i) and inner tributaries U(i), equation s = 1..S, row t = (s - 1) / nsub:

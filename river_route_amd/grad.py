@@ -63,6 +63,25 @@ def _set_coeffs(plan: Plan, c1, c2, c3, c4dt, device: int) -> None:
     plan.set_coeffs(-c1h[plan._indices], _host(c2), _host(c3), None if c4dt is None else _host(c4dt))
 
 
+def _route_backward(plan, coeffs, c4dt, device, grads, shapes, want_coef, need_coef, work_bytes, adjoint):
+    """What the backward passes of RapidRoute and UnitRoute share.  The saved coefficients go back onto the plan (c4dt: what the forward
+    set); `grads` become contiguous float64 (None stays None); one output per entry of `shapes` (None: not wanted) and, if want_coef,
+    one row of coefficient gradients per entry of `coeffs` are allocated, and `work_bytes()` bytes of work memory (torch's allocator
+    owns the tapes); adjoint(*grads, *outputs, g_coef, work, nbytes, stream) makes the engine's call on torch's stream.  Returns the
+    outputs, then the coefficient rows need_coef asks for (None for the others)."""
+    _set_coeffs(plan, *coeffs[:3], c4dt, plan.device)
+    stream = torch.cuda.current_stream(plan.device).cuda_stream
+    f64 = dict(dtype=torch.float64, device=device)
+    grads = [None if g is None else g.to(**f64).contiguous() for g in grads]
+    outs = [None if shape is None else torch.empty(shape, **f64) for shape in shapes]
+    g_coef = torch.empty((len(coeffs), plan.n), **f64) if want_coef else None
+    nbytes = work_bytes()
+    work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
+    adjoint(*grads, *outs, g_coef, work, nbytes, stream)
+    coef = [g_coef[j].to(c.device) if want_coef and want else None for j, (c, want) in enumerate(zip(coeffs, need_coef))]
+    return (*outs, *coef)
+
+
 class RapidRoute(torch.autograd.Function):
     """(discharge[T, n], q_final[n]) = RapidMuskingum routing of T rows of qlateral (None: channel-only, then `rows` gives T) from
     q0 with nsub sub-steps per row and per-reach coefficients c1, c2, c3, c4dt.  Forward: rr_rapid_route_dev (or
@@ -94,30 +113,15 @@ class RapidRoute(torch.autograd.Function):
         need = ctx.needs_input_grad      # plan, nsub, rows, q0, qlateral, c1, c2, c3, c4dt
         want_q0, want_ql = need[3], need[4] and qlateral is not None
         want_coef = any(need[5:8]) or (need[8] and qlateral is not None)
-        none = (None,) * 9
         if (grad_discharge is None and grad_qfinal is None) or not (want_q0 or want_ql or want_coef):
-            return none
-        dev = plan.device
-        c1, c2, c3, c4dt = ctx.coeffs
-        _set_coeffs(plan, c1, c2, c3, c4dt if qlateral is not None else None, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        device = q0.device
-        f64 = dict(dtype=torch.float64, device=device)
-        g_out = None if grad_discharge is None else grad_discharge.to(**f64).contiguous()
-        g_fin = None if grad_qfinal is None else grad_qfinal.to(**f64).contiguous()
-        g_ql = torch.empty((T, plan.n), **f64) if want_ql else None
-        g_q0 = torch.empty(plan.n, **f64) if want_q0 else None
-        g_coef = torch.empty((4, plan.n), **f64) if want_coef else None
-        nbytes = plan.rapid_adjoint_work_bytes(T, nsub)
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)       # torch's allocator owns the tapes
-        plan.rapid_adjoint_dev(q0.detach(), None if qlateral is None else qlateral.detach(), T, discharge, g_out, g_fin, g_ql, g_q0,
-                               g_coef, work, nbytes, T, nsub, stream)
-        coef = [None] * 4
-        if g_coef is not None:
-            for j, c in enumerate((c1, c2, c3, c4dt)):
-                if need[5 + j] and c is not None:
-                    coef[j] = g_coef[j].to(c.device)
-        return (None, None, None, g_q0, g_ql, *coef)
+            return (None,) * 9
+        ql = None if qlateral is None else qlateral.detach()
+        return (None, None, None, *_route_backward(
+            plan, ctx.coeffs, ctx.coeffs[3] if qlateral is not None else None, q0.device, (grad_discharge, grad_qfinal),
+            (plan.n if want_q0 else None, (T, plan.n) if want_ql else None), want_coef,
+            [need[5 + j] and c is not None for j, c in enumerate(ctx.coeffs)], lambda: plan.rapid_adjoint_work_bytes(T, nsub),
+            lambda g_out, g_fin, g_q0, g_ql, g_coef, work, nbytes, stream: plan.rapid_adjoint_dev(
+                q0.detach(), ql, T, discharge, g_out, g_fin, g_ql, g_q0, g_coef, work, nbytes, T, nsub, stream)))
 
 
 def _check_tensor(t, name, shape):
@@ -131,6 +135,55 @@ def _check_tensor(t, name, shape):
         raise ValueError(f'{name} must be contiguous')
 
 
+def _check_rows(t, name, n):
+    if not isinstance(t, torch.Tensor) or t.ndim != 2:
+        raise ValueError(f'{name} must be a 2-D (T, n) tensor (ensembles have no adjoint: route members one by one)')
+    T = int(t.shape[0])
+    if T < 1:
+        raise ValueError(f'{name} has no rows')
+    _check_tensor(t, name, (T, n))
+    return T
+
+
+def _check_call(plan, state_len, states, k, x, dt_routing, dt_runoff, rows_per_window):
+    """The checks the routing functions share before their rows: the plan's type, the time steps, the state vectors (of plan.n or
+    plan.n_inner values, as state_len names), k and x, rows_per_window.  Returns nsub."""
+    if not isinstance(plan, Plan):
+        raise TypeError('plan must be a river_route_amd.engine.Plan (one GPU; partitioned plans have no adjoint)')
+    if not (float(dt_routing) > 0 and float(dt_runoff) > 0):
+        raise ValueError('dt_routing and dt_runoff must be positive')
+    nsub = int(round(float(dt_runoff) / float(dt_routing)))
+    if nsub < 1 or nsub * float(dt_routing) != float(dt_runoff):
+        raise ValueError(f'dt_runoff ({dt_runoff}) must be a whole number of routing steps ({dt_routing})')
+    for t, name in states:
+        _check_tensor(t, name, (getattr(plan, state_len),))
+    for t, name in ((k, 'k'), (x, 'x')):
+        _check_tensor(t, name, (plan.n,))
+    if rows_per_window is not None and int(rows_per_window) < 1:
+        raise ValueError('rows_per_window must be >= 1')
+    return nsub
+
+
+def _check_device(plan, pairs):
+    """The last checks, so that the others are made before a device is needed: the plan has a GPU and every tensor given is on it."""
+    if plan.device < 0:
+        raise ValueError('plan is host-only (RR_DEVICE_NONE): the adjoint runs on the GPU only')
+    for t, name in pairs:
+        if t is not None and (t.device.type != 'cuda' or t.device.index != plan.device):
+            raise ValueError(f"{name} must be on cuda:{plan.device}, the plan's device (it is on {t.device})")
+
+
+def _in_windows(T, rows_per_window, state, route):
+    """Rows [0, T) in windows of rows_per_window rows (None: one window), chained through the state tuple: route(t0, t1, *state) returns the
+    window's discharge rows followed by its final state.  Returns (discharge[T, n], *final state)."""
+    R = T if rows_per_window is None else min(T, int(rows_per_window))
+    parts = []
+    for t0 in range(0, T, R):
+        d, *state = route(t0, min(T, t0 + R), *state)
+        parts.append(d)
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), *state
+
+
 def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None):
     """Differentiable RapidMuskingum routing: (discharge[T, n], q_final[n]) as torch tensors on the plan's device.
 
@@ -140,46 +193,18 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
     steps.  Gradients reach q0, qlateral, k and x (whichever require grad).  rows_per_window routes the series in windows chained
     through q_final -> q0, so the tape memory of the backward pass is one window's.  Every argument is checked before the GPU is
     touched."""
-    if not isinstance(plan, Plan):
-        raise TypeError('plan must be a river_route_amd.engine.Plan (one GPU; partitioned plans have no adjoint)')
-    n = plan.n
-    if not (float(dt_routing) > 0 and float(dt_runoff) > 0):
-        raise ValueError('dt_routing and dt_runoff must be positive')
-    nsub = int(round(float(dt_runoff) / float(dt_routing)))
-    if nsub < 1 or nsub * float(dt_routing) != float(dt_runoff):
-        raise ValueError(f'dt_runoff ({dt_runoff}) must be a whole number of routing steps ({dt_routing})')
-    _check_tensor(q0, 'q0', (n,))
+    nsub = _check_call(plan, 'n', ((q0, 'q0'),), k, x, dt_routing, dt_runoff, rows_per_window)
     if qlateral is None:
         if rows is None or int(rows) < 1:
             raise ValueError('channel-only routing (qlateral=None) needs rows >= 1')
         T = int(rows)
     else:
-        if not isinstance(qlateral, torch.Tensor) or qlateral.ndim != 2:
-            raise ValueError('qlateral must be a 2-D (T, n) tensor (ensembles have no adjoint: route members one by one)')
-        T = int(qlateral.shape[0])
-        if T < 1:
-            raise ValueError('qlateral has no rows')
-        _check_tensor(qlateral, 'qlateral', (T, n))
-    for t, name in ((k, 'k'), (x, 'x')):
-        _check_tensor(t, name, (n,))
-    if rows_per_window is not None and int(rows_per_window) < 1:
-        raise ValueError('rows_per_window must be >= 1')
-    if plan.device < 0:
-        raise ValueError('plan is host-only (RR_DEVICE_NONE): the adjoint runs on the GPU only')
-    for t, name in ((q0, 'q0'), (qlateral, 'qlateral')):
-        if t is not None and (t.device.type != 'cuda' or t.device.index != plan.device):
-            raise ValueError(f"{name} must be on cuda:{plan.device}, the plan's device (it is on {t.device})")
-
+        T = _check_rows(qlateral, 'qlateral', plan.n)
+    _check_device(plan, ((q0, 'q0'), (qlateral, 'qlateral')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
     c4dt = (c1 + c2) / float(dt_runoff)
-    R = T if rows_per_window is None else min(T, int(rows_per_window))
-    q, parts = q0, []
-    for t0 in range(0, T, R):
-        t1 = min(T, t0 + R)
-        ql = None if qlateral is None else qlateral[t0:t1]
-        d, q = RapidRoute.apply(plan, nsub, t1 - t0, q, ql, c1, c2, c3, c4dt)
-        parts.append(d)
-    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q
+    return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRoute.apply(
+        plan, nsub, t1 - t0, q, None if qlateral is None else qlateral[t0:t1], c1, c2, c3, c4dt))
 
 
 # ---- UnitMuskingum ----
@@ -250,69 +275,15 @@ class UnitRoute(torch.autograd.Function):
         T = int(lateral.shape[0])
         need = ctx.needs_input_grad      # plan, nsub, q_ch0, q_full0, lateral, c1, c2, c3
         want_coef = any(need[5:8])
-        none = (None,) * 8
         if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[2:5]) or want_coef):
-            return none
-        dev = plan.device
-        c1, c2, c3 = ctx.coeffs
-        _set_coeffs(plan, c1, c2, c3, None, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        f64 = dict(dtype=torch.float64, device=lateral.device)
-        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
-        g_qch0 = torch.empty(plan.n_inner, **f64) if need[2] else None
-        g_qfull0 = torch.empty(plan.n_inner, **f64) if need[3] else None
-        g_lat = torch.empty((T, plan.n), **f64) if need[4] else None
-        g_coef = torch.empty((3, plan.n), **f64) if want_coef else None
-        nbytes = plan.unit_adjoint_work_bytes(T, nsub)
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=lateral.device)       # torch's allocator owns the tapes
-        plan.unit_adjoint_dev(q_ch0.detach(), q_full0.detach(), lateral.detach(), T, discharge, g_out, g_c, g_f, g_lat, g_qch0, g_qfull0,
-                              g_coef, work, nbytes, T, nsub, stream)
-        coef = [None] * 3
-        if g_coef is not None:
-            for j, c in enumerate((c1, c2, c3)):
-                if need[5 + j]:
-                    coef[j] = g_coef[j].to(c.device)
-        return (None, None, g_qch0, g_qfull0, g_lat, *coef)
-
-
-def _check_rows(t, name, n):
-    if not isinstance(t, torch.Tensor) or t.ndim != 2:
-        raise ValueError(f'{name} must be a 2-D (T, n) tensor (ensembles have no adjoint: route members one by one)')
-    T = int(t.shape[0])
-    if T < 1:
-        raise ValueError(f'{name} has no rows')
-    _check_tensor(t, name, (T, n))
-    return T
-
-
-def _check_cuda(pairs, device):
-    for t, name in pairs:
-        if t.device.type != 'cuda' or t.device.index != device:
-            raise ValueError(f'{name} must be on cuda:{device} (it is on {t.device})')
-
-
-def _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window):
-    """The checks unit_route and unit_muskingum share; returns nsub."""
-    if not isinstance(plan, Plan):
-        raise TypeError('plan must be a river_route_amd.engine.Plan (one GPU; partitioned plans have no adjoint)')
-    if not (float(dt_routing) > 0 and float(dt_runoff) > 0):
-        raise ValueError('dt_routing and dt_runoff must be positive')
-    nsub = int(round(float(dt_runoff) / float(dt_routing)))
-    if nsub < 1 or nsub * float(dt_routing) != float(dt_runoff):
-        raise ValueError(f'dt_runoff ({dt_runoff}) must be a whole number of routing steps ({dt_routing})')
-    _check_tensor(q_ch0, 'q_ch0', (plan.n_inner,))
-    _check_tensor(q_full0, 'q_full0', (plan.n_inner,))
-    for t, name in ((k, 'k'), (x, 'x')):
-        _check_tensor(t, name, (plan.n,))
-    if rows_per_window is not None and int(rows_per_window) < 1:
-        raise ValueError('rows_per_window must be >= 1')
-    return nsub
-
-
-def _check_unit_device(plan, tensors):
-    if plan.device < 0:
-        raise ValueError('plan is host-only (RR_DEVICE_NONE): the adjoint runs on the GPU only')
-    _check_cuda(tensors, plan.device)
+            return (None,) * 8
+        return (None, None, *_route_backward(
+            plan, ctx.coeffs, None, lateral.device, (grad_discharge, grad_qch, grad_qfull),
+            (plan.n_inner if need[2] else None, plan.n_inner if need[3] else None, (T, plan.n) if need[4] else None), want_coef, need[5:8],
+            lambda: plan.unit_adjoint_work_bytes(T, nsub),
+            lambda g_out, g_c, g_f, g_qch0, g_qfull0, g_lat, g_coef, work, nbytes, stream: plan.unit_adjoint_dev(
+                q_ch0.detach(), q_full0.detach(), lateral.detach(), T, discharge, g_out, g_c, g_f, g_lat, g_qch0, g_qfull0, g_coef, work,
+                nbytes, T, nsub, stream)))
 
 
 def uh_convolve(kernel, state, depth):
@@ -329,13 +300,10 @@ def uh_convolve(kernel, state, depth):
     _check_rows(depth, 'depth', n)
     if depth.device.type != 'cuda':
         raise ValueError(f'depth must be on a GPU (it is on {depth.device})')
-    _check_cuda(((kernel, 'kernel'), (state, 'state')), depth.device.index)
+    for t, name in ((kernel, 'kernel'), (state, 'state')):
+        if t.device != depth.device:
+            raise ValueError(f'{name} must be on cuda:{depth.device.index} (it is on {t.device})')
     return UhConvolve.apply(kernel, state, depth)
-
-
-def _coefficients_and_window(k, x, dt_routing, T, rows_per_window):
-    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
-    return c1, c2, c3, (T if rows_per_window is None else min(T, int(rows_per_window)))
 
 
 def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None):
@@ -348,15 +316,12 @@ def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_
     lateral, k and x (a headwater's k and x get 0: its coefficients are never read).  rows_per_window routes the series in windows
     chained through the states, so the tape memory of the backward pass is one window's.  Every argument is checked before the GPU
     is touched."""
-    nsub = _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window)
+    nsub = _check_call(plan, 'n_inner', ((q_ch0, 'q_ch0'), (q_full0, 'q_full0')), k, x, dt_routing, dt_runoff, rows_per_window)
     T = _check_rows(lateral, 'lateral', plan.n)
-    _check_unit_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
-    c1, c2, c3, R = _coefficients_and_window(k, x, dt_routing, T, rows_per_window)
-    q_ch, q_full, parts = q_ch0, q_full0, []
-    for t0 in range(0, T, R):
-        d, q_ch, q_full = UnitRoute.apply(plan, nsub, q_ch, q_full, lateral[t0:min(T, t0 + R)], c1, c2, c3)
-        parts.append(d)
-    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q_ch, q_full
+    _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: UnitRoute.apply(
+        plan, nsub, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
 
 
 def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None):
@@ -365,18 +330,18 @@ def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_ro
     q_ch[n_inner], q_full[n_inner], uh_state_out[n_ks, n]); gradients reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x.
     With rows_per_window each window convolves its own rows and hands q_ch, q_full and the convolution's state to the next, as the
     router does from file to file."""
-    nsub = _check_unit_plan(plan, k, x, q_ch0, q_full0, dt_routing, dt_runoff, rows_per_window)
+    nsub = _check_call(plan, 'n_inner', ((q_ch0, 'q_ch0'), (q_full0, 'q_full0')), k, x, dt_routing, dt_runoff, rows_per_window)
     T = _check_rows(depth, 'depth', plan.n)
     if not isinstance(uh_kernel, torch.Tensor) or uh_kernel.ndim != 2 or int(uh_kernel.shape[0]) < 1:
         raise ValueError('uh_kernel must be a 2-D (n_ks, n) tensor')
     n_ks = int(uh_kernel.shape[0])
     _check_tensor(uh_kernel, 'uh_kernel', (n_ks, plan.n))
     _check_tensor(uh_state, 'uh_state', (n_ks, plan.n))
-    _check_unit_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
-    c1, c2, c3, R = _coefficients_and_window(k, x, dt_routing, T, rows_per_window)
-    q_ch, q_full, state, parts = q_ch0, q_full0, uh_state, []
-    for t0 in range(0, T, R):
-        lateral, state = UhConvolve.apply(uh_kernel, state, depth[t0:min(T, t0 + R)])
-        d, q_ch, q_full = UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3)
-        parts.append(d)
-    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), q_ch, q_full, state
+    _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+
+    def route(t0, t1, q_ch, q_full, state):
+        lateral, state = UhConvolve.apply(uh_kernel, state, depth[t0:t1])
+        return (*UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3), state)
+
+    return _in_windows(T, rows_per_window, (q_ch0, q_full0, uh_state), route)
