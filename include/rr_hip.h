@@ -472,6 +472,29 @@ int rr_uh_adjoint_dev(int device, const double *kernel, const double *depth, con
                       double *grad_depth, double *grad_kernel, double *grad_state, void *work, int64_t work_bytes, int64_t T,
                       int64_t n_ks, int64_t n, void *stream);
 
+/* ---- adjoint of the skill scores (river_route/metrics.py) ----
+ * The gradient of a scalar loss L through the five scores of one rr_metrics_update_dev + rr_metrics_finish_dev pair over all `rows`
+ * rows, with respect to y_pred.  y_true, y_pred, their pitches and types and n are those of the update; `state` is the
+ * RR_METRICS_STATE x n state it left; grad_scores[5 * n] is dL/d(out) of rr_metrics_finish_dev (grad_scores[k * n + j]).  With
+ * t = y_true[r, j], p = y_pred[r, c], c the column of y_pred that column j is scored against, column j adds to grad_pred[r, c]
+ *   A + B (t - mean_true) + P (p - mean_pred) + S sign(t - p),  sign(0) = 0,
+ * A, B, P, S following from the state and the five gradients.  A score whose gradient is exactly 0 adds
+ * nothing; a score that is NaN by rr_metrics_finish_dev's rules with a gradient other than 0 makes the column's gradient NaN; r
+ * passes no gradient where its unclipped value lies outside [-1, 1].  grad_pred has y_pred's element type, row r at
+ * grad_pred + r * grad_pitch elements.
+ * Without a column map (order, distinct_columns, segments NULL; n_distinct = n) c = j and every element of the n columns is written.
+ * With one, the caller passes the map sorted: order[n] is a stable argsort of pred_columns, distinct_columns[n_distinct] its
+ * distinct values ascending, segments[n_distinct + 1] the start of each value's run in `order` (segments[n_distinct] = n).
+ * Column distinct_columns[u] of grad_pred receives the sum of the shares of the y_true columns order[segments[u]] ..
+ * order[segments[u + 1] - 1], added in that order; other columns of grad_pred are not touched (the caller zero-fills them).
+ * The maps are not range-checked on the device.  Work memory: rr_metrics_adjoint_work_bytes = 48 n bytes (six doubles per column).
+ * Enqueue only, allocates nothing, no atomics: the same inputs give the same bits.  RR_E_INVALID for a null or short argument. */
+int rr_metrics_adjoint_work_bytes(int64_t n, int64_t *bytes);
+int rr_metrics_adjoint_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                           const void *y_pred, int pred_is_f32, int64_t pred_pitch, const double *state, const double *grad_scores,
+                           int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
+                           void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream);
+
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);

@@ -15,7 +15,8 @@
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
 // rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp, rr_kernels_adjoint_unit.hpp (device code), rr_exec.hpp (plan object, executor),
-// then the C ABI below; rr_adjoint.hpp (the adjoints' host side) is included where its entry points are.
+// then the C ABI below; rr_adjoint.hpp (the adjoints' host side) and rr_kernels_metrics_adjoint.hpp (the adjoint of the skill
+// scores, device code) are included where their entry points are.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
 #include "rr_kernels_tile.hpp"
@@ -1526,6 +1527,61 @@ int rr_dev_synchronize(int device)
     if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_dev_synchronize: no such HIP device");
     HIPCHK(hipSetDevice(device));
     HIPCHK(hipDeviceSynchronize());
+    return RR_OK;
+}
+
+}  // extern "C"
+
+// ---- adjoint of the skill scores (rr_kernels_metrics_adjoint.hpp) ----
+
+#include "rr_kernels_metrics_adjoint.hpp"      // here, not at the top: the kernels above keep their place in the code object
+
+extern "C" {
+
+int rr_metrics_adjoint_work_bytes(int64_t n, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, "rr_metrics_adjoint_work_bytes: null out");
+    *bytes = 0;
+    if (n < 0 || n > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "rr_metrics_adjoint_work_bytes: sizes out of range");
+    *bytes = kMetricsAdjCoef * n * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_metrics_adjoint_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                           const void *y_pred, int pred_is_f32, int64_t pred_pitch, const double *state, const double *grad_scores,
+                           int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
+                           void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_adjoint_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    int64_t need = 0;
+    if (int rc = rr_metrics_adjoint_work_bytes(n, &need)) return rc;
+    if (rows < 0) return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: sizes out of range");
+    if (n == 0 || rows == 0) return RR_OK;
+    if (!y_true || !y_pred || !state || !grad_scores || !grad_pred) return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: null array");
+    const bool mapped = order || distinct_columns || segments;
+    if (mapped && !(order && distinct_columns && segments))
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: order, distinct_columns and segments come together or not at all");
+    if (mapped ? (n_distinct < 1 || n_distinct > n) : n_distinct != n)
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: n_distinct must be n without a column map and 1 .. n with one");
+    if (true_pitch < n || pred_pitch < (mapped ? 1 : n) || grad_pitch < (mapped ? 1 : n))
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: row pitch shorter than the columns read or written");
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_dev: work memory smaller than rr_metrics_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    double *coef = static_cast<double *>(work);
+    hipLaunchKernelGGL(k_metrics_adjoint_coef, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, state, grad_scores, n, coef);
+    HIPCHK(hipGetLastError());
+    int64_t splits, rows_per_split;
+    metrics_split(n_distinct, rows, splits, rows_per_split);      // the forward's row ranges: narrow inputs still fill the card
+    const dim3 g((unsigned)((n_distinct + kBlock - 1) / kBlock), (unsigned)splits);
+#define RR_METRICS_ADJ_LAUNCH(TT_, TP_)                                                                                          \
+    hipLaunchKernelGGL((k_metrics_adjoint_rows<TT_, TP_>), g, dim3(kBlock), 0, (hipStream_t)stream, (const TT_ *)y_true, true_pitch, \
+                       (const TP_ *)y_pred, pred_pitch, (const double *)coef, n, order, distinct_columns, segments, n_distinct, rows, \
+                       rows_per_split, (TP_ *)grad_pred, grad_pitch)
+    if (true_is_f32) { if (pred_is_f32) RR_METRICS_ADJ_LAUNCH(float, float); else RR_METRICS_ADJ_LAUNCH(float, double); }
+    else { if (pred_is_f32) RR_METRICS_ADJ_LAUNCH(double, float); else RR_METRICS_ADJ_LAUNCH(double, double); }
+#undef RR_METRICS_ADJ_LAUNCH
+    HIPCHK(hipGetLastError());
     return RR_OK;
 }
 

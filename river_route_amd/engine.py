@@ -13,7 +13,8 @@ from ._lib import RRError, check, ptr
 
 __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'uh_adjoint_work_bytes', 'uh_adjoint_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
            'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
-           'metrics_update_dev', 'metrics_finish_dev', 'grid_overlap_area', 'grid_overlap_area_dev']
+           'metrics_update_dev', 'metrics_finish_dev', 'metrics_adjoint_work_bytes', 'metrics_adjoint_dev', 'grid_overlap_area',
+           'grid_overlap_area_dev']
 
 
 MODE_RAPID, MODE_MUSKINGUM, MODE_UNIT = 0, 1, 2      # include/rr_hip.h: RR_MODE_*
@@ -535,6 +536,23 @@ def metrics_update_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is
 def metrics_finish_dev(n, state, out, device: int = 0, stream=None) -> None:
     """rr_metrics_finish_dev: [9][n] state -> out[5][n] (me, mae, mse, pearson_r, kge2012); only enqueues."""
     check(_lib.lib().rr_metrics_finish_dev(int(device), int(n), ptr(state), ptr(out), stream))
+
+
+def metrics_adjoint_work_bytes(n: int) -> int:
+    """rr_metrics_adjoint_work_bytes: device work memory one rr_metrics_adjoint_dev over n scored columns needs."""
+    out = C.c_int64(0)
+    check(_lib.lib().rr_metrics_adjoint_work_bytes(int(n), C.byref(out)))
+    return int(out.value)
+
+
+def metrics_adjoint_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is_f32, pred_pitch, state, grad_scores, n_distinct, order,
+                        distinct_columns, segments, grad_pred, grad_pitch, work, work_bytes, device: int = 0, stream=None) -> None:
+    """rr_metrics_adjoint_dev: dL/dy_pred from the [9][n] score state and dL/d(scores)[5][n]; only enqueues.  order, distinct_columns
+    and segments are the sorted column map (all None: column j against column j)."""
+    check(_lib.lib().rr_metrics_adjoint_dev(int(device), int(n), int(rows), ptr(y_true), int(bool(true_is_f32)), int(true_pitch), ptr(y_pred),
+                                            int(bool(pred_is_f32)), int(pred_pitch), ptr(state), ptr(grad_scores), int(n_distinct),
+                                            ptr(order), ptr(distinct_columns), ptr(segments), ptr(grad_pred), int(grad_pitch), ptr(work),
+                                            int(work_bytes), stream))
 
 
 def grid_overlap_area(row_rings, ring_offsets, ring_weight, lon, lat, x_bounds, y_bounds, row_cells, pair_offsets,

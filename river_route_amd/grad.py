@@ -20,17 +20,23 @@ unit_muskingum, the two chained as the router chains them, in windows if asked:
 
 Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, ensembles, partitioned plans and plans
 with set_unit_weights edge data are refused.
+
+The loss a calibration minimises is a skill score at gauges, and `scores` is rr.metrics.scores with an autograd graph (DESIGN.md
+section 12c): the same five values, bit for bit, and a backward pass that writes dL/dQ in one streaming pass on the GPU:
+
+    kge = rr.grad.scores(observed, Q, columns=gauges)['kge2012']      # observed[T, n_gauges] against Q[:, gauges], no gather copy
+    (1 - kge).mean().backward()
 """
 from __future__ import annotations
 
 import numpy as np
 import torch
 
-from . import engine
+from . import engine, metrics
 from .engine import Plan
 
 __all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
-           'unit_muskingum']
+           'unit_muskingum', 'Scores', 'scores']
 
 
 def muskingum_coefficients(k, x, dt_routing):
@@ -345,3 +351,142 @@ def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_ro
         return (*UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (q_ch0, q_full0, uh_state), route)
+
+
+# ---- skill scores as a loss ----
+
+def _pitch(a) -> int:
+    """Elements from one row of a 2-D tensor that metrics._Rows accepted to the next (one row: its width)."""
+    return int(a.stride(0)) if a.shape[0] > 1 else int(a.shape[1])
+
+
+def column_map_pointers(cols_dev, n, n_distinct):
+    """Device addresses of (columns, order, distinct columns, segment starts) inside the one int32 tensor that
+    np.concatenate(_sorted_columns(...)) uploads: n, n, n_distinct and n_distinct + 1 values.  None: four times None."""
+    if cols_dev is None:
+        return None, None, None, None
+    base, size = cols_dev.data_ptr(), cols_dev.element_size()
+    return tuple(base + k * size for k in (0, n, 2 * n, 2 * n + n_distinct))
+
+
+class Scores(torch.autograd.Function):
+    """out[5, n] = the scores of rr.metrics.SCORES per column of y_true[T, n] (the tensor of a metrics._Rows, a constant) against
+    y_pred, a (T, m) or (T,) tensor.  Forward: rr_metrics_update_dev and rr_metrics_finish_dev, as rr.metrics.scores calls them.
+    Backward: rr_metrics_adjoint_dev from the 9 x n state the forward left; beside it only the two inputs (saved tensors, read in
+    place) and the sorted column map are kept.  cols is None or (columns, order, distinct columns, segment starts) as int32 host
+    arrays."""
+
+    @staticmethod
+    def forward(ctx, y_pred, y_true, cols):
+        t, p = y_true, metrics._Rows(y_pred.detach(), 'y_pred').tensor
+        dev, where = p.device.index or 0, p.device
+        T, n = (int(v) for v in t.shape)
+        f32 = torch.float32
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        cols_dev = None if cols is None else torch.from_numpy(np.concatenate(cols)).to(where)
+        state = torch.zeros((engine.METRICS_STATE, n), dtype=torch.float64, device=where)
+        nbytes = engine.metrics_work_bytes(n, T)
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=where)
+        n_distinct = n if cols is None else len(cols[2])
+        engine.metrics_update_dev(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p),
+                                  column_map_pointers(cols_dev, n, n_distinct)[0], state, work, nbytes, device=dev, stream=stream)
+        out = torch.empty((engine.METRICS_SCORES, n), dtype=torch.float64, device=where)
+        engine.metrics_finish_dev(n, state, out, device=dev, stream=stream)
+        ctx.save_for_backward(t, p, state, cols_dev)      # a change of the rows in place between the two passes is noticed
+        ctx.n_distinct = n_distinct
+        ctx.pred_shape = tuple(y_pred.shape)
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_out):
+        if grad_out is None or not ctx.needs_input_grad[0]:
+            return None, None, None
+        t, p, state, cols_dev = ctx.saved_tensors
+        dev, where, nd = p.device.index or 0, p.device, ctx.n_distinct
+        T, n = (int(v) for v in t.shape)
+        m = int(p.shape[1])
+        f32 = torch.float32
+        g = grad_out.to(dtype=torch.float64, device=where).contiguous()
+        _, order, distinct, segments = column_map_pointers(cols_dev, n, nd)
+        # unscored columns are zero and stay so: the kernel writes the scored ones only
+        make = torch.empty if cols_dev is None else torch.zeros
+        grad = make((T, m), dtype=p.dtype, device=where)
+        nbytes = engine.metrics_adjoint_work_bytes(n)
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=where)
+        engine.metrics_adjoint_dev(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p), state, g, nd, order,
+                                   distinct, segments, grad, m, work, nbytes, device=dev, stream=torch.cuda.current_stream(dev).cuda_stream)
+        return grad.reshape(ctx.pred_shape), None, None
+
+
+def _check_series(a, name):
+    if not isinstance(a, torch.Tensor):
+        raise TypeError(f'{name} must be a torch tensor on the GPU (rr.metrics.scores takes numpy arrays; it has no gradient)')
+    if a.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f'{name} must be float32 or float64 (it is {a.dtype})')
+    if a.dim() not in (1, 2):
+        raise ValueError(f'{name} must be 1-D (time) or 2-D (time, column)')
+    return int(a.shape[0]), (int(a.shape[1]) if a.dim() == 2 else 1)
+
+
+def _sorted_columns(columns, n, m):
+    """columns (host values) checked against n scored columns and y_pred's m, with the backward's segment map: (columns, a stable
+    argsort, the distinct values, the start of each value's run) as int32, so a column scored several times adds its shares by
+    ascending index."""
+    c = np.asarray(columns)
+    if c.shape != (n,) or not np.issubdtype(c.dtype, np.integer):
+        raise ValueError(f'columns must be a 1-D integer array of length {n}')
+    if c.min() < 0 or c.max() >= m:
+        raise ValueError(f'columns refers to column {int(c.min() if c.min() < 0 else c.max())} of y_pred, which has {m} columns')
+    if m > np.iinfo(np.int32).max:
+        raise ValueError('y_pred has too many columns for a column map')
+    order = np.argsort(c, kind='stable')
+    distinct, starts = np.unique(c[order], return_index=True)
+    return tuple(a.astype(np.int32) for a in (c, order, distinct, np.append(starts, n)))
+
+
+def scores(y_true, y_pred, columns=None) -> dict:
+    """rr.metrics.scores with autograd: {'me', 'mae', 'mse', 'pearson_r', 'kge2012'} -> (n,) float64 tensors on the GPU, the values
+    rr.metrics.scores returns for the same tensors bit for bit, each carrying a graph to y_pred.
+
+    y_true (T, n) or (T,) and y_pred (T, m) or (T,) are float32 or float64 tensors on one GPU; y_true is a constant (one that
+    requires grad is refused).  columns: optional int array of length n, column j of y_true is scored against column columns[j]
+    of y_pred (repeats allowed, no gather copy); without it m must equal n.  Views whose columns are adjacent and whose rows do
+    not overlap are read in place, others are copied first.
+
+    The backward pass writes dL/dy_pred (y_pred's shape and dtype) on the GPU from the per-column state the forward left: columns
+    nobody scores get 0, a column scored several times the sum of its shares.  A score whose incoming gradient is exactly 0 for a
+    column adds nothing there, so a constant series may sit in an mse loss although its pearson_r and kge2012 are NaN; a NaN score
+    with a non-zero gradient makes the column's gradient NaN.  No atomics: two backward passes give the same bits.  Every argument
+    is checked before the GPU is touched."""
+    T, n = _check_series(y_true, 'y_true')
+    Tp, m = _check_series(y_pred, 'y_pred')
+    if y_true.requires_grad:
+        raise ValueError('y_true is a constant here: it must not require grad (detach it)')
+    if T != Tp:
+        raise ValueError(f'y_true has {T} rows, y_pred {Tp}')
+    if T < 1:
+        raise ValueError('y_true and y_pred have no rows')
+    if n < 1:
+        raise ValueError('y_true has no columns')
+    cols = None
+    if columns is None:
+        if m != n:
+            raise ValueError(f'y_pred has {m} columns, expected {n} (or pass columns=)')
+    else:
+        on_gpu = isinstance(columns, torch.Tensor) and columns.device.type != 'cpu'
+        if on_gpu:      # its values are read after the device checks; shape and type need no device
+            if columns.dim() != 1 or int(columns.shape[0]) != n or columns.is_floating_point() or columns.is_complex() or columns.dtype == torch.bool:
+                raise ValueError(f'columns must be a 1-D integer array of length {n}')
+        else:
+            cols = _sorted_columns(columns, n, m)
+    for a, name in ((y_true, 'y_true'), (y_pred, 'y_pred')):
+        if a.device.type != 'cuda':
+            raise ValueError(f'{name} must be on the GPU (it is on {a.device})')
+    if y_true.device != y_pred.device:
+        raise ValueError(f'y_true is on {y_true.device}, y_pred on {y_pred.device}')
+    if columns is not None and cols is None:
+        cols = _sorted_columns(columns.detach().cpu(), n, m)
+    out = Scores.apply(y_pred, metrics._Rows(y_true, 'y_true').tensor, cols)
+    return {k: out[i] for i, k in enumerate(metrics.SCORES)}
