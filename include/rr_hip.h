@@ -433,6 +433,29 @@ int rr_rapid_adjoint_dev(rr_plan *plan, const double *q0, const double *lateral,
                          const double *grad_out, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef,
                          void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream);
 
+/* ---- the same for several forcing series at once ----
+ * `members` rr_rapid_route_dev calls on one plan with one coefficient set (a mini-batch of windows, the members of a forcing
+ * ensemble), their gradients from one pair of sweeps: every reverse and replay tick is one launch over (positions, members), so the
+ * tick launches number 2 (S + depth - 1) whatever the member count.  Member m's arrays lie m pitches (in doubles) behind member 0's:
+ *   q0                 at q0_pitch (0: one q0[n] shared by every member; otherwise >= n);
+ *   lateral, grad_lateral    at lat_pitch (>= T*n; lat_rows >= T rows per member);
+ *   discharge, grad_out      at out_pitch (>= T*n);
+ *   grad_qfinal, grad_q0     [members*n], dense;
+ *   grad_coef[4*n]     the SUM over the members, folded in ascending member order (within a member its sub-step ranges in order).
+ * NULL arguments mean what they mean in rr_rapid_adjoint_dev, for every member alike.  Each member's grad_lateral and grad_q0 are
+ * the bits rr_rapid_adjoint_dev gives for that member alone; with members == 1 so is grad_coef.
+ * Work memory (rr_rapid_adjoint_batch_work_bytes; caller-provided, the call allocates nothing and only enqueues on `stream`):
+ *   8 n (members (2 S + 2 T + 2 depth + 4 splits + 2) + min(T, 16)) bytes, splits = min(S, ceil(2048 / (members ceil(n / 256)))):
+ *   the single call's tapes, rows, partial sums and scratch rows once per member, the permutation's rows once.
+ * rr_rapid_adjoint_batch_work_bytes readies the plan as rr_rapid_adjoint_work_bytes does.  No atomics.  Refused: what
+ * rr_rapid_adjoint_dev refuses, then RR_E_INVALID for members < 1 or > 65535, for a pitch shorter than one member's rows, and for
+ * too little work memory. */
+int rr_rapid_adjoint_batch_work_bytes(rr_plan *plan, int64_t members, int64_t T, int64_t nsub, int64_t *bytes);
+int rr_rapid_adjoint_batch_dev(rr_plan *plan, int64_t members, const double *q0, int64_t q0_pitch, const double *lateral, int64_t lat_rows,
+                               int64_t lat_pitch, const double *discharge, const double *grad_out, int64_t out_pitch,
+                               const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef, void *work,
+                               int64_t work_bytes, int64_t T, int64_t nsub, void *stream);
+
 /* ---- adjoint of UnitMuskingum routing ----
  * The gradient of a scalar loss L through one rr_unit_route_dev call (unit_route, river_route/routers/_numba_kernels.py:88-171, with
  * the edge data of the reference's callers: a_inner_data = a_hw_data = 1, lhs_off_data = -c1 of the row) of T rows, nsub sub-steps,

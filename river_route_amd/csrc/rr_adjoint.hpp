@@ -6,42 +6,48 @@
 namespace {
 
 constexpr int64_t kAdjPermRows = 16;          // rows per pass of the tiled permutation
-constexpr int64_t kAdjTargetBlocks = 2048;    // blocks of a split reduction: column blocks x sub-step ranges
+constexpr int64_t kAdjTargetBlocks = 2048;    // blocks of a split reduction: column blocks x sub-step ranges x members
+constexpr int64_t kAdjMaxMembers = 65535;     // members of a batched call: a grid's second and third dimension
 
 // What differs between the two routers outside the kernels: the name of the sizing entry point (the errors name it) and two row counts
 // of the work memory: sums per reach in the reduction (c1..c4 / c1..c3) and scratch rows (the tick's running sum and its discarded
 // discharge row; Unit adds q_ch, updated in place, q_ch0, dL/d(q_ch final) and dL/d(q_full final) in engine order).
-struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; };
+struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; bool batch = false; };      // batch: the member-batched entry points
 constexpr AdjointKind kRapidAdjoint{"rr_rapid_adjoint_work_bytes", 4, 2};
+constexpr AdjointKind kRapidAdjointBatch{"rr_rapid_adjoint_batch_work_bytes", 4, 2, true};
 constexpr AdjointKind kUnitAdjoint{"rr_unit_adjoint_work_bytes", 3, 6};
 
 // The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
 // (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
 // order), lateral rows and gradient rows in engine order (T rows each), the permutation's intermediate rows, the reduction slab
-// (slab_rows x n per sub-step range), the scratch rows.
+// (slab_rows x n per sub-step range), the scratch rows.  A batched call (members > 1) has every section but the permutation's rows
+// once per member, member m's part m pitches into the section: with one member this is the single call's layout, byte for byte.
 struct AdjointLayout {
     int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
     int64_t chunk, splits, steps_per_split;
+    int64_t qtape_pitch, mtape_pitch, row_pitch, slab_pitch, scratch_pitch;      // doubles from one member's part to the next
 };
 
-AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, const AdjointKind &K)
+AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, const AdjointKind &K, int64_t members = 1)
 {
     AdjointLayout L{};
     const int64_t S = T * nsub;
     L.chunk = std::min<int64_t>(T, kAdjPermRows);
-    const int64_t col_blocks = (n + kBlock - 1) / kBlock;
+    const int64_t col_blocks = ((n + kBlock - 1) / kBlock) * members;
     const int64_t want = std::max<int64_t>(1, (kAdjTargetBlocks + col_blocks - 1) / col_blocks);
     L.splits = std::max<int64_t>(1, std::min(want, S));
     L.steps_per_split = (S + L.splits - 1) / L.splits;
     L.splits = (S + L.steps_per_split - 1) / L.steps_per_split;
+    L.qtape_pitch = (S + depth + 1) * n; L.mtape_pitch = (S + depth - 1) * n; L.row_pitch = T * n;
+    L.slab_pitch = L.splits * K.slab_rows * n; L.scratch_pitch = K.scratch_rows * n;
     L.qtape = 0;
-    L.mtape = L.qtape + (S + depth + 1) * n;
-    L.lat = L.mtape + (S + depth - 1) * n;
-    L.grad = L.lat + T * n;
-    L.mrows = L.grad + T * n;
+    L.mtape = L.qtape + members * L.qtape_pitch;
+    L.lat = L.mtape + members * L.mtape_pitch;
+    L.grad = L.lat + members * L.row_pitch;
+    L.mrows = L.grad + members * L.row_pitch;
     L.slab = L.mrows + L.chunk * n;
-    L.scratch = L.slab + L.splits * K.slab_rows * n;
-    L.total = L.scratch + K.scratch_rows * n;
+    L.scratch = L.slab + members * L.slab_pitch;
+    L.total = L.scratch + members * L.scratch_pitch;
     return L;
 }
 
@@ -74,20 +80,25 @@ struct AdjointCall {
     void *work; int64_t work_bytes;
     int64_t T, nsub;
     hipStream_t st;
+    // a batched call (rr_rapid_adjoint_batch_*): members, and the doubles from one member's q0 (0: one q0 for all), lateral /
+    // grad_lateral rows and discharge / grad_out rows to the next's.  The single-member entry points leave these as they are.
+    int64_t members = 1, q0_pitch = 0, lat_pitch = 0, out_pitch = 0;
     // set by adjoint_check
     int64_t n, S, dmax, ticks;
     bool one;                                                       // nsub == 1: the kernels' SINGLE_SUBSTEP forms
     AdjointLayout L;
     double *qtape, *mtape, *elat, *egrad, *mrows, *slab, *scratch;
 
-    void rows_between(int which, const double *src, double *dst) const      // T rows, params <-> engine order
+    // T rows of every member, params <-> engine order; member m's rows m pitches from the first's (one stream: the members share mrows)
+    void rows_between(int which, const double *src, double *dst, int64_t src_pitch = 0, int64_t dst_pitch = 0) const
     {
-        for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
-            permute_rows_via(P, which, RowView{const_cast<double *>(src), n, 0, (uint32_t)T}, RowView{dst, n, 0, (uint32_t)T}, t0,
-                             (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
+        for (int64_t m = 0; m < members; ++m)
+            for (int64_t t0 = 0; t0 < T; t0 += L.chunk)
+                permute_rows_via(P, which, RowView{const_cast<double *>(src) + m * src_pitch, n, 0, (uint32_t)T},
+                                 RowView{dst + m * dst_pitch, n, 0, (uint32_t)T}, t0, (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
     }
     const double *egrad_out() const { return grad_out ? egrad : nullptr; }      // masked dL/d(discharge) in engine order
-    dim3 reduce_grid() const { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits); }
+    dim3 reduce_grid() const { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits, (unsigned)members); }
 };
 
 // A check that is an entry point's own: after which shared ones it is tested (the plan's boundary check, the sizes, the lateral rows,
@@ -125,11 +136,13 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     const int64_t n = H.n, T = c.T, nsub = c.nsub;
     if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return no(RR_E_INVALID, ": need T >= 1 and sub-steps >= 1");
     if (T * nsub + H.depth > 0x7FFFFFFFLL) return no(RR_E_INVALID, ": too many sub-steps for one call: split the series into windows");
+    const auto members_ok = [&] { return c.members >= 1 && c.members <= kAdjMaxMembers; };
     if (sizing) {
+        if (!members_ok()) return no(RR_E_INVALID, ": need 1 <= members <= 65535");
         HIPCHK(hipSetDevice(P->device));
         if (n == 0) return RR_OK;
         if (int rc = adjoint_ready(P)) return rc;
-        *bytes = adjoint_layout(n, H.depth, T, nsub, K).total * (int64_t)sizeof(double);
+        *bytes = adjoint_layout(n, H.depth, T, nsub, K, c.members).total * (int64_t)sizeof(double);
         return RR_OK;
     }
     if (int rc = own(AdjOwn::Wanted)) return rc;
@@ -137,7 +150,10 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     if (int rc = own(AdjOwn::Lateral)) return rc;
     if (c.grad_out && !c.discharge) return no(RR_E_INVALID, ": grad_out needs the discharge of the forward call (its clamp mask)");
     if (int rc = own(AdjOwn::GradOut)) return rc;
-    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K);
+    if (!members_ok()) return no(RR_E_INVALID, ": need 1 <= members <= 65535");
+    if (K.batch && ((c.q0_pitch != 0 && c.q0_pitch < n) || (c.lateral && c.lat_pitch < T * n) || ((c.discharge || c.grad_out) && c.out_pitch < T * n)))
+        return no(RR_E_INVALID, ": a member pitch shorter than one member's rows (q0_pitch: 0 or >= n; lat_pitch, out_pitch >= T * n)");
+    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K, c.members);
     const int64_t need = L.total * (int64_t)sizeof(double);
     if (!c.work || c.work_bytes < need)
         return fail(RR_E_INVALID, std::string(who) + ": work memory smaller than " + K.sizer + " (" + std::to_string(need) + " bytes)");
@@ -151,11 +167,11 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     return RR_OK;
 }
 
-int adjoint_work_bytes(const AdjointKind &K, rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes)
+int adjoint_work_bytes(const AdjointKind &K, rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes, int64_t members = 1)
 {
     if (!bytes) return fail(RR_E_INVALID, std::string(K.sizer) + ": null argument");
     AdjointCall c{};
-    c.P = P; c.T = T; c.nsub = nsub;
+    c.P = P; c.T = T; c.nsub = nsub; c.members = members;
     return adjoint_check(K.sizer, K, c, bytes, {});
 }
 
@@ -213,53 +229,91 @@ void adjoint_reduce_args(const AdjointCall &c, Args &r)
 
 // ---- RapidMuskingum ----
 
-int rapid_adjoint(const char *who, AdjointCall &c, const double *q0, const double *grad_qfinal, double *grad_lateral, double *grad_q0,
-                  double *grad_coef)
+// What a checked call enqueues.  ENS: a batched call (rr_rapid_adjoint_batch_dev) -- the member-batched kernels on grids with a member
+// dimension, so the two sweeps launch once per tick whatever the member count; otherwise the single-member kernels, launched as ever.
+template <bool ENS>
+void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double *grad_qfinal, double *grad_lateral, double *grad_q0,
+                           double *grad_coef)
 {
     rr_plan *const P = c.P;
     const double *const lateral = c.lateral, *const discharge = c.discharge, *const grad_out = c.grad_out;
-    const int64_t T = c.T, nsub = c.nsub;
+    const int64_t T = c.T, nsub = c.nsub, n = c.n, S = c.S;
     const hipStream_t st = c.st;
-    const int rc = adjoint_check(who, kRapidAdjoint, c, nullptr, {
+    const AdjointLayout &L = c.L;
+    const unsigned M = (unsigned)c.members;
+    const int64_t lat_pitch = ENS ? c.lat_pitch : 0, out_pitch = ENS ? c.out_pitch : 0;
+    // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        const int64_t count = T * n;
+        const dim3 g((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192), M);
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_mask_batch, g, dim3(kBlock), 0, st, c.mtape, grad_out, discharge, count, 1.0 / (double)nsub, L.mtape_pitch, out_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_mask, g, dim3(kBlock), 0, st, c.mtape, grad_out, discharge, count, 1.0 / (double)nsub);
+        c.rows_between(0, c.mtape, c.egrad, L.mtape_pitch, L.row_pitch);
+    }
+    if (grad_coef) {
+        if (lateral) c.rows_between(0, lateral, c.elat, lat_pitch, L.row_pitch);
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), M);
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_tape_init_batch, g, dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n,
+                               L.qtape_pitch, c.q0_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_tape_init, g, dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
+        TickArgsOf<ENS> a{};
+        if constexpr (ENS) { a.tape_pitch = L.qtape_pitch; a.in_pitch = L.row_pitch; a.scratch_pitch = L.scratch_pitch; }
+        const auto tick = lateral ? (c.one ? k_tick<true, true, ENS> : k_tick<true, false, ENS>) : (c.one ? k_tick<false, true, ENS> : k_tick<false, false, ENS>);
+        adjoint_replay(c, a, [&](dim3 g) { g.y = M; hipLaunchKernelGGL(tick, g, dim3(kBlock), 0, st, a); });
+    }
+    AdjTickArgsOf<ENS> ra{};
+    ra.gf = grad_qfinal; ra.perm = P->d_perm;
+    if constexpr (ENS) { ra.tape_pitch = L.mtape_pitch; ra.g_pitch = L.row_pitch; ra.gf_pitch = n; }
+    adjoint_reverse(c, ra, [&](dim3 g) {
+        g.y = M;
+        hipLaunchKernelGGL((c.one ? k_adj_tick<true, ENS> : k_adj_tick<false, ENS>), g, dim3(kBlock), 0, st, ra);
+    });
+    if (grad_coef) {
+        AdjReduceArgsOf<ENS> r{};
+        adjoint_reduce_args(c, r);
+        if constexpr (ENS) { r.qtape_pitch = L.qtape_pitch; r.mtape_pitch = L.mtape_pitch; r.lat_pitch = L.row_pitch; r.slab_pitch = L.slab_pitch; }
+        hipLaunchKernelGGL((c.one ? k_adj_reduce<true, ENS> : k_adj_reduce<false, ENS>), c.reduce_grid(), dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef || grad_q0) {
+        if constexpr (ENS)      // without dL/dq0 only member 0's blocks have work: they fold every member's ranges
+            hipLaunchKernelGGL(k_adj_merge_batch, dim3((unsigned)((n + kBlock - 1) / kBlock), grad_q0 ? M : 1u), dim3(kBlock), 0, st,
+                               (const double *)c.slab, L.splits, c.members, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2, (const double *)P->d_c3, n, S,
+                               (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0, L.mtape_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, (const double *)c.mtape,
+                               (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
+                               (const double *)P->d_c3, n, S, (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0);
+    }
+    if (grad_lateral) {
+        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535), M);
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_rows_batch, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const double *)P->d_c4, n, T, nsub, S, (int32_t)c.dmax, L.row_pitch, L.mtape_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
+                               T, nsub, S, (int32_t)c.dmax);
+        c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
+    }
+}
+
+int rapid_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const double *q0, const double *grad_qfinal, double *grad_lateral,
+                  double *grad_q0, double *grad_coef)
+{
+    rr_plan *const P = c.P;
+    const double *const lateral = c.lateral;
+    const int rc = adjoint_check(who, K, c, nullptr, {
         {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_q0 && !grad_coef)), kAdjNothing, ""},
         {AdjOwn::Wanted, grad_coef && !q0, RR_E_INVALID, ": the coefficient gradients need q0"},
         {AdjOwn::Lateral, P && lateral && !P->has_c4, RR_E_STATE, ": lateral rows but no c4_dt (rr_plan_set_coeffs got NULL)"},
         {AdjOwn::GradOut, grad_lateral && !lateral, RR_E_INVALID, ": grad_lateral of a channel-only call (lateral is NULL)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-
-    const int64_t n = c.n, S = c.S;
-    // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
-        const int64_t count = T * n;
-        hipLaunchKernelGGL(k_adj_mask, dim3((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192)), dim3(kBlock), 0, st, c.mtape, grad_out,
-                           discharge, count, 1.0 / (double)nsub);
-        c.rows_between(0, c.mtape, c.egrad);
-    }
-    if (grad_coef) {
-        if (lateral) c.rows_between(0, lateral, c.elat);
-        hipLaunchKernelGGL(k_adj_tape_init, grid1(n), dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
-        TickArgs a{};
-        const auto tick = lateral ? (c.one ? k_tick<true, true> : k_tick<true, false>) : (c.one ? k_tick<false, true> : k_tick<false, false>);
-        adjoint_replay(c, a, [&](dim3 g) { hipLaunchKernelGGL(tick, g, dim3(kBlock), 0, st, a); });
-    }
-    AdjTickArgs ra{};
-    ra.gf = grad_qfinal; ra.perm = P->d_perm;
-    adjoint_reverse(c, ra, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_adj_tick<true> : k_adj_tick<false>), g, dim3(kBlock), 0, st, ra); });
-    if (grad_coef) {
-        AdjReduceArgs r{};
-        adjoint_reduce_args(c, r);
-        hipLaunchKernelGGL((c.one ? k_adj_reduce<true> : k_adj_reduce<false>), c.reduce_grid(), dim3(kBlock), 0, st, r);
-    }
-    if (grad_coef || grad_q0)
-        hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, c.L.splits, (const double *)c.mtape,
-                           (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
-                           (const double *)P->d_c3, n, S, (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0);
-    if (grad_lateral) {
-        const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535));
-        hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
-                           T, nsub, S, (int32_t)c.dmax);
-        c.rows_between(1, c.egrad, grad_lateral);
-    }
+    if (K.batch) rapid_adjoint_enqueue<true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    else rapid_adjoint_enqueue<false>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

@@ -1112,7 +1112,21 @@ int rr_rapid_adjoint_dev(rr_plan *P, const double *q0, const double *lateral, in
                          void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream)
 {
     AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream};
-    return rapid_adjoint("rr_rapid_adjoint_dev", c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    return rapid_adjoint("rr_rapid_adjoint_dev", kRapidAdjoint, c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+}
+
+int rr_rapid_adjoint_batch_work_bytes(rr_plan *P, int64_t members, int64_t T, int64_t nsub, int64_t *bytes)
+{
+    return adjoint_work_bytes(kRapidAdjointBatch, P, T, nsub, bytes, members);
+}
+
+int rr_rapid_adjoint_batch_dev(rr_plan *P, int64_t members, const double *q0, int64_t q0_pitch, const double *lateral, int64_t lat_rows,
+                               int64_t lat_pitch, const double *discharge, const double *grad_out, int64_t out_pitch, const double *grad_qfinal,
+                               double *grad_lateral, double *grad_q0, double *grad_coef, void *work, int64_t work_bytes, int64_t T, int64_t nsub,
+                               void *stream)
+{
+    AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream, members, q0_pitch, lat_pitch, out_pitch};
+    return rapid_adjoint("rr_rapid_adjoint_batch_dev", kRapidAdjointBatch, c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
 }
 
 int rr_unit_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes) { return adjoint_work_bytes(kUnitAdjoint, P, T, nsub, bytes); }

@@ -10,6 +10,13 @@
 // A reach reads only its one downstream reach, at this step and the next: with D(i) = Dmax - lag(i) (levels to the outlet),
 // reverse tick tau handles reach i at reverse step r = tau - D(i), s = S - r, and every tick is free of dependencies -- the
 // forward's lag trick with the edges turned round.  Tapes are tick-indexed: row tau holds what every position wrote at tick tau.
+//
+// Member-batched forms (rr_rapid_adjoint_batch_dev): several forcing series on one plan and one coefficient
+// set.  The members share every read-only plan array; member m owns a q tape, a mu tape, engine-order lateral and gradient rows,
+// slab and scratch rows at member pitches (64-bit element counts).  The templated kernels take a trailing ENS flag and an args
+// struct with the pitches appended, and form every index as (ENS ? index + offset : index), so their single-member instantiations
+// are the code they were (rr_kernels_tick.hpp: TickEnsArgs); the member is blockIdx.y, in the reduction, whose y is the sub-step
+// range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling that runs the same body on the member's pointers.
 #pragma once
 
 namespace {
@@ -33,10 +40,23 @@ struct AdjTickArgs {
     Div32 nsub;
 };
 
+// Member blockIdx.y: its mu tape rows (ma, mb, mc) at tape_pitch, its dL/d(discharge) rows at g_pitch and its dL/d(q_final) at gf_pitch.
+struct AdjTickEnsArgs : AdjTickArgs {
+    int64_t tape_pitch, g_pitch, gf_pitch;
+};
+template <bool ENS> using AdjTickArgsOf = typename std::conditional<ENS, AdjTickEnsArgs, AdjTickArgs>::type;
+__device__ __forceinline__ int64_t member_tape0(const AdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_tape0(const AdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
+__device__ __forceinline__ int64_t member_g0(const AdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_g0(const AdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.g_pitch; }
+__device__ __forceinline__ int64_t member_gf0(const AdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_gf0(const AdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.gf_pitch; }
+
 // One reverse tick: mu of every active position.  One reach per lane over lag-ordered positions, like k_tick; the downstream
 // reads hit a handful of cache lines per wave (the downstream reaches of consecutive positions are consecutive positions).
-template <bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgs a)
+// ENS: the member-batched form; the fma sequence of a member is the single call's.
+template <bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgsOf<ENS> a)
 {
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (p >= a.p_hi) return;
@@ -48,34 +68,56 @@ __global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgs a)
     if (SINGLE_SUBSTEP) t = ts;
     else { uint32_t rem; t = a.nsub.div(ts, rem); }
 
-    double m = a.g ? a.g[(int64_t)t * a.n + p] : 0.0;
-    if (r == 0 && a.gf) m += a.gf[a.perm[p]];
-    if (r > 0) m = __builtin_fma(a.c3[p], a.ma[p], m);
+    const int64_t mt = member_tape0(a), mg = member_g0(a), mf = member_gf0(a);
+    double m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
+    if (r == 0 && a.gf) m += a.gf[ENS ? a.perm[p] + mf : a.perm[p]];
+    if (r > 0) m = __builtin_fma(a.c3[p], a.ma[ENS ? p + mt : p], m);
     const int32_t d = a.down[p];
     if (d >= 0) {
-        m = __builtin_fma(a.w[p], a.ma[d], m);                   // c1[d] mu[s, d]: d ran reverse step r one tick ago
-        if (r > 0) m = __builtin_fma(a.c2[d], a.mb[d], m);       // c2[d] mu[s+1, d]: two ticks ago
+        m = __builtin_fma(a.w[p], a.ma[ENS ? d + mt : d], m);                   // c1[d] mu[s, d]: d ran reverse step r one tick ago
+        if (r > 0) m = __builtin_fma(a.c2[d], a.mb[ENS ? d + mt : d], m);       // c2[d] mu[s+1, d]: two ticks ago
     }
-    a.mc[p] = m;
+    a.mc[ENS ? p + mt : p] = m;
 }
 
 // q tape row tau - 1 at every position's first forward tick holds q0: what k_tick reads as "its own last value" and, two ticks
 // later, as "the old upstream value" of the reach below.  Storage row = tick + 2 (ticks -2 and -1 come first).
-__global__ __launch_bounds__(kBlock) void k_adj_tape_init(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag,
-                                                          int64_t n)
+__device__ __forceinline__ void adj_tape_init(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag, int64_t n)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     qtape[(int64_t)((lag[p] & kLagMask) + 1) * n + p] = q0[perm[p]];
 }
+__global__ __launch_bounds__(kBlock) void k_adj_tape_init(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag,
+                                                          int64_t n)
+{
+    adj_tape_init(qtape, q0, perm, lag, n);
+}
+// member blockIdx.y: its tape at tape_pitch, its q0 at q0_pitch (0: one q0 for every member)
+__global__ __launch_bounds__(kBlock) void k_adj_tape_init_batch(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag,
+                                                                int64_t n, int64_t tape_pitch, int64_t q0_pitch)
+{
+    adj_tape_init(qtape + (int64_t)blockIdx.y * tape_pitch, q0 + (int64_t)blockIdx.y * q0_pitch, perm, lag, n);
+}
 
 // dL/d(discharge) in params order with the forward's clamp and mean applied: the discharge row is max(mean, 0), so a value
 // that came out <= 0 passes no gradient.
-__global__ __launch_bounds__(kBlock) void k_adj_mask(double *dst, const double *grad_out, const double *discharge, int64_t count,
-                                                     double inv_nsub)
+__device__ __forceinline__ void adj_mask(double *dst, const double *grad_out, const double *discharge, int64_t count, double inv_nsub)
 {
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (int64_t)gridDim.x * kBlock)
         dst[k] = discharge[k] > 0.0 ? grad_out[k] * inv_nsub : 0.0;
+}
+__global__ __launch_bounds__(kBlock) void k_adj_mask(double *dst, const double *grad_out, const double *discharge, int64_t count,
+                                                     double inv_nsub)
+{
+    adj_mask(dst, grad_out, discharge, count, inv_nsub);
+}
+// member blockIdx.y: its destination rows at dst_pitch, its discharge and dL/d(discharge) rows at row_pitch
+__global__ __launch_bounds__(kBlock) void k_adj_mask_batch(double *dst, const double *grad_out, const double *discharge, int64_t count,
+                                                           double inv_nsub, int64_t dst_pitch, int64_t row_pitch)
+{
+    const int64_t m = blockIdx.y;
+    adj_mask(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, count, inv_nsub);
 }
 
 struct AdjReduceArgs {
@@ -90,11 +132,25 @@ struct AdjReduceArgs {
     Div32 nsub;
 };
 
+// Member blockIdx.z: its tapes at qtape_pitch / mtape_pitch, its lateral rows at lat_pitch, its [splits][4][n] of the slab at slab_pitch.
+struct AdjReduceEnsArgs : AdjReduceArgs {
+    int64_t qtape_pitch, mtape_pitch, lat_pitch, slab_pitch;
+};
+template <bool ENS> using AdjReduceArgsOf = typename std::conditional<ENS, AdjReduceEnsArgs, AdjReduceArgs>::type;
+struct AdjReduceMember { int64_t q, m, lat, slab; };
+__device__ __forceinline__ AdjReduceMember member_offsets(const AdjReduceArgs &) { return {0, 0, 0, 0}; }
+__device__ __forceinline__ AdjReduceMember member_offsets(const AdjReduceEnsArgs &e)
+{
+    const int64_t m = blockIdx.z;
+    return {m * e.qtape_pitch, m * e.mtape_pitch, m * e.lat_pitch, m * e.slab_pitch};
+}
+
 // Partial sums over one range of sub-steps per column (blockIdx.y = range): the four coefficient gradients
 //   sum_s mu[s,i] * {sum_u q[s,u], sum_u q[s-1,u], q[s-1,i], ql[t(s-1),i]}.
 // The ranges are merged in a fixed order by k_adj_merge: no atomics, repeated calls give the same bits.
-template <bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_adj_reduce(const AdjReduceArgs a)
+// ENS: the member-batched form, member m's sums in slab [m][range][4][n].
+template <bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_adj_reduce(const AdjReduceArgsOf<ENS> a)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= a.n) return;
@@ -102,11 +158,12 @@ __global__ __launch_bounds__(kBlock) void k_adj_reduce(const AdjReduceArgs a)
     const int32_t lag = a.lag[p] & kLagMask;
     const int32_t u0 = a.child_ptr[p], u1 = a.child_ptr[p + 1];
     const int64_t s0 = (int64_t)blockIdx.y * a.steps_per_split, s1 = min(a.total_substeps, s0 + a.steps_per_split);
+    const AdjReduceMember mo = member_offsets(a);
     double g1 = 0.0, g2 = 0.0, g3 = 0.0, g4 = 0.0;
     for (int64_t ts = s0; ts < s1; ++ts) {
         // forward tick of this sub-step: ts + lag; its inputs were written one (new upstream, own old) and two (old upstream) ticks before
-        const double *q1 = a.qtape + (ts + lag + 1) * n, *q2 = q1 - n;
-        const double mu = a.mtape[(a.total_substeps - 1 - ts + a.dmax - lag) * n + p];
+        const double *q1 = a.qtape + (ENS ? (ts + lag + 1) * n + mo.q : (ts + lag + 1) * n), *q2 = q1 - n;
+        const double mu = a.mtape[ENS ? (a.total_substeps - 1 - ts + a.dmax - lag) * n + p + mo.m : (a.total_substeps - 1 - ts + a.dmax - lag) * n + p];
         double s_new = 0.0, s_old = 0.0;
         for (int32_t u = u0; u < u1; ++u) { s_new += q1[u]; s_old += q2[u]; }
         g1 = __builtin_fma(mu, s_new, g1);
@@ -116,18 +173,18 @@ __global__ __launch_bounds__(kBlock) void k_adj_reduce(const AdjReduceArgs a)
             uint32_t t;
             if (SINGLE_SUBSTEP) t = (uint32_t)ts;
             else { uint32_t rem; t = a.nsub.div((uint32_t)ts, rem); }
-            g4 = __builtin_fma(mu, a.lat[(int64_t)t * n + p], g4);
+            g4 = __builtin_fma(mu, a.lat[ENS ? (int64_t)t * n + p + mo.lat : (int64_t)t * n + p], g4);
         }
     }
-    double *out = a.slab + (int64_t)blockIdx.y * 4 * n + p;
+    double *out = a.slab + (ENS ? (int64_t)blockIdx.y * 4 * n + p + mo.slab : (int64_t)blockIdx.y * 4 * n + p);
     out[0] = g1; out[n] = g2; out[2 * n] = g3; out[3 * n] = g4;
 }
 
 // Merge of the ranges in order, scattered to params order; dL/dq0[i] = c3[i] mu[1,i] + c2[d] mu[1,d].
-__global__ __launch_bounds__(kBlock) void k_adj_merge(const double *slab, int64_t splits, const double *mtape, const int32_t *lag,
-                                                      const int32_t *down, const int32_t *perm, const double *c2, const double *c3,
-                                                      int64_t n, int64_t total_substeps, int32_t dmax, int has_lateral,
-                                                      double *grad_coef, double *grad_q0)
+__device__ __forceinline__ void adj_merge(const double *slab, int64_t splits, const double *mtape, const int32_t *lag,
+                                          const int32_t *down, const int32_t *perm, const double *c2, const double *c3,
+                                          int64_t n, int64_t total_substeps, int32_t dmax, int has_lateral,
+                                          double *grad_coef, double *grad_q0)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
@@ -147,11 +204,30 @@ __global__ __launch_bounds__(kBlock) void k_adj_merge(const double *slab, int64_
         grad_q0[i] = v;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_adj_merge(const double *slab, int64_t splits, const double *mtape, const int32_t *lag,
+                                                      const int32_t *down, const int32_t *perm, const double *c2, const double *c3,
+                                                      int64_t n, int64_t total_substeps, int32_t dmax, int has_lateral,
+                                                      double *grad_coef, double *grad_q0)
+{
+    adj_merge(slab, splits, mtape, lag, down, perm, c2, c3, n, total_substeps, dmax, has_lateral, grad_coef, grad_q0);
+}
+// Member blockIdx.y writes its own dL/dq0 row (grad_q0[members][n]) from its mu tape.  The coefficient gradients are one sum over
+// the members: the slab [members][splits][4][n] is contiguous (adjoint_layout), so the blocks of member 0 fold all members x splits
+// ranges in storage order -- members ascending, within a member the ranges in order -- and the others leave grad_coef alone.
+__global__ __launch_bounds__(kBlock) void k_adj_merge_batch(const double *slab, int64_t splits, int64_t members, const double *mtape,
+                                                            const int32_t *lag, const int32_t *down, const int32_t *perm, const double *c2,
+                                                            const double *c3, int64_t n, int64_t total_substeps, int32_t dmax,
+                                                            int has_lateral, double *grad_coef, double *grad_q0, int64_t tape_pitch)
+{
+    const int64_t m = blockIdx.y;
+    adj_merge(slab, splits * members, mtape + m * tape_pitch, lag, down, perm, c2, c3, n, total_substeps, dmax, has_lateral,
+              m == 0 ? grad_coef : nullptr, grad_q0 ? grad_q0 + m * n : nullptr);
+}
 
 // dL/dql[t, p] = c4dt[p] * sum of mu over the sub-steps of row t, engine order (the rows then go to params order through the
 // tiled permutation).  Row t's sub-steps ran at consecutive reverse ticks, latest first.
-__global__ __launch_bounds__(kBlock) void k_adj_rows(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
-                                                     int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
+__device__ __forceinline__ void adj_rows(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
+                                         int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
@@ -162,6 +238,18 @@ __global__ __launch_bounds__(kBlock) void k_adj_rows(double *dst, const double *
         for (int64_t k = 0; k < nsub; ++k) m += mtape[(base - (t * nsub + k)) * n + p];
         dst[t * n + p] = c * m;
     }
+}
+__global__ __launch_bounds__(kBlock) void k_adj_rows(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
+                                                     int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
+{
+    adj_rows(dst, mtape, lag, c4, n, T, nsub, total_substeps, dmax);
+}
+// member blockIdx.z (y walks the rows): its gradient rows at dst_pitch, its mu tape at tape_pitch
+__global__ __launch_bounds__(kBlock) void k_adj_rows_batch(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
+                                                           int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax, int64_t dst_pitch,
+                                                           int64_t tape_pitch)
+{
+    adj_rows(dst + (int64_t)blockIdx.z * dst_pitch, mtape + (int64_t)blockIdx.z * tape_pitch, lag, c4, n, T, nsub, total_substeps, dmax);
 }
 
 }  // namespace

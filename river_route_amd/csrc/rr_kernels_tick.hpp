@@ -29,17 +29,34 @@ struct TickArgs {
     double inv_nsub;
 };
 
+// The member-batched tick (ENS; the tape replay of a batched adjoint call, rr_adjoint.hpp): member blockIdx.y shares every plan array
+// and has its three state rows tape_pitch doubles, its lateral rows in_pitch and its running sum and discharge row scratch_pitch
+// doubles behind the first member's.  64-bit element counts: member x rows x n passes 2^32 at 1M reaches.  Indices are formed as
+// (ENS ? index + offset : index): with a constant condition only the live arm is emitted, so k_tick<.., false> is the code it was.
+struct TickEnsArgs : TickArgs {
+    int64_t tape_pitch, in_pitch, scratch_pitch;
+};
+template <bool ENS> using TickArgsOf = typename std::conditional<ENS, TickEnsArgs, TickArgs>::type;
+__device__ __forceinline__ int64_t member_tape0(const TickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_tape0(const TickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
+__device__ __forceinline__ int64_t member_in0(const TickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_in0(const TickEnsArgs &e) { return (int64_t)blockIdx.y * e.in_pitch; }
+__device__ __forceinline__ int64_t member_scratch0(const TickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_scratch0(const TickEnsArgs &e) { return (int64_t)blockIdx.y * e.scratch_pitch; }
+
 // One routing tick for Muskingum / RapidMuskingum.  One reach per lane; positions are lag-ordered so a
 // wave reads contiguous spans of every array, including the upstream values (rr_plan.hpp).
-template <bool HAS_LATERAL, bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_tick(const TickArgs a)
+// ENS: the member-batched form (TickEnsArgs); it has no boundary reaches (the adjoint refuses partitioned plans).
+template <bool HAS_LATERAL, bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_tick(const TickArgsOf<ENS> a)
 {
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (p >= a.p_hi) return;
     const int32_t lag_bits = a.lag[p];
     const int32_t ts = (int32_t)a.tau - (lag_bits & kLagMask);
     if (ts < 0 || ts >= (int32_t)a.total_substeps) return;
-    if (lag_bits & kGhostBit) {   // boundary inflow: the value another GPU computed for this sub-step
+    const int64_t mt = member_tape0(a), mi = member_in0(a), ms = member_scratch0(a);
+    if (!ENS && (lag_bits & kGhostBit)) {   // boundary inflow: the value another GPU computed for this sub-step
         a.xc[p] = a.ghost[(int64_t)ts * a.n_ghost + a.bidx[p]];
         return;
     }
@@ -53,28 +70,28 @@ __global__ __launch_bounds__(kBlock) void k_tick(const TickArgs a)
         // one upstream weight per reach (what the reference's callers produce): the arithmetic of k_tile, operation for
         // operation, so a call routed here and one routed there agree bit for bit (split run == joint run)
         double s_new = 0.0, s_old = 0.0;
-        for (int32_t u = u0; u < u1; ++u) { s_new += a.xa[u]; s_old += a.xb[u]; }
-        const double lat = HAS_LATERAL ? a.c4[p] * a.in[(int64_t)a.in_rows.mod(t) * a.in_ld + p] : 0.0;
-        r = __builtin_fma(a.c1row[p], s_new, __builtin_fma(a.c2[p], s_old, __builtin_fma(a.c3[p], a.xa[p], lat)));
+        for (int32_t u = u0; u < u1; ++u) { s_new += a.xa[ENS ? u + mt : u]; s_old += a.xb[ENS ? u + mt : u]; }
+        const double lat = HAS_LATERAL ? a.c4[p] * a.in[ENS ? (int64_t)a.in_rows.mod(t) * a.in_ld + p + mi : (int64_t)a.in_rows.mod(t) * a.in_ld + p] : 0.0;
+        r = __builtin_fma(a.c1row[p], s_new, __builtin_fma(a.c2[p], s_old, __builtin_fma(a.c3[p], a.xa[ENS ? p + mt : p], lat)));
     } else {
-        r = a.c3[p] * a.xa[p];
-        if (HAS_LATERAL) r += a.c4[p] * a.in[(int64_t)a.in_rows.mod(t) * a.in_ld + p];
+        r = a.c3[p] * a.xa[ENS ? p + mt : p];
+        if (HAS_LATERAL) r += a.c4[p] * a.in[ENS ? (int64_t)a.in_rows.mod(t) * a.in_ld + p + mi : (int64_t)a.in_rows.mod(t) * a.in_ld + p];
         const double c2 = a.c2[p];
-        for (int32_t u = u0; u < u1; ++u) r += c2 * a.xb[u];
-        for (int32_t u = u0; u < u1; ++u) r += a.w[u] * a.xa[u];
+        for (int32_t u = u0; u < u1; ++u) r += c2 * a.xb[ENS ? u + mt : u];
+        for (int32_t u = u0; u < u1; ++u) r += a.w[u] * a.xa[ENS ? u + mt : u];
     }
-    if (lag_bits & kExportBit) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = r;
-    a.xc[p] = r;
+    if (!ENS && (lag_bits & kExportBit)) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = r;
+    a.xc[ENS ? p + mt : p] = r;
 
     if (SINGLE_SUBSTEP) {
-        a.out[(int64_t)a.out_rows.mod(t) * a.out_ld + p] = r > 0.0 ? r : 0.0;
+        a.out[ENS ? (int64_t)a.out_rows.mod(t) * a.out_ld + p + ms : (int64_t)a.out_rows.mod(t) * a.out_ld + p] = r > 0.0 ? r : 0.0;
     } else {
-        const double acc = (s == 0 ? 0.0 : a.isum[p]) + r;
+        const double acc = (s == 0 ? 0.0 : a.isum[ENS ? p + ms : p]) + r;
         if (s + 1 == a.nsub.d) {
             const double v = acc * a.inv_nsub;
-            a.out[(int64_t)a.out_rows.mod(t) * a.out_ld + p] = v > 0.0 ? v : 0.0;
+            a.out[ENS ? (int64_t)a.out_rows.mod(t) * a.out_ld + p + ms : (int64_t)a.out_rows.mod(t) * a.out_ld + p] = v > 0.0 ? v : 0.0;
         } else {
-            a.isum[p] = acc;
+            a.isum[ENS ? p + ms : p] = acc;
         }
     }
 }

@@ -243,6 +243,22 @@ class Plan:
                                               ptr(grad_qfinal), ptr(grad_lateral), ptr(grad_q0), ptr(grad_coef), ptr(work),
                                               int(work_bytes), int(T), int(num_substeps), stream))
 
+    def rapid_adjoint_batch_work_bytes(self, members: int, T: int, num_substeps: int = 1) -> int:
+        """rr_rapid_adjoint_batch_work_bytes: bytes of work memory rapid_adjoint_batch_dev needs for `members` series of T rows x
+        num_substeps sub-steps (readies the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_rapid_adjoint_batch_work_bytes(self._h, int(members), int(T), int(num_substeps), C.byref(out)))
+        return int(out.value)
+
+    def rapid_adjoint_batch_dev(self, members, q0, q0_pitch, lateral, lat_rows, lat_pitch, discharge, grad_out, out_pitch, grad_qfinal,
+                                grad_lateral, grad_q0, grad_coef, work, work_bytes, T, num_substeps, stream=None) -> None:
+        """rr_rapid_adjoint_batch_dev (enqueue only): rapid_adjoint_dev for `members` series at once, member m's arrays m pitches
+        (in values) behind the first's; grad_qfinal and grad_q0 are [members, n], grad_coef[4, n] is the sum over the members."""
+        check(_lib.lib().rr_rapid_adjoint_batch_dev(self._h, int(members), ptr(q0), int(q0_pitch), ptr(lateral), int(lat_rows), int(lat_pitch),
+                                                    ptr(discharge), ptr(grad_out), int(out_pitch), ptr(grad_qfinal), ptr(grad_lateral),
+                                                    ptr(grad_q0), ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps),
+                                                    stream))
+
     # -- adjoint of unit_route_dev (rr.grad) --
     def unit_adjoint_work_bytes(self, T: int, num_substeps: int = 1) -> int:
         """rr_unit_adjoint_work_bytes: bytes of work memory unit_adjoint_dev needs for T rows x num_substeps sub-steps (readies

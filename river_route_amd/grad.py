@@ -18,8 +18,14 @@ unit_muskingum, the two chained as the router chains them, in windows if asked:
 
     Q, q_ch, q_full, uh_state = rr.grad.unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state0, k, x, 900.0, 3600.0)
 
-Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, ensembles, partitioned plans and plans
-with set_unit_weights edge data are refused.
+Several forcing series on one network and one coefficient set (a mini-batch of windows, the members of a forcing ensemble) go
+through rapid_route_batch: the forward is rapid_route's, member by member, and the backward is one
+rr_rapid_adjoint_batch_dev call whose two sweeps launch once per tick for all members together; k and x get the sum over the members:
+
+    Q, q_final = rr.grad.rapid_route_batch(plan, q0, qlateral, k, x, 900.0, 3600.0)      # qlateral[B, T, n] -> Q[B, T, n], q_final[B, n]
+
+Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, partitioned plans and plans with
+set_unit_weights edge data are refused, and so is a 3-D qlateral everywhere but in rapid_route_batch.
 
 The loss a calibration minimises is a skill score at gauges, and `scores` is rr.metrics.scores with an autograd graph (DESIGN.md
 section 12c): the same five values, bit for bit, and a backward pass that writes dL/dQ in one streaming pass on the GPU:
@@ -35,7 +41,7 @@ import torch
 from . import engine, metrics
 from .engine import Plan
 
-__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
+__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
            'unit_muskingum', 'Scores', 'scores']
 
 
@@ -179,15 +185,15 @@ def _check_device(plan, pairs):
             raise ValueError(f"{name} must be on cuda:{plan.device}, the plan's device (it is on {t.device})")
 
 
-def _in_windows(T, rows_per_window, state, route):
+def _in_windows(T, rows_per_window, state, route, axis=0):
     """Rows [0, T) in windows of rows_per_window rows (None: one window), chained through the state tuple: route(t0, t1, *state) returns the
-    window's discharge rows followed by its final state.  Returns (discharge[T, n], *final state)."""
+    window's discharge rows followed by its final state.  Returns (discharge[T, n], *final state); `axis` is the discharge's time axis."""
     R = T if rows_per_window is None else min(T, int(rows_per_window))
     parts = []
     for t0 in range(0, T, R):
         d, *state = route(t0, min(T, t0 + R), *state)
         parts.append(d)
-    return (parts[0] if len(parts) == 1 else torch.cat(parts, 0)), *state
+    return (parts[0] if len(parts) == 1 else torch.cat(parts, axis)), *state
 
 
 def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None):
@@ -211,6 +217,120 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
     c4dt = (c1 + c2) / float(dt_runoff)
     return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRoute.apply(
         plan, nsub, t1 - t0, q, None if qlateral is None else qlateral[t0:t1], c1, c2, c3, c4dt))
+
+
+# ---- RapidMuskingum, several series at once ----
+
+kMaxMembers = 65535      # members of one rr_rapid_adjoint_batch_dev call
+
+
+class RapidRouteBatch(torch.autograd.Function):
+    """(discharge[B, T, n], q_final[B, n]) = RapidRoute for B series at once: q0[B, n] (rows of n adjacent values, any pitch: an
+    expanded (n,) q0 has pitch 0), qlateral[B, T, n] or None, one set of coefficients.  Forward: RapidRoute's call, member by member,
+    so every member's values are RapidRoute's bits.  Backward: rr_rapid_adjoint_batch_dev on groups of `per_sweep` members (None: all) in
+    ascending order, the groups' coefficient gradients added in that order."""
+
+    @staticmethod
+    def forward(ctx, plan, nsub, rows, per_sweep, q0, qlateral, c1, c2, c3, c4dt):
+        dev = plan.device
+        B, T = int(q0.shape[0]), int(rows)
+        _set_coeffs(plan, c1, c2, c3, c4dt if qlateral is not None else None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        q = q0.detach().clone(memory_format=torch.contiguous_format)
+        discharge = torch.empty((B, T, plan.n), dtype=torch.float64, device=q0.device)
+        ql = None if qlateral is None else qlateral.detach()
+        for m in range(B):
+            if ql is not None:
+                plan.rapid_route_dev(q[m], ql[m], T, discharge[m], T, T, nsub, stream)
+            else:
+                plan.muskingum_route_dev(q[m], discharge[m], T, T, nsub, stream)
+        ctx.plan, ctx.nsub, ctx.rows, ctx.per_sweep = plan, int(nsub), T, per_sweep
+        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach(), None if c4dt is None else c4dt.detach())
+        ctx.save_for_backward(q0, qlateral, discharge)
+        ctx.set_materialize_grads(False)
+        return discharge, q
+
+    @staticmethod
+    def backward(ctx, grad_discharge, grad_qfinal):
+        plan, nsub, T = ctx.plan, ctx.nsub, ctx.rows
+        q0, qlateral, discharge = ctx.saved_tensors
+        need = ctx.needs_input_grad      # plan, nsub, rows, per_sweep, q0, qlateral, c1, c2, c3, c4dt
+        want_q0, want_ql = need[4], need[5] and qlateral is not None
+        want_coef = any(need[6:9]) or (need[9] and qlateral is not None)
+        if (grad_discharge is None and grad_qfinal is None) or not (want_q0 or want_ql or want_coef):
+            return (None,) * 10
+        B, n = int(q0.shape[0]), plan.n
+        _set_coeffs(plan, *ctx.coeffs[:3], ctx.coeffs[3] if qlateral is not None else None, plan.device)
+        stream = torch.cuda.current_stream(plan.device).cuda_stream
+        f64 = dict(dtype=torch.float64, device=discharge.device)
+        g_out = None if grad_discharge is None else grad_discharge.to(**f64).contiguous()
+        g_fin = None if grad_qfinal is None else grad_qfinal.to(**f64).contiguous()
+        g_q0 = torch.empty((B, n), **f64) if want_q0 else None
+        g_ql = torch.empty((B, T, n), **f64) if want_ql else None
+        ql = None if qlateral is None else qlateral.detach()
+        q0_pitch = int(q0.stride(0)) if B > 1 else n
+        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
+        nbytes = max(plan.rapid_adjoint_batch_work_bytes(g, T, nsub) for g in {group, B % group or group})
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
+        g_coef = None
+
+        def members(t, m0, m1):
+            return None if t is None else t[m0:m1]
+
+        for m0 in range(0, B, group):
+            m1 = min(B, m0 + group)
+            part = torch.empty((4, n), **f64) if want_coef else None
+            plan.rapid_adjoint_batch_dev(m1 - m0, q0.data_ptr() + 8 * m0 * q0_pitch, q0_pitch, members(ql, m0, m1), T, T * n,
+                                         discharge[m0:m1], members(g_out, m0, m1), T * n, members(g_fin, m0, m1), members(g_ql, m0, m1),
+                                         members(g_q0, m0, m1), part, work, nbytes, T, nsub, stream)
+            if want_coef:
+                g_coef = part if g_coef is None else g_coef + part
+        coef = [g_coef[j].to(c.device) if want_coef and need[6 + j] and c is not None else None for j, c in enumerate(ctx.coeffs)]
+        return (None, None, None, None, g_q0, g_ql, *coef)
+
+
+def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, members_per_sweep=None):
+    """rapid_route for B forcing series on one network and one set of coefficients: (discharge[B, T, n], q_final[B, n]).
+
+    qlateral[B, T, n] is a contiguous float64 tensor on the plan's GPU (None routes channel-only: then `rows` gives T and q0 gives B);
+    q0 is (B, n), or (n,) for one initial state shared by every member, whose gradient is then the sum over the members; k and x are
+    as in rapid_route and serve all members.  Every member's discharge and q_final are the bits rapid_route gives for that member
+    alone (the forward is the same call, member by member), and so are its dL/dqlateral and dL/dq0; k and x get the sum over the
+    members.  The backward pass is one rr_rapid_adjoint_batch_dev call: its tick launches do not grow with B.  members_per_sweep (None:
+    all members in one sweep) bounds the tape memory: the backward then runs groups of that many members in ascending order and adds
+    the groups' coefficient gradients in that order.  rows_per_window chains windows through q_final -> q0 as rapid_route does.
+    Every argument is checked before the GPU is touched."""
+    nsub = _check_call(plan, 'n', (), k, x, dt_routing, dt_runoff, rows_per_window)
+    n = plan.n
+    if members_per_sweep is not None and int(members_per_sweep) < 1:
+        raise ValueError('members_per_sweep must be >= 1')
+    if not isinstance(q0, torch.Tensor) or q0.ndim not in (1, 2):
+        raise ValueError('q0 must be a (B, n) tensor, or (n,) for one state shared by every member')
+    if qlateral is None:
+        if q0.ndim != 2:
+            raise ValueError('channel-only routing (qlateral=None) takes its member count from q0, which must be (B, n)')
+        if rows is None or int(rows) < 1:
+            raise ValueError('channel-only routing (qlateral=None) needs rows >= 1')
+        B, T = int(q0.shape[0]), int(rows)
+    else:
+        if not isinstance(qlateral, torch.Tensor) or qlateral.ndim != 3:
+            raise ValueError('qlateral must be a 3-D (B, T, n) tensor (one series: rapid_route)')
+        B, T = int(qlateral.shape[0]), int(qlateral.shape[1])
+        if T < 1:
+            raise ValueError('qlateral has no rows')
+        _check_tensor(qlateral, 'qlateral', (B, T, n))
+    if B < 1:
+        raise ValueError('no members')
+    _check_tensor(q0, 'q0', (B, n) if q0.ndim == 2 else (n,))
+    _check_device(plan, ((q0, 'q0'), (qlateral, 'qlateral')))
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    c4dt = (c1 + c2) / float(dt_runoff)
+    if q0.ndim == 1:
+        q0 = q0.unsqueeze(0).expand(B, n)      # autograd sums the members' rows into the one q0
+    whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
+    return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRouteBatch.apply(
+        plan, nsub, t1 - t0, members_per_sweep, q, None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(),
+        c1, c2, c3, c4dt), axis=1)
 
 
 # ---- UnitMuskingum ----
