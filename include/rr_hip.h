@@ -14,7 +14,8 @@
  *   rr_uh_convolve      <- UnitHydrograph.convolve  river_route/uhkernels/UnitHydrograph.py:77-107
  *                          (call site river_route/routers/UnitMuskingum.py:75)
  *   rr_unit_adjoint_dev <- the gradient of a loss through unit_route (same lines), rr_uh_adjoint_dev <- through
- *                          UnitHydrograph.convolve (same lines); rr_rapid_adjoint_dev <- through rapid_route
+ *                          UnitHydrograph.convolve (same lines); rr_rapid_adjoint_dev <- through rapid_route;
+ *                          rr_rapid_adjoint_batch_dev, rr_unit_adjoint_batch_dev <- through several such calls at once
  *   rr_plan_create      <- the CSC structure the routers take from tools.adjacency_matrix
  *                          (river_route/tools.py:75-109; river_route/routers/Muskingum.py:189-192)
  *   rr_plan_set_coeffs  <- the coefficient vectors of Muskingum._set_muskingum_coefficients
@@ -480,6 +481,31 @@ int rr_unit_adjoint_dev(rr_plan *plan, const double *q_ch0, const double *q_full
                         const double *discharge, const double *grad_out, const double *grad_qch_final, const double *grad_qfull_final,
                         double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
                         int64_t T, int64_t nsub, void *stream);
+
+/* ---- the same for several forcing series at once ----
+ * `members` rr_unit_route_dev calls (unit_route, river_route/routers/_numba_kernels.py:88-171, call site
+ * river_route/routers/UnitMuskingum.py:82-92) on one plan with one coefficient set, their gradients from one pair of sweeps: every
+ * replay and reverse tick is one launch over (positions, members), so the tick launches number 2 (S + depth - 1) whatever the member
+ * count.  Member m's arrays lie m pitches (in doubles) behind member 0's:
+ *   q_ch0, q_full0           at state_pitch (0: one pair of states[n_inner] shared by every member; otherwise >= n_inner);
+ *   lateral, grad_lateral    at lat_pitch (>= T*n; lat_rows >= T rows per member);
+ *   discharge, grad_out      at out_pitch (>= T*n);
+ *   grad_qch_final, grad_qfull_final, grad_qch0, grad_qfull0    [members*n_inner], dense;
+ *   grad_coef[3*n]           the SUM over the members, folded in ascending member order (within a member its sub-step ranges in order).
+ * NULL arguments mean what they mean in rr_unit_adjoint_dev, for every member alike.  Each member's grad_lateral, grad_qch0 and
+ * grad_qfull0 are the bits rr_unit_adjoint_dev gives for that member alone; with members == 1 so is grad_coef.
+ * Work memory (rr_unit_adjoint_batch_work_bytes; caller-provided, the call allocates nothing and only enqueues on `stream`):
+ *   8 n (members (2 S + 2 T + 2 depth + 3 splits + 6) + min(T, 16)) bytes, splits = min(S, ceil(2048 / (members ceil(n / 256)))):
+ *   the single call's tapes, rows, partial sums and six scratch rows once per member, the permutation's rows once.
+ * rr_unit_adjoint_batch_work_bytes readies the plan as rr_unit_adjoint_work_bytes does.  No atomics.  Refused: what
+ * rr_unit_adjoint_dev refuses, then RR_E_INVALID for members < 1 or > 65535, for a pitch shorter than one member's rows or states,
+ * and for too little work memory. */
+int rr_unit_adjoint_batch_work_bytes(rr_plan *plan, int64_t members, int64_t T, int64_t nsub, int64_t *bytes);
+int rr_unit_adjoint_batch_dev(rr_plan *plan, int64_t members, const double *q_ch0, const double *q_full0, int64_t state_pitch,
+                              const double *lateral, int64_t lat_rows, int64_t lat_pitch, const double *discharge, const double *grad_out,
+                              int64_t out_pitch, const double *grad_qch_final, const double *grad_qfull_final, double *grad_lateral,
+                              double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes, int64_t T,
+                              int64_t nsub, void *stream);
 
 /* ---- adjoint of the unit-hydrograph convolution ----
  * The gradient through one rr_uh_convolve_dev call (UnitHydrograph.convolve, river_route/uhkernels/UnitHydrograph.py:93-107):

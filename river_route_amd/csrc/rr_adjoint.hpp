@@ -1,4 +1,4 @@
-// rr_adjoint.hpp -- the host side of the routing adjoints (rr_rapid_adjoint_*, rr_unit_adjoint_*; DESIGN.md section 12): one driver
+// rr_adjoint.hpp -- the host side of the routing adjoints (rr_rapid_adjoint_*, rr_unit_adjoint_*; DESIGN.md section 12, 12d, 12e): one driver
 // (refusals, work-memory layout, forward replay, reverse sweep) and, per router, the kernels plugged into it and a few checks of its own.
 // Part of the one translation unit rr_engine.hip builds (included from there, after rr_exec.hpp; not a stand-alone header).
 #pragma once
@@ -16,6 +16,7 @@ struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; bool ba
 constexpr AdjointKind kRapidAdjoint{"rr_rapid_adjoint_work_bytes", 4, 2};
 constexpr AdjointKind kRapidAdjointBatch{"rr_rapid_adjoint_batch_work_bytes", 4, 2, true};
 constexpr AdjointKind kUnitAdjoint{"rr_unit_adjoint_work_bytes", 3, 6};
+constexpr AdjointKind kUnitAdjointBatch{"rr_unit_adjoint_batch_work_bytes", 3, 6, true};
 
 // The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
 // (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
@@ -80,9 +81,10 @@ struct AdjointCall {
     void *work; int64_t work_bytes;
     int64_t T, nsub;
     hipStream_t st;
-    // a batched call (rr_rapid_adjoint_batch_*): members, and the doubles from one member's q0 (0: one q0 for all), lateral /
-    // grad_lateral rows and discharge / grad_out rows to the next's.  The single-member entry points leave these as they are.
-    int64_t members = 1, q0_pitch = 0, lat_pitch = 0, out_pitch = 0;
+    // a batched call (rr_rapid_adjoint_batch_*, rr_unit_adjoint_batch_*): members, and the doubles from one member's q0 (0: one q0
+    // for all), lateral / grad_lateral rows and discharge / grad_out rows to the next's; for UnitMuskingum, whose states have n_inner
+    // values, state_pitch instead of q0_pitch (0: one q_ch0 and one q_full0 for all).  The single-member entry points leave these as they are.
+    int64_t members = 1, q0_pitch = 0, lat_pitch = 0, out_pitch = 0, state_pitch = 0;
     // set by adjoint_check
     int64_t n, S, dmax, ticks;
     bool one;                                                       // nsub == 1: the kernels' SINGLE_SUBSTEP forms
@@ -102,8 +104,9 @@ struct AdjointCall {
 };
 
 // A check that is an entry point's own: after which shared ones it is tested (the plan's boundary check, the sizes, the lateral rows,
-// grad_out), whether it is hit, its status and text.  kAdjNothing is no refusal: no gradient is asked for, the call returns RR_OK.
-enum class AdjOwn { Plan, Wanted, Lateral, GradOut };
+// grad_out, the member pitches), whether it is hit, its status and text.  kAdjNothing is no refusal: no gradient is asked for, the call
+// returns RR_OK.
+enum class AdjOwn { Plan, Wanted, Lateral, GradOut, Pitch };
 constexpr int kAdjNothing = 1;
 struct OwnCheck { AdjOwn at; bool hit; int code; const char *what; };
 
@@ -153,6 +156,7 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     if (!members_ok()) return no(RR_E_INVALID, ": need 1 <= members <= 65535");
     if (K.batch && ((c.q0_pitch != 0 && c.q0_pitch < n) || (c.lateral && c.lat_pitch < T * n) || ((c.discharge || c.grad_out) && c.out_pitch < T * n)))
         return no(RR_E_INVALID, ": a member pitch shorter than one member's rows (q0_pitch: 0 or >= n; lat_pitch, out_pitch >= T * n)");
+    if (int rc = own(AdjOwn::Pitch)) return rc;
     const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K, c.members);
     const int64_t need = L.total * (int64_t)sizeof(double);
     if (!c.work || c.work_bytes < need)
@@ -320,67 +324,128 @@ int rapid_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const d
 
 // ---- UnitMuskingum ----
 
-int unit_adjoint(const char *who, AdjointCall &c, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
-                 const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef)
+// What a checked call enqueues, as rapid_adjoint_enqueue: ENS is a batched call (rr_unit_adjoint_batch_dev) on grids with a member
+// dimension; otherwise the single-member kernels, launched as ever.  ni: the plan's inner reaches (0: no state and no tick).
+template <bool ENS>
+void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
+                          const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef)
 {
     rr_plan *const P = c.P;
     const double *const lateral = c.lateral, *const discharge = c.discharge, *const grad_out = c.grad_out;
-    const int64_t T = c.T, nsub = c.nsub;
+    const int64_t T = c.T, nsub = c.nsub, n = c.n, S = c.S;
     const hipStream_t st = c.st;
+    const AdjointLayout &L = c.L;
+    const unsigned M = (unsigned)c.members;
+    const int64_t lat_pitch = ENS ? c.lat_pitch : 0, out_pitch = ENS ? c.out_pitch : 0;
+    double *const qch = c.scratch + 2 * n, *const qch0e = qch + n, *const gcf = qch0e + n, *const gff = gcf + n;      // member m's: m scratch pitches on
+    const bool tape = grad_coef && ni > 0;
+    const unsigned col_blocks = (unsigned)((n + kBlock - 1) / kBlock), row_blocks = (unsigned)std::min<int64_t>(T, 65535);
+    // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
+    if (grad_out) {
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_mask_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
+                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub, L.mtape_pitch, out_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_mask_unit, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
+                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
+        c.rows_between(0, c.mtape, c.egrad, L.mtape_pitch, L.row_pitch);
+    }
+    if (ni > 0 && (tape || grad_qch_final || grad_qfull_final)) {
+        if constexpr (ENS) {
+            dim3 g = grid1(ni);
+            g.y = M;
+            hipLaunchKernelGGL(k_adj_unit_in_batch, g, dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff,
+                               grad_qch_final, grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni,
+                               L.qtape_pitch, L.scratch_pitch, c.state_pitch);
+        } else
+            hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff,
+                               grad_qch_final, grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
+    }
+    if (tape) {      // k_tick_unit on its one-weight branch
+        c.rows_between(0, lateral, c.elat, lat_pitch, L.row_pitch);
+        UnitTickArgsOf<ENS> ua{};
+        ua.hw_children = P->d_hwc; ua.qch = qch; ua.a2 = nullptr; ua.c1own = nullptr; ua.zc = nullptr; ua.za = nullptr;
+        if constexpr (ENS) { ua.tape_pitch = L.qtape_pitch; ua.in_pitch = L.row_pitch; ua.scratch_pitch = L.scratch_pitch; }
+        adjoint_replay(c, ua.t, [&](dim3 g) {
+            g.y = M;
+            hipLaunchKernelGGL((c.one ? k_tick_unit<true, ENS> : k_tick_unit<false, ENS>), g, dim3(kBlock), 0, st, ua);
+        });
+    }
+    if (ni > 0) {      // with no inner reach there is no state and no tick
+        UnitAdjTickArgsOf<ENS> a{};
+        a.child_ptr = P->d_child_ptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
+        if constexpr (ENS) { a.tape_pitch = L.mtape_pitch; a.g_pitch = L.row_pitch; a.gf_pitch = L.scratch_pitch; }
+        adjoint_reverse(c, a, [&](dim3 g) {
+            g.y = M;
+            hipLaunchKernelGGL((c.one ? k_adj_tick_unit<true, ENS> : k_adj_tick_unit<false, ENS>), g, dim3(kBlock), 0, st, a);
+        });
+    }
+    if (tape) {
+        UnitAdjReduceArgsOf<ENS> r{};
+        adjoint_reduce_args(c, r);
+        r.hw_children = P->d_hwc; r.qch0 = qch0e;
+        if constexpr (ENS) {
+            r.qtape_pitch = L.qtape_pitch; r.mtape_pitch = L.mtape_pitch; r.lat_pitch = L.row_pitch; r.qch0_pitch = L.scratch_pitch;
+            r.slab_pitch = L.slab_pitch;
+        }
+        hipLaunchKernelGGL((c.one ? k_adj_reduce_unit<true, ENS> : k_adj_reduce_unit<false, ENS>), c.reduce_grid(), dim3(kBlock), 0, st, r);
+    }
+    if (grad_coef) {
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_merge_unit_batch, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, c.members,
+                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_perm, n, grad_coef);
+        else
+            hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, (const int32_t *)P->d_child_ptr,
+                               (const int32_t *)P->d_perm, n, grad_coef);
+    }
+    if (grad_qch0 || grad_qfull0) {
+        if constexpr (ENS) {
+            dim3 g = grid1(ni);
+            g.y = M;
+            hipLaunchKernelGGL(k_adj_state_unit_batch, g, dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
+                               (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
+                               (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax, L.mtape_pitch);
+        } else
+            hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
+                               (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
+                               (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax);
+    }
+    if (grad_lateral) {
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_rows_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
+                               grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
+                               nsub, S, (int32_t)c.dmax, L.row_pitch, L.scratch_pitch, L.mtape_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_rows_unit, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
+                               grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
+                               nsub, S, (int32_t)c.dmax);
+        c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
+    }
+}
+
+int unit_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
+                 const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef)
+{
+    rr_plan *const P = c.P;
+    const double *const lateral = c.lateral;
     const int64_t ni = P ? (int64_t)P->h.inner_pos.size() : 0;
     if (ni == 0) { grad_qch0 = nullptr; grad_qfull0 = nullptr; }      // no inner reach: the state vectors are empty
-    const int rc = adjoint_check(who, kUnitAdjoint, c, nullptr, {
+    // grad_lateral lies at lat_pitch whether or not the lateral rows are given (they are needed with grad_coef only)
+    const bool rows_ok = c.T >= 1 && c.T <= 0x7FFFFFFFLL;
+    const int rc = adjoint_check(who, K, c, nullptr, {
         {AdjOwn::Plan, P && P->unit_general, RR_E_UNSUPPORTED,
          ": general edge data (rr_plan_set_unit_weights): the adjoint is that of the reference callers' unit weights"},
         {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_qch0 && !grad_qfull0 && !grad_coef)), kAdjNothing, ""},
         {AdjOwn::Wanted, grad_coef && ni > 0 && (!q_ch0 || !q_full0 || !lateral), RR_E_INVALID,
-         ": the coefficient gradients need q_ch0, q_full0 and the lateral rows"}});
+         ": the coefficient gradients need q_ch0, q_full0 and the lateral rows"},
+        {AdjOwn::Pitch, K.batch && P && rows_ok && (c.state_pitch < 0 || (c.state_pitch != 0 && c.state_pitch < ni) ||
+                                                    (grad_lateral && c.lat_pitch < c.T * P->h.n)), RR_E_INVALID,
+         ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch, out_pitch >= T * n)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-
-    const int64_t n = c.n, S = c.S;
-    double *const qch = c.scratch + 2 * n, *const qch0e = qch + n, *const gcf = qch0e + n, *const gff = gcf + n;
-    const bool tape = grad_coef && ni > 0;
-    const unsigned row_blocks = (unsigned)std::min<int64_t>(T, 65535);
-    // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
-        hipLaunchKernelGGL(k_adj_mask_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
-                           (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
-        c.rows_between(0, c.mtape, c.egrad);
-    }
-    if (ni > 0 && (tape || grad_qch_final || grad_qfull_final))
-        hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff, grad_qch_final,
-                           grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
-    if (tape) {      // k_tick_unit on its one-weight branch
-        c.rows_between(0, lateral, c.elat);
-        UnitTickArgs ua{};
-        ua.hw_children = P->d_hwc; ua.qch = qch; ua.a2 = nullptr; ua.c1own = nullptr; ua.zc = nullptr; ua.za = nullptr;
-        adjoint_replay(c, ua.t, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_tick_unit<true> : k_tick_unit<false>), g, dim3(kBlock), 0, st, ua); });
-    }
-    if (ni > 0) {      // with no inner reach there is no state and no tick
-        UnitAdjTickArgs a{};
-        a.child_ptr = P->d_child_ptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
-        adjoint_reverse(c, a, [&](dim3 g) { hipLaunchKernelGGL((c.one ? k_adj_tick_unit<true> : k_adj_tick_unit<false>), g, dim3(kBlock), 0, st, a); });
-    }
-    if (tape) {
-        UnitAdjReduceArgs r{};
-        adjoint_reduce_args(c, r);
-        r.hw_children = P->d_hwc; r.qch0 = qch0e;
-        hipLaunchKernelGGL((c.one ? k_adj_reduce_unit<true> : k_adj_reduce_unit<false>), c.reduce_grid(), dim3(kBlock), 0, st, r);
-    }
-    if (grad_coef)
-        hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, c.L.splits, (const int32_t *)P->d_child_ptr,
-                           (const int32_t *)P->d_perm, n, grad_coef);
-    if (grad_qch0 || grad_qfull0)
-        hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
-                           (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
-                           (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax);
-    if (grad_lateral) {
-        hipLaunchKernelGGL(k_adj_rows_unit, dim3((unsigned)((n + kBlock - 1) / kBlock), row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
-                           grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                           (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T, nsub,
-                           S, (int32_t)c.dmax);
-        c.rows_between(1, c.egrad, grad_lateral);
-    }
+    if (K.batch) unit_adjoint_enqueue<true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+    else unit_adjoint_enqueue<false>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

@@ -1137,7 +1137,23 @@ int rr_unit_adjoint_dev(rr_plan *P, const double *q_ch0, const double *q_full0, 
                         int64_t T, int64_t nsub, void *stream)
 {
     AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream};
-    return unit_adjoint("rr_unit_adjoint_dev", c, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+    return unit_adjoint("rr_unit_adjoint_dev", kUnitAdjoint, c, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0,
+                        grad_coef);
+}
+
+int rr_unit_adjoint_batch_work_bytes(rr_plan *P, int64_t members, int64_t T, int64_t nsub, int64_t *bytes)
+{
+    return adjoint_work_bytes(kUnitAdjointBatch, P, T, nsub, bytes, members);
+}
+
+int rr_unit_adjoint_batch_dev(rr_plan *P, int64_t members, const double *q_ch0, const double *q_full0, int64_t state_pitch, const double *lateral,
+                              int64_t lat_rows, int64_t lat_pitch, const double *discharge, const double *grad_out, int64_t out_pitch,
+                              const double *grad_qch_final, const double *grad_qfull_final, double *grad_lateral, double *grad_qch0,
+                              double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream)
+{
+    AdjointCall c{P, lateral, lat_rows, discharge, grad_out, work, work_bytes, T, nsub, (hipStream_t)stream, members, 0, lat_pitch, out_pitch, state_pitch};
+    return unit_adjoint("rr_unit_adjoint_batch_dev", kUnitAdjointBatch, c, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0,
+                        grad_qfull0, grad_coef);
 }
 
 // ---- adjoint of the unit-hydrograph convolution (rr_kernels_adjoint_unit.hpp) ----

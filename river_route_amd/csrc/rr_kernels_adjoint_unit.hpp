@@ -1,5 +1,5 @@
 // rr_kernels_adjoint_unit.hpp -- the adjoint of UnitMuskingum routing (rr_unit_adjoint_dev) and of the unit-hydrograph convolution
-// (rr_uh_adjoint_dev), DESIGN.md section 12.  The host side that launches them: unit_adjoint in rr_adjoint.hpp, which shares its
+// (rr_uh_adjoint_dev), DESIGN.md section 12.  The host side that launches them: unit_adjoint_enqueue in rr_adjoint.hpp, which shares its
 // driver with the Rapid adjoint; rr_uh_adjoint_dev in rr_engine.hip.  Part of the one translation unit rr_engine.hip builds (included
 // from there, after rr_kernels_adjoint.hpp; not a stand-alone header).
 //
@@ -15,6 +15,13 @@
 // loads) where a phi tape would cost a second S x n array, and mu - c3 mu[s+1] would cancel.  Tick indexing as in
 // rr_kernels_adjoint.hpp: reach at lag l runs forward sub-step ts at tick ts + l and reverse step r = S - 1 - ts at reverse tick
 // r + Dmax - l; a headwater has the lag its position in the tree gives it and takes no part in the reverse ticks.
+//
+// Member-batched forms (rr_unit_adjoint_batch_dev), by the convention of rr_kernels_adjoint.hpp: the members
+// share every read-only plan array; member m owns a q tape, a mu tape, engine-order lateral and gradient rows, slab and six scratch
+// rows at member pitches (64-bit element counts).  The templated kernels take a trailing ENS flag and an args struct with the pitches
+// appended and form every index as (ENS ? index + offset : index); the member is blockIdx.y, in the reduction, whose y is the
+// sub-step range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling on the member's pointers: three share a
+// __forceinline__ body with their kernel, two (rows, merge) repeat its statements (see k_adj_merge_unit_batch).
 #pragma once
 
 namespace {
@@ -33,9 +40,23 @@ struct UnitAdjTickArgs {
     Div32 nsub;
 };
 
+// Member blockIdx.y: its mu tape rows (ma, mb, mc) at tape_pitch, its dL/d(discharge) rows at g_pitch and its two final-state
+// gradient rows (in its scratch rows) at gf_pitch.
+struct UnitAdjTickEnsArgs : UnitAdjTickArgs {
+    int64_t tape_pitch, g_pitch, gf_pitch;
+};
+template <bool ENS> using UnitAdjTickArgsOf = typename std::conditional<ENS, UnitAdjTickEnsArgs, UnitAdjTickArgs>::type;
+__device__ __forceinline__ int64_t member_tape0(const UnitAdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_tape0(const UnitAdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
+__device__ __forceinline__ int64_t member_g0(const UnitAdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_g0(const UnitAdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.g_pitch; }
+__device__ __forceinline__ int64_t member_gf0(const UnitAdjTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_gf0(const UnitAdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.gf_pitch; }
+
 // One reverse tick: mu of every active inner position (k_adj_tick with the two-state recurrence).
-template <bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgs a)
+// ENS: the member-batched form; the fma sequence of a member is the single call's.
+template <bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgsOf<ENS> a)
 {
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (p >= a.p_hi) return;
@@ -48,24 +69,25 @@ __global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgs 
     if (SINGLE_SUBSTEP) t = ts;
     else { uint32_t rem; t = a.nsub.div(ts, rem); }
 
-    double m = a.g ? a.g[(int64_t)t * a.n + p] : 0.0;
+    const int64_t mt = member_tape0(a), mg = member_g0(a), mf = member_gf0(a);
+    double m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
     if (r == 0) {
-        if (a.gff) m += a.gff[p];
-        if (a.gcf) m += a.gcf[p];
+        if (a.gff) m += a.gff[ENS ? p + mf : p];
+        if (a.gcf) m += a.gcf[ENS ? p + mf : p];
     }
     const int32_t d = a.down[p];
     if (d >= 0) {
-        m = __builtin_fma(a.w[p], a.ma[d], m);
-        if (r > 0) m = __builtin_fma(a.c2[d], a.mb[d], m);
+        m = __builtin_fma(a.w[p], a.ma[ENS ? d + mt : d], m);
+        if (r > 0) m = __builtin_fma(a.c2[d], a.mb[ENS ? d + mt : d], m);
     }
-    if (r > 0) m = __builtin_fma(a.c3[p], a.ma[p], m);
-    a.mc[p] = m;
+    if (r > 0) m = __builtin_fma(a.c3[p], a.ma[ENS ? p + mt : p], m);
+    a.mc[ENS ? p + mt : p] = m;
 }
 
 // dL/d(discharge) in params order with the forward's output rule applied: an inner reach's row is max(mean, 0), a headwater's is
 // its lateral inflow as it is.  One column per lane, rows strided over blockIdx.y.
-__global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
-                                                          const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
+__device__ __forceinline__ void adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
+                                              const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
 {
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
@@ -77,12 +99,25 @@ __global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const dou
         dst[k] = hw ? g : (discharge[k] > 0.0 ? g * inv_nsub : 0.0);
     }
 }
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
+                                                          const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
+{
+    adj_mask_unit(dst, grad_out, discharge, inv, child_ptr, n, T, inv_nsub);
+}
+// member blockIdx.z (y walks the rows): its destination rows at dst_pitch, its discharge and dL/d(discharge) rows at row_pitch
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_batch(double *dst, const double *grad_out, const double *discharge,
+                                                                const int32_t *inv, const int32_t *child_ptr, int64_t n, int64_t T,
+                                                                double inv_nsub, int64_t dst_pitch, int64_t row_pitch)
+{
+    const int64_t m = blockIdx.z;
+    adj_mask_unit(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, inv, child_ptr, n, T, inv_nsub);
+}
 
 // Inner-indexed vectors to engine positions: the tape's first rows (q_full0 where the reach below reads its "old" value), the
 // q_ch row k_tick_unit updates in place and a copy of q_ch0 that stays (the c3 gradient's first term); the final-state gradients.
-__global__ __launch_bounds__(kBlock) void k_adj_unit_in(double *qtape, double *qch, double *qch0, const double *q_full0, const double *q_ch0,
-                                                        double *gcf, double *gff, const double *grad_qch_final, const double *grad_qfull_final,
-                                                        const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner)
+__device__ __forceinline__ void adj_unit_in(double *qtape, double *qch, double *qch0, const double *q_full0, const double *q_ch0,
+                                            double *gcf, double *gff, const double *grad_qch_final, const double *grad_qfull_final,
+                                            const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner)
 {
     const int32_t k = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (k >= n_inner) return;
@@ -94,6 +129,25 @@ __global__ __launch_bounds__(kBlock) void k_adj_unit_in(double *qtape, double *q
     }
     if (grad_qch_final) gcf[p] = grad_qch_final[k];
     if (grad_qfull_final) gff[p] = grad_qfull_final[k];
+}
+__global__ __launch_bounds__(kBlock) void k_adj_unit_in(double *qtape, double *qch, double *qch0, const double *q_full0, const double *q_ch0,
+                                                        double *gcf, double *gff, const double *grad_qch_final, const double *grad_qfull_final,
+                                                        const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner)
+{
+    adj_unit_in(qtape, qch, qch0, q_full0, q_ch0, gcf, gff, grad_qch_final, grad_qfull_final, inner_pos, lag, n, n_inner);
+}
+// member blockIdx.y: its tape at tape_pitch, its scratch rows (qch, qch0, gcf, gff) at scratch_pitch, its states at state_pitch
+// (0: one pair of states for every member), its final-state gradients [members][n_inner], dense
+__global__ __launch_bounds__(kBlock) void k_adj_unit_in_batch(double *qtape, double *qch, double *qch0, const double *q_full0,
+                                                              const double *q_ch0, double *gcf, double *gff, const double *grad_qch_final,
+                                                              const double *grad_qfull_final, const int32_t *inner_pos, const int32_t *lag,
+                                                              int64_t n, int32_t n_inner, int64_t tape_pitch, int64_t scratch_pitch,
+                                                              int64_t state_pitch)
+{
+    const int64_t m = blockIdx.y, ms = m * scratch_pitch;
+    adj_unit_in(qtape + m * tape_pitch, qch + ms, qch0 + ms, q_full0 ? q_full0 + m * state_pitch : nullptr,
+                q_ch0 ? q_ch0 + m * state_pitch : nullptr, gcf + ms, gff + ms, grad_qch_final ? grad_qch_final + m * n_inner : nullptr,
+                grad_qfull_final ? grad_qfull_final + m * n_inner : nullptr, inner_pos, lag, n, n_inner);
 }
 
 struct UnitAdjReduceArgs {
@@ -109,11 +163,26 @@ struct UnitAdjReduceArgs {
     Div32 nsub;
 };
 
+// Member blockIdx.z: its tapes at qtape_pitch / mtape_pitch, its lateral rows at lat_pitch, its q_ch0 row (in its scratch rows) at
+// qch0_pitch, its [splits][3][n] of the slab at slab_pitch.
+struct UnitAdjReduceEnsArgs : UnitAdjReduceArgs {
+    int64_t qtape_pitch, mtape_pitch, lat_pitch, qch0_pitch, slab_pitch;
+};
+template <bool ENS> using UnitAdjReduceArgsOf = typename std::conditional<ENS, UnitAdjReduceEnsArgs, UnitAdjReduceArgs>::type;
+struct UnitAdjReduceMember { int64_t q, m, lat, qch0, slab; };
+__device__ __forceinline__ UnitAdjReduceMember member_offsets(const UnitAdjReduceArgs &) { return {0, 0, 0, 0, 0}; }
+__device__ __forceinline__ UnitAdjReduceMember member_offsets(const UnitAdjReduceEnsArgs &e)
+{
+    const int64_t m = blockIdx.z;
+    return {m * e.qtape_pitch, m * e.mtape_pitch, m * e.lat_pitch, m * e.qch0_pitch, m * e.slab_pitch};
+}
+
 // Partial sums over one range of sub-steps per inner reach (blockIdx.y = range):
 //   sum_s mu[s,i] * {sum_H l + sum_U q_full[s,u],  sum_H l + sum_U q_full[s-1,u],  q_ch[s-1,i]}
 // with q_ch[s-1,i] = q_full[s-1,i] - l[t(s-1),i] from the tape (q_ch0 at s = 1).  Merged in order by k_adj_merge_unit.
-template <bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_adj_reduce_unit(const UnitAdjReduceArgs a)
+// ENS: the member-batched form, member m's sums in slab [m][range][3][n].
+template <bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_adj_reduce_unit(const UnitAdjReduceArgsOf<ENS> a)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= a.n) return;
@@ -123,26 +192,27 @@ __global__ __launch_bounds__(kBlock) void k_adj_reduce_unit(const UnitAdjReduceA
     const int32_t lag = a.lag[p] & kLagMask;
     const int32_t uh = u0 + (int32_t)a.hw_children[p];
     const int64_t s0 = (int64_t)blockIdx.y * a.steps_per_split, s1 = min(a.total_substeps, s0 + a.steps_per_split);
+    const UnitAdjReduceMember mo = member_offsets(a);
     double g1 = 0.0, g2 = 0.0, g3 = 0.0;
     for (int64_t ts = s0; ts < s1; ++ts) {
-        const double *q1 = a.qtape + (ts + lag + 1) * n, *q2 = q1 - n;
-        const double mu = a.mtape[(a.total_substeps - 1 - ts + a.dmax - lag) * n + p];
+        const double *q1 = a.qtape + (ENS ? (ts + lag + 1) * n + mo.q : (ts + lag + 1) * n), *q2 = q1 - n;
+        const double mu = a.mtape[ENS ? (a.total_substeps - 1 - ts + a.dmax - lag) * n + p + mo.m : (a.total_substeps - 1 - ts + a.dmax - lag) * n + p];
         double s_hw = 0.0, s_new = 0.0, s_old = 0.0;
         for (int32_t u = u0; u < uh; ++u) s_hw += q1[u];
         for (int32_t u = uh; u < u1; ++u) { s_new += q1[u]; s_old += q2[u]; }
         double prev;
-        if (ts == 0) prev = a.qch0[p];
+        if (ts == 0) prev = a.qch0[ENS ? p + mo.qch0 : p];
         else {
             uint32_t t;
             if (SINGLE_SUBSTEP) t = (uint32_t)(ts - 1);
             else { uint32_t rem; t = a.nsub.div((uint32_t)(ts - 1), rem); }
-            prev = q1[p] - a.lat[(int64_t)t * n + p];
+            prev = q1[p] - a.lat[ENS ? (int64_t)t * n + p + mo.lat : (int64_t)t * n + p];
         }
         g1 = __builtin_fma(mu, s_hw + s_new, g1);
         g2 = __builtin_fma(mu, s_hw + s_old, g2);
         g3 = __builtin_fma(mu, prev, g3);
     }
-    double *out = a.slab + (int64_t)blockIdx.y * 3 * n + p;
+    double *out = a.slab + (ENS ? (int64_t)blockIdx.y * 3 * n + p + mo.slab : (int64_t)blockIdx.y * 3 * n + p);
     out[0] = g1; out[n] = g2; out[2 * n] = g3;
 }
 
@@ -160,11 +230,28 @@ __global__ __launch_bounds__(kBlock) void k_adj_merge_unit(const double *slab, i
             for (int c = 0; c < 3; ++c) g[c] += slab[(k * 3 + c) * n + p];
     grad_coef[i] = g[0]; grad_coef[n + i] = g[1]; grad_coef[2 * n + i] = g[2];
 }
+// The coefficient gradients are one sum over the members: the slab [members][splits][3][n] is contiguous (adjoint_layout), so one
+// member's worth of blocks folds all members x splits ranges in storage order -- members ascending, within a member its ranges in order.
+// The fold is written out again here, and k_adj_rows_unit_batch's body below, where the other siblings share a __forceinline__ body
+// with their kernel: inlined, these two bodies changed the instruction order of the single-member kernels, whose code section 12e keeps.
+__global__ __launch_bounds__(kBlock) void k_adj_merge_unit_batch(const double *slab, int64_t splits, int64_t members, const int32_t *child_ptr,
+                                                                 const int32_t *perm, int64_t n, double *grad_coef)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int32_t i = perm[p];
+    double g[3] = {0.0, 0.0, 0.0};
+    if (child_ptr[p] != child_ptr[p + 1])
+        for (int64_t k = 0; k < splits * members; ++k)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) g[c] += slab[(k * 3 + c) * n + p];
+    grad_coef[i] = g[0]; grad_coef[n + i] = g[1]; grad_coef[2 * n + i] = g[2];
+}
 
 // dL/dq_ch0[i] = c3[i] mu[1,i], dL/dq_full0[i] = c2[d] mu[1,d], inner order.
-__global__ __launch_bounds__(kBlock) void k_adj_state_unit(double *grad_qch0, double *grad_qfull0, const double *mtape, const int32_t *inner_pos,
-                                                           const int32_t *lag, const int32_t *down, const double *c2, const double *c3, int64_t n,
-                                                           int32_t n_inner, int64_t total_substeps, int32_t dmax)
+__device__ __forceinline__ void adj_state_unit(double *grad_qch0, double *grad_qfull0, const double *mtape, const int32_t *inner_pos,
+                                               const int32_t *lag, const int32_t *down, const double *c2, const double *c3, int64_t n,
+                                               int32_t n_inner, int64_t total_substeps, int32_t dmax)
 {
     const int32_t k = (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (k >= n_inner) return;
@@ -176,6 +263,22 @@ __global__ __launch_bounds__(kBlock) void k_adj_state_unit(double *grad_qch0, do
         grad_qfull0[k] = d >= 0 ? c2[d] * mtape[(tau - 1) * n + d] : 0.0;
     }
 }
+__global__ __launch_bounds__(kBlock) void k_adj_state_unit(double *grad_qch0, double *grad_qfull0, const double *mtape, const int32_t *inner_pos,
+                                                           const int32_t *lag, const int32_t *down, const double *c2, const double *c3, int64_t n,
+                                                           int32_t n_inner, int64_t total_substeps, int32_t dmax)
+{
+    adj_state_unit(grad_qch0, grad_qfull0, mtape, inner_pos, lag, down, c2, c3, n, n_inner, total_substeps, dmax);
+}
+// member blockIdx.y: its rows of grad_qch0 / grad_qfull0 [members][n_inner] from its mu tape at tape_pitch
+__global__ __launch_bounds__(kBlock) void k_adj_state_unit_batch(double *grad_qch0, double *grad_qfull0, const double *mtape,
+                                                                 const int32_t *inner_pos, const int32_t *lag, const int32_t *down,
+                                                                 const double *c2, const double *c3, int64_t n, int32_t n_inner,
+                                                                 int64_t total_substeps, int32_t dmax, int64_t tape_pitch)
+{
+    const int64_t m = blockIdx.y;
+    adj_state_unit(grad_qch0 ? grad_qch0 + m * n_inner : nullptr, grad_qfull0 ? grad_qfull0 + m * n_inner : nullptr, mtape + m * tape_pitch,
+                   inner_pos, lag, down, c2, c3, n, n_inner, total_substeps, dmax);
+}
 
 // dL/dl[t, p] in engine order (g and dst may be the same rows: a lane reads its own element before it writes it):
 //   inner      sum over the row's sub-steps of phi[s,p] = g[t,p] + [s=S] gff[p] + c1[d] mu[s,d] + c2[d] mu[s+1,d]
@@ -185,6 +288,48 @@ __global__ __launch_bounds__(kBlock) void k_adj_rows_unit(double *dst, const dou
                                                           const int32_t *child_ptr, const int32_t *down, const double *w, const double *c2,
                                                           int64_t n, int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
 {
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    const int32_t d = down[p];
+    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
+    const double *md = mtape + (d >= 0 ? d : 0);
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const double gv = g ? g[t * n + p] : 0.0;
+        double v;
+        if (hw) {
+            double m = 0.0;
+            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
+            v = __builtin_fma(c1d + c2d, m, gv);
+        } else {
+            v = 0.0;
+            for (int64_t k = 0; k < nsub; ++k) {
+                const int64_t ts = t * nsub + k;
+                double phi = gv;
+                if (ts == total_substeps - 1 && gff) phi += gff[p];
+                if (d >= 0) {
+                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
+                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
+                }
+                v += phi;
+            }
+        }
+        dst[t * n + p] = v;
+    }
+}
+// member blockIdx.z (y walks the rows): its gradient rows (dst, g) at row_pitch, its dL/d(q_full final) row at gf_pitch, its mu tape
+// at tape_pitch; k_adj_rows_unit's statements on the member's pointers
+__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_batch(double *dst, const double *g, const double *gff, const double *mtape,
+                                                                const int32_t *lag, const int32_t *child_ptr, const int32_t *down,
+                                                                const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
+                                                                int64_t total_substeps, int32_t dmax, int64_t row_pitch, int64_t gf_pitch,
+                                                                int64_t tape_pitch)
+{
+    const int64_t member = blockIdx.z;
+    dst += member * row_pitch; mtape += member * tape_pitch;
+    if (g) g += member * row_pitch;
+    if (gff) gff += member * gf_pitch;
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0

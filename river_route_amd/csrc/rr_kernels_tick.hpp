@@ -107,11 +107,26 @@ struct UnitTickArgs {
     const double *za;             // ... and last tick's (the work rows hold a reach's discharge where its lateral inflow was: in place)
 };
 
+// The member-batched UnitMuskingum tick (ENS; the tape replay of rr_unit_adjoint_batch_dev, rr_adjoint.hpp): TickEnsArgs' convention.
+// Member blockIdx.y has its three state rows tape_pitch doubles, its lateral rows in_pitch and its scratch rows -- running sum,
+// discharge row and the q_ch row updated in place -- scratch_pitch doubles behind the first member's.
+struct UnitTickEnsArgs : UnitTickArgs {
+    int64_t tape_pitch, in_pitch, scratch_pitch;
+};
+template <bool ENS> using UnitTickArgsOf = typename std::conditional<ENS, UnitTickEnsArgs, UnitTickArgs>::type;
+__device__ __forceinline__ int64_t member_tape0(const UnitTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_tape0(const UnitTickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
+__device__ __forceinline__ int64_t member_in0(const UnitTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_in0(const UnitTickEnsArgs &e) { return (int64_t)blockIdx.y * e.in_pitch; }
+__device__ __forceinline__ int64_t member_scratch0(const UnitTickArgs &) { return 0; }
+__device__ __forceinline__ int64_t member_scratch0(const UnitTickEnsArgs &e) { return (int64_t)blockIdx.y * e.scratch_pitch; }
+
 // One routing tick for UnitMuskingum (river_route/routers/_numba_kernels.py:113-171 in gather form).
 // A headwater publishes its convolved lateral l_t as both its "old" and "new" discharge; an inner reach
 // routes q_ch and publishes q_full = q_ch + l_t.
-template <bool SINGLE_SUBSTEP>
-__global__ __launch_bounds__(kBlock) void k_tick_unit(const UnitTickArgs ua)
+// ENS: the member-batched form (UnitTickEnsArgs); it has no boundary reaches and no general edge data (the adjoint refuses both).
+template <bool SINGLE_SUBSTEP, bool ENS = false>
+__global__ __launch_bounds__(kBlock) void k_tick_unit(const UnitTickArgsOf<ENS> ua)
 {
     const TickArgs &a = ua.t;
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
@@ -119,7 +134,8 @@ __global__ __launch_bounds__(kBlock) void k_tick_unit(const UnitTickArgs ua)
     const int32_t lag_bits = a.lag[p];
     const int32_t ts = (int32_t)a.tau - (lag_bits & kLagMask);
     if (ts < 0 || ts >= (int32_t)a.total_substeps) return;
-    if (lag_bits & kGhostBit) {   // boundary inflow: the discharge another GPU published for this sub-step
+    const int64_t mt = member_tape0(ua), mi = member_in0(ua), ms = member_scratch0(ua);
+    if (!ENS && (lag_bits & kGhostBit)) {   // boundary inflow: the discharge another GPU published for this sub-step
         a.xc[p] = a.ghost[(int64_t)ts * a.n_ghost + a.bidx[p]];
         return;
     }
@@ -127,22 +143,22 @@ __global__ __launch_bounds__(kBlock) void k_tick_unit(const UnitTickArgs ua)
     if (SINGLE_SUBSTEP) { t = (uint32_t)ts; s = 0; }
     else t = a.nsub.div((uint32_t)ts, s);
 
-    const double lat = a.in[(int64_t)a.in_rows.mod(t) * a.in_ld + p];
+    const double lat = a.in[ENS ? (int64_t)a.in_rows.mod(t) * a.in_ld + p + mi : (int64_t)a.in_rows.mod(t) * a.in_ld + p];
     const int32_t u0 = a.child_ptr[p], u1 = a.child_ptr[p + 1];
     if (u0 == u1) {  // headwater: discharge is the lateral inflow, unclamped and un-averaged (lines 122-123)
-        a.xc[p] = lat;
-        if (lag_bits & kExportBit) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = lat;
-        if (s == 0) a.out[(int64_t)a.out_rows.mod(t) * a.out_ld + p] = lat;
+        a.xc[ENS ? p + mt : p] = lat;
+        if (!ENS && (lag_bits & kExportBit)) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = lat;
+        if (s == 0) a.out[ENS ? (int64_t)a.out_rows.mod(t) * a.out_ld + p + ms : (int64_t)a.out_rows.mod(t) * a.out_ld + p] = lat;
         return;
     }
     const int32_t uh = u0 + (int32_t)ua.hw_children[p];
     double r;
     if (a.c1row) {      // the arithmetic of k_tile, operation for operation (see k_tick)
         double s_hw = 0.0, s_new = 0.0, s_old = 0.0;
-        for (int32_t u = u0; u < uh; ++u) s_hw += a.xa[u];   // headwater tributaries: "old" value is l_t too
-        for (int32_t u = uh; u < u1; ++u) { s_new += a.xa[u]; s_old += a.xb[u]; }
-        r = __builtin_fma(a.c1row[p], s_hw + s_new, __builtin_fma(a.c2[p], s_hw + s_old, a.c3[p] * ua.qch[p]));
-    } else if (ua.a2) {
+        for (int32_t u = u0; u < uh; ++u) s_hw += a.xa[ENS ? u + mt : u];   // headwater tributaries: "old" value is l_t too
+        for (int32_t u = uh; u < u1; ++u) { s_new += a.xa[ENS ? u + mt : u]; s_old += a.xb[ENS ? u + mt : u]; }
+        r = __builtin_fma(a.c1row[p], s_hw + s_new, __builtin_fma(a.c2[p], s_hw + s_old, a.c3[p] * ua.qch[ENS ? p + ms : p]));
+    } else if (!ENS && ua.a2) {
         // _numba_kernels.py:126-162 term by term: c1 (A_in l_in + A_hw l_hw) + c2 A_hw l_hw + c3 q_ch + c2 (structure of lhs) q_full
         // - lhs_off q_ch+, with the upstream reach's own lateral (same row, its position) separating q_ch+ from what it published
         r = a.c3[p] * ua.qch[p];
@@ -154,26 +170,26 @@ __global__ __launch_bounds__(kBlock) void k_tick_unit(const UnitTickArgs ua)
         }
         ua.zc[p] = r;
     } else {
-        r = a.c3[p] * ua.qch[p];
+        r = a.c3[p] * ua.qch[ENS ? p + ms : p];
         const double c2 = a.c2[p];
-        for (int32_t u = u0; u < uh; ++u) r += c2 * a.xa[u];
-        for (int32_t u = uh; u < u1; ++u) r += c2 * a.xb[u];
-        for (int32_t u = u0; u < u1; ++u) r += a.w[u] * a.xa[u];
+        for (int32_t u = u0; u < uh; ++u) r += c2 * a.xa[ENS ? u + mt : u];
+        for (int32_t u = uh; u < u1; ++u) r += c2 * a.xb[ENS ? u + mt : u];
+        for (int32_t u = u0; u < u1; ++u) r += a.w[u] * a.xa[ENS ? u + mt : u];
     }
-    ua.qch[p] = r;
+    ua.qch[ENS ? p + ms : p] = r;
     const double qfull = r + lat;
-    a.xc[p] = qfull;
-    if (lag_bits & kExportBit) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = qfull;
+    a.xc[ENS ? p + mt : p] = qfull;
+    if (!ENS && (lag_bits & kExportBit)) a.exports[(int64_t)ts * a.n_export + a.bidx[p]] = qfull;
 
     if (SINGLE_SUBSTEP) {
-        a.out[(int64_t)a.out_rows.mod(t) * a.out_ld + p] = qfull > 0.0 ? qfull : 0.0;
+        a.out[ENS ? (int64_t)a.out_rows.mod(t) * a.out_ld + p + ms : (int64_t)a.out_rows.mod(t) * a.out_ld + p] = qfull > 0.0 ? qfull : 0.0;
     } else {
-        const double acc = (s == 0 ? 0.0 : a.isum[p]) + qfull;
+        const double acc = (s == 0 ? 0.0 : a.isum[ENS ? p + ms : p]) + qfull;
         if (s + 1 == a.nsub.d) {
             const double v = acc * a.inv_nsub;
-            a.out[(int64_t)a.out_rows.mod(t) * a.out_ld + p] = v > 0.0 ? v : 0.0;
+            a.out[ENS ? (int64_t)a.out_rows.mod(t) * a.out_ld + p + ms : (int64_t)a.out_rows.mod(t) * a.out_ld + p] = v > 0.0 ? v : 0.0;
         } else {
-            a.isum[p] = acc;
+            a.isum[ENS ? p + ms : p] = acc;
         }
     }
 }

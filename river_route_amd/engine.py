@@ -275,6 +275,25 @@ class Plan:
                                              ptr(grad_qch_final), ptr(grad_qfull_final), ptr(grad_lateral), ptr(grad_qch0), ptr(grad_qfull0),
                                              ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps), stream))
 
+    def unit_adjoint_batch_work_bytes(self, members: int, T: int, num_substeps: int = 1) -> int:
+        """rr_unit_adjoint_batch_work_bytes: bytes of work memory unit_adjoint_batch_dev needs for `members` series of T rows x
+        num_substeps sub-steps (readies the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_unit_adjoint_batch_work_bytes(self._h, int(members), int(T), int(num_substeps), C.byref(out)))
+        return int(out.value)
+
+    def unit_adjoint_batch_dev(self, members, q_ch0, q_full0, state_pitch, lateral, lat_rows, lat_pitch, discharge, grad_out, out_pitch,
+                               grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef, work, work_bytes, T,
+                               num_substeps, stream=None) -> None:
+        """rr_unit_adjoint_batch_dev (enqueue only): unit_adjoint_dev for `members` series at once, member m's arrays m pitches (in
+        values) behind the first's; the final-state gradients and grad_qch0 / grad_qfull0 are [members, n_inner], grad_coef[3, n] is
+        the sum over the members."""
+        check(_lib.lib().rr_unit_adjoint_batch_dev(self._h, int(members), ptr(q_ch0), ptr(q_full0), int(state_pitch), ptr(lateral),
+                                                   int(lat_rows), int(lat_pitch), ptr(discharge), ptr(grad_out), int(out_pitch),
+                                                   ptr(grad_qch_final), ptr(grad_qfull_final), ptr(grad_lateral), ptr(grad_qch0),
+                                                   ptr(grad_qfull0), ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps),
+                                                   stream))
+
     def muskingum_route_dev(self, q_t, discharge, out_rows, num_output_steps, num_routing_per_output,
                             stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output)

@@ -24,8 +24,13 @@ rr_rapid_adjoint_batch_dev call whose two sweeps launch once per tick for all me
 
     Q, q_final = rr.grad.rapid_route_batch(plan, q0, qlateral, k, x, 900.0, 3600.0)      # qlateral[B, T, n] -> Q[B, T, n], q_final[B, n]
 
+UnitMuskingum has the same: unit_route_batch (backward: rr_unit_adjoint_batch_dev), uh_convolve_batch (member
+by member: the convolution's adjoint is a few launches per member, not one per tick) and unit_muskingum_batch, the two chained:
+
+    Q, q_ch, q_full, uh_state = rr.grad.unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state0, k, x, 900.0, 3600.0)
+
 Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, partitioned plans and plans with
-set_unit_weights edge data are refused, and so is a 3-D qlateral everywhere but in rapid_route_batch.
+set_unit_weights edge data are refused, and so are 3-D rows everywhere but in the *_batch functions.
 
 The loss a calibration minimises is a skill score at gauges, and `scores` is rr.metrics.scores with an autograd graph (DESIGN.md
 section 12c): the same five values, bit for bit, and a backward pass that writes dL/dQ in one streaming pass on the GPU:
@@ -42,7 +47,7 @@ from . import engine, metrics
 from .engine import Plan
 
 __all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
-           'unit_muskingum', 'Scores', 'scores']
+           'unit_muskingum', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores']
 
 
 def muskingum_coefficients(k, x, dt_routing):
@@ -221,7 +226,38 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
 
 # ---- RapidMuskingum, several series at once ----
 
-kMaxMembers = 65535      # members of one rr_rapid_adjoint_batch_dev call
+kMaxMembers = 65535      # members of one rr_rapid_adjoint_batch_dev / rr_unit_adjoint_batch_dev call
+
+
+def _check_members_per_sweep(members_per_sweep):
+    if members_per_sweep is not None and int(members_per_sweep) < 1:
+        raise ValueError('members_per_sweep must be >= 1')
+
+
+def _check_member_rows(t, name, n, single):
+    """Rows of a batched call: a contiguous float64 (B, T, n) tensor (`single` names the function for one series).  Returns B, T."""
+    if not isinstance(t, torch.Tensor) or t.ndim != 3:
+        raise ValueError(f'{name} must be a 3-D (B, T, n) tensor (one series: {single})')
+    B, T = int(t.shape[0]), int(t.shape[1])
+    if T < 1:
+        raise ValueError(f'{name} has no rows')
+    _check_tensor(t, name, (B, T, n))
+    if B < 1:
+        raise ValueError('no members')
+    return B, T
+
+
+def _check_member_state(t, name, B, shape):
+    """A state of a batched call: (B, *shape), or `shape` alone for one state shared by every member."""
+    if not isinstance(t, torch.Tensor) or t.ndim not in (len(shape), len(shape) + 1):
+        dims = ', '.join(('n_inner',) if len(shape) == 1 else ('n_ks', 'n'))
+        raise ValueError(f'{name} must be a (B, {dims}) tensor, or ({dims}{"," if len(shape) == 1 else ""}) for one state shared by every member')
+    _check_tensor(t, name, (B, *shape) if t.ndim == len(shape) + 1 else tuple(shape))
+
+
+def _per_member(t, B, shape):
+    """A shared state as B rows of pitch 0: autograd sums the members' rows into the one state."""
+    return t.unsqueeze(0).expand(B, *shape) if t.ndim == len(shape) else t
 
 
 class RapidRouteBatch(torch.autograd.Function):
@@ -302,8 +338,7 @@ def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_
     Every argument is checked before the GPU is touched."""
     nsub = _check_call(plan, 'n', (), k, x, dt_routing, dt_runoff, rows_per_window)
     n = plan.n
-    if members_per_sweep is not None and int(members_per_sweep) < 1:
-        raise ValueError('members_per_sweep must be >= 1')
+    _check_members_per_sweep(members_per_sweep)
     if not isinstance(q0, torch.Tensor) or q0.ndim not in (1, 2):
         raise ValueError('q0 must be a (B, n) tensor, or (n,) for one state shared by every member')
     if qlateral is None:
@@ -313,12 +348,7 @@ def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_
             raise ValueError('channel-only routing (qlateral=None) needs rows >= 1')
         B, T = int(q0.shape[0]), int(rows)
     else:
-        if not isinstance(qlateral, torch.Tensor) or qlateral.ndim != 3:
-            raise ValueError('qlateral must be a 3-D (B, T, n) tensor (one series: rapid_route)')
-        B, T = int(qlateral.shape[0]), int(qlateral.shape[1])
-        if T < 1:
-            raise ValueError('qlateral has no rows')
-        _check_tensor(qlateral, 'qlateral', (B, T, n))
+        B, T = _check_member_rows(qlateral, 'qlateral', n, 'rapid_route')
     if B < 1:
         raise ValueError('no members')
     _check_tensor(q0, 'q0', (B, n) if q0.ndim == 2 else (n,))
@@ -471,6 +501,211 @@ def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_ro
         return (*UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (q_ch0, q_full0, uh_state), route)
+
+
+# ---- UnitMuskingum, several series at once ----
+
+class UhConvolveBatch(torch.autograd.Function):
+    """(convolved[B, T, n], state_out[B, n_ks, n]) = UhConvolve for B series at once: one kernel[n_ks, n], state[B, n_ks, n] (any member
+    pitch: an expanded (n_ks, n) state has pitch 0), depth[B, T, n] whose members' rows are adjacent.  Forward and backward run member by
+    member through rr_uh_convolve_dev and rr_uh_adjoint_dev, so every member's values are UhConvolve's bits; dL/dkernel is added in
+    member order."""
+
+    @staticmethod
+    def forward(ctx, kernel, state, depth):
+        dev = depth.device.index
+        n_ks, n = kernel.shape
+        B, T = int(depth.shape[0]), int(depth.shape[1])
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        state_out = state.detach().clone(memory_format=torch.contiguous_format)
+        convolved = torch.empty((B, T, n), dtype=torch.float64, device=depth.device)
+        k, d = kernel.detach(), depth.detach()
+        for m in range(B):
+            engine.uh_convolve_dev(k, state_out[m], d[m], convolved[m], T, n_ks, n, dev, stream)
+        ctx.save_for_backward(kernel, depth)
+        ctx.set_materialize_grads(False)
+        return convolved, state_out
+
+    @staticmethod
+    def backward(ctx, grad_convolved, grad_state_out):
+        kernel, depth = ctx.saved_tensors
+        need = ctx.needs_input_grad      # kernel, state, depth
+        if (grad_convolved is None and grad_state_out is None) or not any(need):
+            return None, None, None
+        dev = depth.device.index
+        n_ks, n = kernel.shape
+        B, T = int(depth.shape[0]), int(depth.shape[1])
+        f64 = dict(dtype=torch.float64, device=depth.device)
+        g_c = None if grad_convolved is None else grad_convolved.to(**f64).contiguous()
+        g_s = None if grad_state_out is None else grad_state_out.to(**f64).contiguous()
+        g_state = torch.empty((B, n_ks, n), **f64) if need[1] else None
+        g_depth = torch.empty((B, T, n), **f64) if need[2] else None
+        nbytes = engine.uh_adjoint_work_bytes(T, n_ks, n) if need[0] else 0
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=depth.device)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        k, d = kernel.detach(), depth.detach()
+        g_kernel = None
+
+        def member(t, m):
+            return None if t is None else t[m]
+
+        for m in range(B):
+            part = torch.empty((n_ks, n), **f64) if need[0] else None
+            engine.uh_adjoint_dev(k, d[m], member(g_c, m), member(g_s, m), member(g_depth, m), part, member(g_state, m), work, nbytes, T, n_ks,
+                                  n, dev, stream)
+            if need[0]:
+                g_kernel = part if g_kernel is None else g_kernel + part
+        return g_kernel, g_state, g_depth
+
+
+class UnitRouteBatch(torch.autograd.Function):
+    """(discharge[B, T, n], q_ch[B, n_inner], q_full[B, n_inner]) = UnitRoute for B series at once: q_ch0, q_full0[B, n_inner] (rows of
+    n_inner adjacent values, any pitch: an expanded (n_inner,) state has pitch 0), lateral[B, T, n], one set of coefficients.  Forward:
+    UnitRoute's call, member by member, so every member's values are UnitRoute's bits.  Backward: rr_unit_adjoint_batch_dev on groups of
+    `per_sweep` members (None: all) in ascending order, the groups' coefficient gradients added in that order."""
+
+    @staticmethod
+    def forward(ctx, plan, nsub, per_sweep, q_ch0, q_full0, lateral, c1, c2, c3):
+        dev = plan.device
+        B, T = int(lateral.shape[0]), int(lateral.shape[1])
+        _set_coeffs(plan, c1, c2, c3, None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        q_ch = q_ch0.detach().clone(memory_format=torch.contiguous_format)
+        q_full = q_full0.detach().clone(memory_format=torch.contiguous_format)
+        discharge = torch.empty((B, T, plan.n), dtype=torch.float64, device=lateral.device)
+        lat = lateral.detach()
+        for m in range(B):
+            plan.unit_route_dev(q_ch[m], q_full[m], lat[m], T, discharge[m], T, T, nsub, stream)
+        ctx.plan, ctx.nsub, ctx.per_sweep = plan, int(nsub), per_sweep
+        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach())
+        ctx.save_for_backward(q_ch0, q_full0, lateral, discharge)
+        ctx.set_materialize_grads(False)
+        return discharge, q_ch, q_full
+
+    @staticmethod
+    def backward(ctx, grad_discharge, grad_qch, grad_qfull):
+        plan, nsub = ctx.plan, ctx.nsub
+        q_ch0, q_full0, lateral, discharge = ctx.saved_tensors
+        need = ctx.needs_input_grad      # plan, nsub, per_sweep, q_ch0, q_full0, lateral, c1, c2, c3
+        want_coef = any(need[6:9])
+        if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[3:6]) or want_coef):
+            return (None,) * 9
+        B, T, n, ni = int(lateral.shape[0]), int(lateral.shape[1]), plan.n, plan.n_inner
+        _set_coeffs(plan, *ctx.coeffs, None, plan.device)
+        stream = torch.cuda.current_stream(plan.device).cuda_stream
+        f64 = dict(dtype=torch.float64, device=discharge.device)
+        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
+        g_qch0 = torch.empty((B, ni), **f64) if need[3] else None
+        g_qfull0 = torch.empty((B, ni), **f64) if need[4] else None
+        g_lat = torch.empty((B, T, n), **f64) if need[5] else None
+        lat = lateral.detach()
+        # one pitch serves both states: one of them shared and the other not, or no inner reach at all, and they go as dense rows
+        qc, qf = q_ch0.detach(), q_full0.detach()
+        if ni == 0 or B == 1 or qc.stride(0) != qf.stride(0):
+            qc, qf = qc.contiguous(), qf.contiguous()
+        pitch = int(qc.stride(0)) if B > 1 and ni > 0 else ni
+        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
+        nbytes = max(plan.unit_adjoint_batch_work_bytes(g, T, nsub) for g in {group, B % group or group})
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
+        g_coef = None
+
+        def members(t, m0, m1):
+            return None if t is None else t[m0:m1]
+
+        def state(t, m0):
+            return t.data_ptr() + 8 * m0 * pitch if ni > 0 else None
+
+        for m0 in range(0, B, group):
+            m1 = min(B, m0 + group)
+            part = torch.empty((3, n), **f64) if want_coef else None
+            plan.unit_adjoint_batch_dev(m1 - m0, state(qc, m0), state(qf, m0), pitch, lat[m0:m1], T, T * n, discharge[m0:m1],
+                                        members(g_out, m0, m1), T * n, members(g_c, m0, m1), members(g_f, m0, m1), members(g_lat, m0, m1),
+                                        members(g_qch0, m0, m1), members(g_qfull0, m0, m1), part, work, nbytes, T, nsub, stream)
+            if want_coef:
+                g_coef = part if g_coef is None else g_coef + part
+        coef = [g_coef[j].to(c.device) if want_coef and need[6 + j] else None for j, c in enumerate(ctx.coeffs)]
+        return (None, None, None, g_qch0, g_qfull0, g_lat, *coef)
+
+
+def _check_unit_batch(plan, q_ch0, q_full0, rows, rows_name, single, k, x, dt_routing, dt_runoff, rows_per_window, members_per_sweep):
+    """The checks unit_route_batch and unit_muskingum_batch share.  Returns nsub, B, T."""
+    nsub = _check_call(plan, 'n_inner', (), k, x, dt_routing, dt_runoff, rows_per_window)
+    _check_members_per_sweep(members_per_sweep)
+    B, T = _check_member_rows(rows, rows_name, plan.n, single)
+    for t, name in ((q_ch0, 'q_ch0'), (q_full0, 'q_full0')):
+        _check_member_state(t, name, B, (plan.n_inner,))
+    return nsub, B, T
+
+
+def uh_convolve_batch(kernel, state, depth):
+    """uh_convolve for B series of runoff depths and one kernel: (convolved[B, T, n], state_out[B, n_ks, n]).
+
+    kernel[n_ks, n] and depth[B, T, n] are contiguous float64 tensors on one GPU; state is (B, n_ks, n), or (n_ks, n) for one carried state
+    shared by every member, whose gradient is then the sum over the members.  Every member's values and its dL/dstate and dL/ddepth are
+    the bits uh_convolve gives for that member alone; dL/dkernel is the sum over the members, added in member order.  The calls run
+    member by member (rr_uh_convolve_dev, rr_uh_adjoint_dev): the convolution's adjoint is a few launches per member, not one per tick,
+    so there is nothing for a member dimension to save."""
+    if not isinstance(kernel, torch.Tensor) or kernel.ndim != 2:
+        raise ValueError('kernel must be a 2-D (n_ks, n) tensor')
+    n_ks, n = (int(v) for v in kernel.shape)
+    if n_ks < 1:
+        raise ValueError('kernel has no steps')
+    _check_tensor(kernel, 'kernel', (n_ks, n))
+    B, _ = _check_member_rows(depth, 'depth', n, 'uh_convolve')
+    _check_member_state(state, 'state', B, (n_ks, n))
+    if depth.device.type != 'cuda':
+        raise ValueError(f'depth must be on a GPU (it is on {depth.device})')
+    for t, name in ((kernel, 'kernel'), (state, 'state')):
+        if t.device != depth.device:
+            raise ValueError(f'{name} must be on cuda:{depth.device.index} (it is on {t.device})')
+    return UhConvolveBatch.apply(kernel, _per_member(state, B, (n_ks, n)), depth)
+
+
+def unit_route_batch(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None, members_per_sweep=None):
+    """unit_route for B series of convolved lateral inflow on one network and one set of coefficients: (discharge[B, T, n],
+    q_ch[B, n_inner], q_full[B, n_inner]).
+
+    lateral[B, T, n] is a contiguous float64 tensor on the plan's GPU; q_ch0 and q_full0 are (B, n_inner), or (n_inner,) for one state
+    shared by every member, whose gradient is then the sum over the members; k and x are as in unit_route and serve all members.  Every
+    member's discharge, q_ch and q_full are the bits unit_route gives for that member alone (the forward is the same call, member by
+    member), and so are its dL/dlateral, dL/dq_ch0 and dL/dq_full0; k and x get the sum over the members.  The backward pass is one
+    rr_unit_adjoint_batch_dev call: its tick launches do not grow with B.  members_per_sweep (None: all members in one sweep) bounds the
+    tape memory: the backward then runs groups of that many members in ascending order and adds the groups' coefficient gradients in
+    that order.  rows_per_window chains windows through the states as unit_route does.  Every argument is checked before the GPU is
+    touched."""
+    nsub, B, T = _check_unit_batch(plan, q_ch0, q_full0, lateral, 'lateral', 'unit_route', k, x, dt_routing, dt_runoff, rows_per_window,
+                                   members_per_sweep)
+    _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    ni = plan.n_inner
+    whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
+    return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,))),
+                       lambda t0, t1, q_ch, q_full: UnitRouteBatch.apply(
+                           plan, nsub, members_per_sweep, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(), c1, c2, c3), axis=1)
+
+
+def unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None,
+                         members_per_sweep=None):
+    """unit_muskingum for B series of runoff depths: uh_convolve_batch and unit_route_batch chained per window, as unit_muskingum chains
+    uh_convolve and unit_route.  depth is (B, T, n); uh_state is (B, n_ks, n), or (n_ks, n) for one shared by every member, as q_ch0 and
+    q_full0 may be (n_inner,).  Returns (discharge[B, T, n], q_ch[B, n_inner], q_full[B, n_inner], uh_state_out[B, n_ks, n]); gradients
+    reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x, the shared ones summed over the members."""
+    nsub, B, T = _check_unit_batch(plan, q_ch0, q_full0, depth, 'depth', 'unit_muskingum', k, x, dt_routing, dt_runoff, rows_per_window,
+                                   members_per_sweep)
+    if not isinstance(uh_kernel, torch.Tensor) or uh_kernel.ndim != 2 or int(uh_kernel.shape[0]) < 1:
+        raise ValueError('uh_kernel must be a 2-D (n_ks, n) tensor')
+    n_ks, n, ni = int(uh_kernel.shape[0]), plan.n, plan.n_inner
+    _check_tensor(uh_kernel, 'uh_kernel', (n_ks, n))
+    _check_member_state(uh_state, 'uh_state', B, (n_ks, n))
+    _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
+    c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+
+    def route(t0, t1, q_ch, q_full, state):      # a member's rows of a window are adjacent: the convolution reads them in place
+        lateral, state = UhConvolveBatch.apply(uh_kernel, state, depth[:, t0:t1])
+        return (*UnitRouteBatch.apply(plan, nsub, members_per_sweep, q_ch, q_full, lateral, c1, c2, c3), state)
+
+    return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,)), _per_member(uh_state, B, (n_ks, n))),
+                       route, axis=1)
 
 
 # ---- skill scores as a loss ----
