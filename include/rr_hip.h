@@ -95,6 +95,12 @@ int rr_plan_layout(const rr_plan *plan, int32_t *perm, int32_t *lag, int32_t *ch
  * and how many of them are headwaters (high 16 bits, they come first); xpos[np] position of the mirroring ghost / mirrored
  * reach, -1 elsewhere. */
 int rr_plan_tile_info(const rr_plan *plan, int64_t info[8]);
+/* Headwaters the in-pass routes: with one sub-step per row the record pass that turns lateral rows into
+ * records also routes the headwaters among them, and the time-tiled kernel never writes their records back.  info[0]=1 unless
+ * RR_HW_INPASS=0 switched it off, [1]=eligible positions of the tile layout, [2]=positions that own a reach without an upstream
+ * position in their tile, [3]=of those, left out because a ghost of another tile mirrors them or they are boundary ghosts of a
+ * partitioned network, [4]=left out because their tile holds a reach with more than three upstream reaches. */
+int rr_plan_inpass_info(const rr_plan *plan, int64_t info[5]);
 int rr_plan_tile_layout(const rr_plan *plan, int32_t *tile_ptr, int32_t *tile_level, int32_t *perm, int32_t *lag,
                         int32_t *cfirst, uint32_t *ccnt, int32_t *xpos);
 

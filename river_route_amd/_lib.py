@@ -91,6 +91,7 @@ _SIGNATURES = {
     'rr_plan_info': (C.c_int, [_vp, _vp]),
     'rr_plan_layout': (C.c_int, [_vp, _vp, _vp, _vp]),
     'rr_plan_tile_info': (C.c_int, [_vp, _vp]),
+    'rr_plan_inpass_info': (C.c_int, [_vp, _vp]),
     'rr_plan_tile_layout': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     'rr_plan_direct_info': (C.c_int, [_vp, _vp, _vp, _i64]),
     'rr_plan_direct_layout': (C.c_int, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

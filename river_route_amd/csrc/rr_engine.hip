@@ -58,7 +58,7 @@ void rr_plan_destroy(rr_plan *P)
                         P->d_c3, P->d_c4, P->d_x, P->d_isum, P->d_qch, P->d_a2, P->d_c1own, P->d_z, P->d_ring, P->d_stage, P->d_mrows,
                         P->d_slot_a[0], P->d_slot_a[1], P->d_slot_b[0], P->d_slot_b[1], P->d_m_index[0], P->d_m_index[1],
                         P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef, P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch,
-                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi, P->d_adj_down};
+                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi, P->d_adj_down, P->d_pmeta_hw, P->d_coef_hw, P->d_hwcoef, P->d_hwq};
         for (void *p : ptrs) if (p) (void)hipFree(p);
         P->pipe.destroy();
         for (hipEvent_t e : P->ev) (void)hipEventDestroy(e);
@@ -79,7 +79,9 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
     // =1 the time-tiled one wherever it applies; RR_WAVE_K ticks per task; RR_TILE_BLOCK tile capacity (many small tiles);
     // RR_TILE_LEAN=0 the general tick; RR_UH_PAIRS=0 one record batch per fused-convolution launch; RR_REC_BATCHES=N N record batches
     // per launch of k_rec_in / k_rec_out in every call (1: one, as before multi-batch launches); RR_DIRECT=0 records also where the
-    // params order would allow the direct row path; RR_VERBOSE=1 logs the schedule.
+    // params order would allow the direct row path; RR_HW_INPASS=0 headwaters routed and stored by k_tile, as every other reach; RR_VERBOSE=1
+    // logs the schedule.
+    if (const char *e = getenv("RR_HW_INPASS")) P->hw_inpass = atoi(e) != 0;
     if (const char *e = getenv("RR_WAVE")) { P->wave_enabled = atoi(e) != 0; P->wave_forced = atoi(e) == 1; }
     if (const char *e = getenv("RR_REC_BATCHES")) { P->rec_batches = std::max(1, std::min(kRecMaxLaunchBatches, atoi(e))); P->rec_batches_forced = true; }
     if (const char *e = getenv("RR_WAVE_K")) P->wave_K = std::max(kRec, atoi(e) / kRec * kRec);
@@ -147,17 +149,12 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
         if (!rc && P->tp.ok) {      // tile layout of the time-tiled kernel
             const rr::TilePlan &TP = P->tp;
             const int64_t np = TP.np;
-            std::vector<int2> cm(n);
-            for (int64_t i = 0; i < n; ++i)      // a headwater column is flagged: UnitMuskingum's out-pass leaves it unclamped
-                cm[i] = make_int2(TP.inv[i], (TP.lag[TP.inv[i]] & kLagMask) | (H.child_ptr[H.inv[i] + 1] == H.child_ptr[H.inv[i]] ? kColHeadwater : 0));
             std::vector<int32_t> inner_idx;
             inner_idx.reserve(ni);
             for (int64_t i = 0; i < n; ++i) if (H.child_ptr[H.inv[i] + 1] > H.child_ptr[H.inv[i]]) inner_idx.push_back((int32_t)i);
-            rc = dev_alloc(&P->d_colmeta, n);
-            if (!rc) rc = dev_upload(P->d_colmeta, cm);
-            if (!rc) rc = dev_alloc(&P->d_inner_idx, ni);
+            rc = dev_alloc(&P->d_inner_idx, ni);
             if (!rc) rc = dev_upload(P->d_inner_idx, inner_idx);
-            if (!rc) rc = upload_tile_meta(P, TP.lag, TP.xpos, TP.tile_flags);
+            if (!rc) rc = upload_tile_meta(P, TP.lag, TP.xpos, TP.tile_flags);      // (and the column metadata of the record passes)
             for (int32_t f : TP.tile_flags) P->n_wide_tiles += (f & kTileWide) ? 1 : 0;
             if (!rc) rc = dev_alloc(&P->d_tperm, np);
             if (!rc) rc = dev_upload(P->d_tperm, TP.perm);
@@ -165,6 +162,9 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
             if (!rc) rc = dev_upload(P->d_tinv, TP.inv);
             if (!rc) rc = dev_alloc(&P->d_coef, 3 * np);
             if (!rc) rc = dev_alloc(&P->d_coef_unit, 3 * np);
+            if (!rc) rc = dev_alloc(&P->d_coef_hw, 3 * np);
+            if (!rc) rc = dev_alloc(&P->d_hwcoef, 3 * n);
+            if (!rc) rc = dev_alloc(&P->d_hwq, n);
             if (!rc) rc = dev_alloc(&P->d_sq, np);
             if (!rc) rc = dev_alloc(&P->d_ss, np);
             if (!rc) rc = dev_alloc(&P->d_si, np);
@@ -217,6 +217,19 @@ int rr_plan_tile_info(const rr_plan *P, int64_t info[8])
     const rr::TilePlan &T = P->tp;
     info[0] = T.ok ? 1 : 0; info[1] = T.block; info[2] = T.np; info[3] = T.n_ghost; info[4] = T.n_tiles; info[5] = T.n_levels;
     info[6] = P->wave_threads; info[7] = kRecRows;
+    return RR_OK;
+}
+
+int rr_plan_inpass_info(const rr_plan *P, int64_t info[5])
+{
+    if (!P || !info) return fail(RR_E_INVALID, "rr_plan_inpass_info: null argument");
+    for (int k = 0; k < 5; ++k) info[k] = 0;
+    info[0] = P->hw_inpass ? 1 : 0;
+    if (!P->tp.ok) return RR_OK;
+    std::vector<int32_t> lag(P->tp.lag);      // with the boundary ghosts of a partitioned network, as rr_plan_set_boundary flags them
+    for (int32_t i : P->ghost_reach) lag[P->tp.inv[i]] |= kGhostBit;
+    std::vector<uint8_t> elig;
+    rr::mark_inpass_headwaters(P->tp, lag, kGhostBit, elig, info + 1);
     return RR_OK;
 }
 

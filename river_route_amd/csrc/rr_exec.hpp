@@ -97,6 +97,7 @@ struct Session {
     size_t max_samples = 0;
     int64_t members = 0;          // an ensemble call (Rows::members): member m's record ring at m * ring_stride doubles
     int64_t ring_stride = 0;
+    bool hw = false;              // Tile: the plan's in-pass headwaters are not k_tile's to store in this call (rr_plan::hw_inpass); RapidMuskingum: k_rec_in routes them
 };
 
 // ---- host-pointer calls: PCIe pipeline around the time-tiled kernel ----
@@ -171,6 +172,16 @@ struct rr_plan {
     bool export_inside = false;      // an export reach that another tile mirrors (it has a downstream reach in this plan): streaming kernel only
     double *d_coef = nullptr;        // per position {c1row, c2, c3}
     double *d_coef_unit = nullptr;   // the same with zeros at the positions without upstream positions (UnitMuskingum's short tick)
+    // Headwaters routed by the in-pass (rr_plan.hpp: mark_inpass_headwaters; RR_HW_INPASS=0: off).  The short tick of a call with one
+    // sub-step per row, single member, reads d_pmeta_hw instead of d_pmeta -- the eligible positions carry a ghost's flag there: published,
+    // never stored -- and RapidMuskingum d_coef_hw instead of d_coef: zeros at those positions, whose records k_rec_in has already routed.
+    bool hw_inpass = true;
+    std::vector<uint8_t> hw_elig;    // [np] eligible positions, with the plan's boundary reaches
+    int64_t hw_counts[4] = {0, 0, 0, 0};
+    int4 *d_pmeta_hw = nullptr;
+    double *d_coef_hw = nullptr;
+    double *d_hwcoef = nullptr;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
+    double *d_hwq = nullptr;         // [n] k_rec_in's carry: a column's discharge after the last batch turned into records; launch_state_in: the call's initial state
     std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
     int32_t n_wide_tiles = 0;        // tiles with a reach of more than three upstream reaches: general kernel beside the LEAN one
     double *d_sq = nullptr, *d_ss = nullptr, *d_si = nullptr, *d_sqch = nullptr;
@@ -287,6 +298,19 @@ int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vec
     if (!rc && !P->d_pmeta) rc = dev_alloc(&P->d_pmeta, TP.np);
     if (!rc) rc = dev_upload(P->d_tmeta, tm);
     if (!rc) rc = dev_upload(P->d_pmeta, pm);
+    // the in-pass headwaters: a ghost's flag in the short tick's own position table, a flag in the column metadata for k_rec_in
+    rr::mark_inpass_headwaters(TP, lag, kGhostBit, P->hw_elig, P->hw_counts);
+    if (!P->hw_inpass) { P->hw_elig.assign((size_t)TP.np, 0); P->hw_counts[0] = 0; }
+    for (int64_t p = 0; p < TP.np; ++p) if (P->hw_elig[p]) pm[p].x |= kTileGhostBit;
+    const rr::HostPlan &H = P->h;
+    std::vector<int2> cm((size_t)H.n);
+    for (int64_t i = 0; i < H.n; ++i)      // a headwater column is flagged: UnitMuskingum's out-pass leaves it unclamped
+        cm[i] = make_int2(TP.inv[i], (TP.lag[TP.inv[i]] & kLagMask) | (H.child_ptr[H.inv[i] + 1] == H.child_ptr[H.inv[i]] ? kColHeadwater : 0) |
+                                         (P->hw_elig[TP.inv[i]] ? kColInpass : 0));
+    if (!rc && !P->d_pmeta_hw) rc = dev_alloc(&P->d_pmeta_hw, TP.np);
+    if (!rc) rc = dev_upload(P->d_pmeta_hw, pm);
+    if (!rc && !P->d_colmeta) rc = dev_alloc(&P->d_colmeta, H.n);
+    if (!rc) rc = dev_upload(P->d_colmeta, cm);
     return rc;
 }
 
@@ -300,6 +324,17 @@ int upload_tile_coef(rr_plan *P)
     for (int32_t i : P->ghost_reach) { const int64_t p = P->tp.inv[i]; coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0; }
     int rc = dev_upload(P->d_coef, coef);
     if (rc) return rc;
+    {   // RapidMuskingum's short tick where the in-pass routes headwaters: those publish their record, as a ghost does
+        std::vector<double> hw(coef);
+        for (int64_t p = 0; p < P->tp.np; ++p)
+            if (P->hw_elig[p]) hw[3 * p] = hw[3 * p + 1] = hw[3 * p + 2] = 0.0;
+        rc = dev_upload(P->d_coef_hw, hw);
+        if (rc) return rc;
+        std::vector<double> col(3 * (size_t)P->h.n);      // (a boundary ghost's zeros: its column is not routed by the in-pass)
+        for (int64_t i = 0; i < P->h.n; ++i) for (int k = 0; k < 3; ++k) col[3 * i + k] = coef[3 * (int64_t)P->tp.inv[i] + k];
+        rc = dev_upload(P->d_hwcoef, col);
+        if (rc) return rc;
+    }
     // UnitMuskingum's short tick: a headwater publishes its lateral inflow (_numba_kernels.py:122-123), which zero coefficients do too
     for (int64_t p = 0; p < P->tp.np; ++p)
         if ((P->tp.ccnt[p] & 0xFFFFu) == 0) coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0;
@@ -769,6 +804,10 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         w.tiles = P->d_tmeta; w.pos = P->d_pmeta; w.coef = P->d_coef;
         w.sq = P->d_sq; w.ss = P->d_ss; w.si = P->d_si; w.sqch = P->d_sqch;
         w.np = (int32_t)TP.np; w.KC = (int32_t)S.KC;
+        // headwaters routed by the in-pass: the short tick of a single-member call (launch_tile_diag); RapidMuskingum fed by lateral rows
+        // has k_rec_in route them, UnitMuskingum's are final as any in-pass writes them (discharge = lateral inflow)
+        S.hw = P->hw_inpass && P->lean_enabled && nsub == 1 && S.members == 0 &&
+               (mode == Mode::Unit || (mode == Mode::Rapid && !io.runoff && !io.uh_kernel));
         if (S.members > 0) {      // an ensemble: one ring per member, the members' carried state np apart (k_tile<..., ENS>)
             if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->ring_cap) { S.open = false; return fail(RR_E_STATE, "route: the ensemble was not reserved"); }
             S.ring_stride = S.rec_chunks * kRec * TP.np;
@@ -787,10 +826,10 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
                 (long long)n, (long long)T, (long long)(S.KC * kRec), P->dp.n_tiles, P->direct_window, (long long)P->dp.n_holes, (long long)P->dp.n_exports,
                 (long long)P->dp.skel.np, P->dp.skel.n_tiles, P->dp.skel.n_levels, (long long)S.rec_chunks, (double)S.rec_chunks * kRec * P->dp.skel.np * 8 / 1e9);
     else if (getenv("RR_VERBOSE"))
-        fprintf(stderr, "rr: n=%lld T=%lld nsub=%lld tiled=%d K=%lld tiles=%d levels=%d block=%d ghosts=%lld ring_chunks=%lld (%.1f GB) rec_batches=%lld lds=%zu\n",
+        fprintf(stderr, "rr: n=%lld T=%lld nsub=%lld tiled=%d K=%lld tiles=%d levels=%d block=%d ghosts=%lld ring_chunks=%lld (%.1f GB) rec_batches=%lld lds=%zu hw_inpass=%d (%lld of %lld headwater positions)\n",
                 (long long)n, (long long)T, (long long)nsub, (int)(S.kernel == Kernel::Tile), (long long)(S.KC * kRec), P->tp.n_tiles, P->tp.n_levels, P->tp.block,
                 (long long)P->tp.n_ghost, (long long)S.rec_chunks, S.kernel == Kernel::Tile ? (double)S.rec_chunks * kRec * P->tp.np * 8 / 1e9 : 0.0,
-                (long long)S.rec_nb, tile_lds_bytes(P->wave_threads));
+                (long long)S.rec_nb, tile_lds_bytes(P->wave_threads), (int)S.hw, (long long)(S.hw ? P->hw_counts[0] : 0), (long long)P->hw_counts[1]);
     if (S.kernel == Kernel::Tick) {
         // work ring in engine order: lateral rows come in, discharge rows overwrite them in place; rows stay until the
         // outlet-most reaches have passed them
@@ -1016,7 +1055,13 @@ int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_
     } else {
         w.tile_filter = lean ? 1 : 0;
         w.coef = (lean && unit) ? coef_unit : coef;
+        const int4 *const pos = w.pos;
+        if (lean && S.hw) {      // (S.hw: the plan's own tiles) the in-pass headwaters are published, not stored: their flag and, RapidMuskingum, zero coefficients
+            w.pos = P->d_pmeta_hw;
+            if (!unit) w.coef = P->d_coef_hw;
+        }
         hipLaunchKernelGGL(tile_kernel(unit, S.nsub > 1, lean, S.mode == Mode::Muskingum), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
+        w.pos = pos;      // (no in-pass headwater in a tile the general kernel takes)
         if (lean && n_wide > 0) {
             w.tile_filter = 2; w.coef = coef;
             hipLaunchKernelGGL(tile_kernel(unit, false, false), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
@@ -1125,6 +1170,8 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     // faster (427 / 469 us per 128 rows against 419 / 434-448 at 1M reaches; a plain copy shows the same, profiles/r03_hbm_probe_*.txt)
     const dim3 gp((unsigned)((n + kRecInCols - 1) / kRecInCols));      // (the in-pass's; launch_rec_out has its own)
     const bool sub = S.nsub > 1;
+    const bool hw = in && S.hw && S.mode == Mode::Rapid;      // k_rec_in<..., HW>: the flagged columns leave as discharge
+    if (hw) { ra.hw_coef = P->d_hwcoef; ra.hw_carry = P->d_hwq; }
     hipStream_t st = rec_stream(P);
     const int aux = aux_begin(P, in ? 0 : 1, st);
     if (S.members > 0) {      // an ensemble: every member's rows in one launch, member on the grid's second dimension
@@ -1156,9 +1203,11 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
                            rec_in_uh_lds_bytes(uh_padded_taps(S.io.uh_nks), count), st, ra, ua);
     } else if (in && ra.rows_in32) {
         if (sub) hipLaunchKernelGGL((k_rec_in<true, true>), gp, dim3(kRecInThreads), 0, st, ra);
+        else if (hw) hipLaunchKernelGGL((k_rec_in<false, true, false, true>), gp, dim3(kRecInThreads), 0, st, ra);
         else hipLaunchKernelGGL((k_rec_in<false, true>), gp, dim3(kRecInThreads), 0, st, ra);
     } else if (in) {
         if (sub) hipLaunchKernelGGL(k_rec_in<true>, gp, dim3(kRecInThreads), 0, st, ra);
+        else if (hw) hipLaunchKernelGGL((k_rec_in<false, false, false, true>), gp, dim3(kRecInThreads), 0, st, ra);
         else hipLaunchKernelGGL(k_rec_in<false>, gp, dim3(kRecInThreads), 0, st, ra);
     } else {
         launch_rec_out(ra, sub, n, st);
@@ -1464,6 +1513,7 @@ int launch_state_in(rr_plan *P, const double *d_q, hipStream_t stream)
         const bool d = P->sch.kernel == Kernel::Direct;
         const int64_t np = d ? P->dp.skel.np : P->tp.np;
         if (d) HIPCHK(hipMemcpyAsync(P->d_dq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
+        if (!d && P->hw_inpass) HIPCHK(hipMemcpyAsync(P->d_hwq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));      // k_rec_in's carry starts from the call's state
         if (np > 0)
             hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, d ? P->d_ksq : P->d_sq, d ? P->d_kss : P->d_ss, d ? P->d_ksi : P->d_si, d_q,
                                d ? P->d_kperm : P->d_tperm, d ? P->d_kpmeta : P->d_pmeta, (int32_t)np);

@@ -43,6 +43,9 @@ struct RecPermArgs {
     int32_t clamp;            // k_rec_out: 0 records hold final values (sub-steps), 1 clamp at zero, 2 clamp all but headwater columns (UnitMuskingum)
     uint32_t in32_sel, out32_sel;   // byte selectors of the float32 rows (rr_plan_set_row_format): kSelNative, or kSelSwap for a big-endian file's rows
     int32_t batches;          // k_rec_in / k_rec_out: consecutive batches from `batch` on, walked by each workgroup (0 or 1: one)
+    // k_rec_in<..., HW>: the columns flagged kColInpass leave as DISCHARGE records (see k_rec_in)
+    const double *hw_coef;    // per params column {c1row, c2, c3}: the coefficients k_tile's general table holds for the column's position
+    double *hw_carry;         // per params column: the discharge of the column's last routed row, from launch to launch (the call's initial state before the first)
 };
 
 // Ensembles (rr_kernels_tile.hpp: member_chunk0): member blockIdx.y has its rows at m * row_pitch elements from the first member's and its record
@@ -64,6 +67,7 @@ __device__ __forceinline__ RecPermArgs member_args(const RecEnsArgs &e)      // 
 }
 
 constexpr int32_t kColHeadwater = 1 << 30;      // colmeta[].y: lag | this flag
+constexpr int32_t kColInpass = 1 << 29;         // colmeta[].y: a headwater the in-pass may route (rr_plan.hpp: mark_inpass_headwaters)
 
 constexpr int kRecTileRows = 16 * kRecBatch + 15;      // tick-rows behind one batch of records
 constexpr int kRecTileLd = kRecCols + 1;
@@ -140,14 +144,24 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
 // are there): the 15 tick-rows before a later batch are the last 15 of the one before it, still in LDS -- moved to the tile's top,
 // not read from HBM again (131.75 rows read per 128 at four batches instead of 143).  A later batch's row loads are all in flight
 // before the previous batch's records leave; the column metadata and scale stay in LDS for the whole walk.
-template <bool SUB, bool IN32 = false, bool ENS = false>
+// HW (RapidMuskingum, one sub-step per row, the short tick): a headwater's discharge q+ = fma(c3, q, c4dt ql) depends on its own column
+// only, and the whole column of the batch is here in LDS.  One thread per flagged column (kColInpass) walks the column's 128 tick-rows of
+// the batch in time order and replaces the scaled lateral by the discharge, so the record k_tile receives is final: the position has zero
+// coefficients and a ghost's flag in k_tile's tables of this mode, publishes the slot and never stores the record (DESIGN.md section
+// 3c).  The arithmetic is the tick's own three nested multiply-adds with the sums of a reach without upstream reaches (0.0) written out:
+// the same bits, signed zeros included.  q is carried from batch to batch in LDS and from launch to launch in a.hw_carry; the call's
+// first row starts from the caller's state, which the call puts there.  Rows outside the call keep what every column gets (0.0 * scale).  The rows a later batch of the walk
+// keeps at the tile's top are exactly those the column has not routed yet (tile rows from 143 - o on, o = lag % 16).
+template <bool SUB, bool IN32 = false, bool ENS = false, bool HW = false>
 __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS> args)
 {
+    static_assert(!HW || (!SUB && !ENS), "headwaters are routed by the in-pass only with one sub-step per row, single member");
     const RecPermArgs &a = member_args(args);
     constexpr int R = kRecTileRows, G = kRecInThreads / kRecInCols;      // G rows of the tile loaded at once
     __shared__ double tile[R * (kRecInCols + 1)];
     __shared__ int2 smeta[kRecInCols];
     __shared__ double sscale[kRecInCols];
+    __shared__ double shw[5][HW ? kRecInCols : 1];      // HW: c1row, c2, c3, q, and the scale write_records applies (1.0 to a routed column)
     const int tid = threadIdx.x;
     auto first_row = [&](int64_t tick_first) -> int64_t {      // runoff row of the tile's first tick-row
         uint32_t sub_unused;
@@ -172,9 +186,14 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
         double v[RPT];
         int2 cm = make_int2(-1, 0);
         double cs = 1.0;
+        double hc1 = 0.0, hc2 = 0.0, hc3 = 0.0, hq = 0.0;
         if (tid < kRecInCols) {
             cm = live ? a.colmeta[i] : make_int2(-1, 0);
             cs = a.scale ? a.scale[i] : 1.0;
+            if constexpr (HW) {      // (params order: these loads wait for nothing)
+                hc1 = a.hw_coef[3 * i]; hc2 = a.hw_coef[3 * i + 1]; hc3 = a.hw_coef[3 * i + 2];
+                hq = a.hw_carry[i];
+            }
         }
 #pragma unroll
         for (int q = 0; q < RPT; ++q) v[q] = load(row_first + min(r0 + q * G, need - 1));
@@ -184,9 +203,50 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
             const int64_t row = row_first + r;
             if (r < R) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && live) ? v[q] : 0.0;
         }
-        if (tid < kRecInCols) { smeta[c] = cm; sscale[c] = cs; }
+        if (tid < kRecInCols) {
+            smeta[c] = cm; sscale[c] = cs;
+            if constexpr (HW) { shw[0][c] = hc1; shw[1][c] = hc2; shw[2][c] = hc3; shw[3][c] = hq; shw[4][c] = (cm.y & kColInpass) ? 1.0 : cs; }
+        }
     }
     __syncthreads();
+    // HW: the flagged columns of the batch in the tile, lateral -> discharge.  Eight rows at a time through registers (sixteen spill), so that the
+    // serial chain is three multiply-adds per row and not an LDS round trip.
+    auto route_headwaters = [&](int64_t first) {      // first: tick-row of the tile's row 0
+        if (tid >= kRecInCols) return;
+        const int2 m = smeta[tid];
+        if (m.x < 0 || !(m.y & kColInpass)) return;
+        const double c1 = shw[0][tid], c2 = shw[1][tid], c3 = shw[2][tid], sc = sscale[tid];
+        double q = shw[3][tid];
+        const int r_first = 15 - (m.y & 15);      // the column's rows of the batch: [r_first, r_first + 128)
+        double *col = tile + r_first * (kRecInCols + 1) + tid;
+        const int64_t t_first = first + r_first;
+        constexpr int kBlk = 8;      // rows per register block
+#pragma unroll 1
+        for (int b = 0; b < kRecRows; b += kBlk) {
+            double x[kBlk];
+#pragma unroll
+            for (int k = 0; k < kBlk; ++k) x[k] = col[(b + k) * (kRecInCols + 1)] * sc;
+            const int64_t t0 = t_first + b;
+            if (t0 >= 0 && t0 + kBlk <= a.T) {
+#pragma unroll
+                for (int k = 0; k < kBlk; ++k) { q = __builtin_fma(c1, 0.0, __builtin_fma(c2, 0.0, __builtin_fma(c3, q, x[k]))); x[k] = q; }
+            } else {      // the call's first and last rows: a row outside the call is not routed
+#pragma unroll
+                for (int k = 0; k < kBlk; ++k) {
+                    const bool in = t0 + k >= 0 && t0 + k < a.T;
+                    const double qn = __builtin_fma(c1, 0.0, __builtin_fma(c2, 0.0, __builtin_fma(c3, q, x[k])));
+                    q = in ? qn : q; x[k] = in ? qn : x[k];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < kBlk; ++k) col[(b + k) * (kRecInCols + 1)] = x[k];
+        }
+        shw[3][tid] = q;
+    };
+    const double *wscale = HW ? shw[4] : sscale;      // the scale on the way out
+    // (routed as soon as a batch's tile is whole, before the next batch's loads are issued: beside sixteen loads in flight the walk's
+    // registers do not fit, and a spilled load is waited for at once)
+    if constexpr (HW) { route_headwaters(tick_first); __syncthreads(); }
     const int nb = a.batches > 1 ? a.batches : 1;
     for (int b = 1; b < nb; ++b) {
         // the next batch's tile, rows [row_next, row_next + need): its first `keep` rows are this tile's last -- 15 without sub-steps, with
@@ -200,7 +260,7 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
             const int r = keep + r0 + q * G;
             if (r < need) v[q] = load(row_next + r);
         }
-        write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, sscale);
+        write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, wscale);
 #pragma unroll
         for (int q = 0; q < KPT; ++q) {
             const int r = r0 + q * G;
@@ -220,8 +280,12 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
         }
         __syncthreads();
         tick_first = tick_next; row_first = row_next;
+        if constexpr (HW) { route_headwaters(tick_first); __syncthreads(); }
     }
-    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, sscale);
+    if constexpr (HW) {
+        if (tid < kRecInCols && live && (smeta[tid].y & kColInpass)) a.hw_carry[i] = shw[3][tid];      // (written by this thread)
+    }
+    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, wscale);
 }
 
 // The in-pass with the unit-hydrograph convolution fused in (UnitHydrograph.py:93-107, direct form): the tile is COMPUTED

@@ -377,6 +377,22 @@ void build_tile_plan(const std::vector<int32_t> &down, const std::vector<int32_t
     T.ok = true;
 }
 
+int64_t mark_inpass_headwaters(const TilePlan &T, const std::vector<int32_t> &lag, int32_t boundary_ghost, std::vector<uint8_t> &eligible, int64_t counts[4])
+{
+    eligible.assign((size_t)T.np, 0);
+    int64_t c[4] = {0, 0, 0, 0};
+    for (int64_t p = 0; p < T.np; ++p) {
+        if ((lag[p] & kTileGhost) || (T.ccnt[p] & 0xFFFFu) != 0) continue;      // a mirror position / a reach with an upstream position in its tile (a boundary ghost is one)
+        ++c[1];
+        if (lag[p] & (kTileExport | boundary_ghost)) { ++c[2]; continue; }
+        if (T.tile_flags[T.tile_of[p]] & 1) { ++c[3]; continue; }
+        eligible[p] = 1;
+        ++c[0];
+    }
+    if (counts) for (int k = 0; k < 4; ++k) counts[k] = c[k];
+    return c[0];
+}
+
 void build_direct_plan(const std::vector<int32_t> &down, const std::vector<int32_t> &lag_of, int32_t lanes, int32_t wmax, int32_t skel_block,
                        DirectPlan &D, const std::vector<uint8_t> *ghost, const std::vector<int32_t> *export_slot)
 {

@@ -104,6 +104,21 @@ struct TilePlan {
 void build_tile_plan(const std::vector<int32_t> &down, const std::vector<int32_t> &lag_of, int32_t block, TilePlan &out,
                      const std::vector<uint8_t> *big = nullptr, bool skeleton_only = false);
 
+// ---- headwaters routed by the in-pass ----
+//
+// A headwater's discharge is a recurrence in time over its own column: the in-pass (k_rec_in) can route it while the column's rows
+// are in LDS, and k_tile then only publishes the record, as it does for a ghost, and never writes it back.  Eligible is a position
+// that owns its reach (no mirror), has no upstream position in its tile, and
+//   * is not a boundary ghost of a partitioned network (`boundary_ghost`: that flag in lag[]; its record is the ghost series');
+//   * is not mirrored by a ghost of another tile (kTileExport): dropping its own store would still need the second store into the
+//     ghost's record -- those few (a headwater that hangs directly off a skeleton reach) stay with k_tile;
+//   * does not sit in a tile with a reach of more than three upstream reaches (tile_flags & 1): the general kernel routes that tile.
+// A boundary export (its slot travels in xpos[]) stays eligible: k_tile stores the export series from the record it publishes.
+// lag[np]: TilePlan::lag with the boundary flags of the plan.  counts (optional): eligible, headwater positions, excluded as mirrored
+// or boundary ghost, excluded for their tile.  Returns the number of eligible positions.
+int64_t mark_inpass_headwaters(const TilePlan &tp, const std::vector<int32_t> &lag, int32_t boundary_ghost, std::vector<uint8_t> &eligible,
+                               int64_t counts[4] = nullptr);
+
 // ---- direct tiles: rows in params order read and written by the routing kernel itself ----
 //
 // Where the params order numbers every small subtree contiguously (any depth-first post-order does: a subtree is then a

@@ -93,6 +93,13 @@ class Plan:
         return dict(ok=bool(info[0]), block=int(info[1]), positions=int(info[2]), ghosts=int(info[3]), tiles=int(info[4]),
                     levels=int(info[5]), threads=int(info[6]), batch_rows=int(info[7]))
 
+    def inpass_info(self) -> dict:
+        """Headwaters the in-pass routes, see rr_plan_inpass_info."""
+        info = np.zeros(5, dtype=np.int64)
+        check(_lib.lib().rr_plan_inpass_info(self._h, ptr(info)))
+        return dict(enabled=bool(info[0]), eligible=int(info[1]), headwater_positions=int(info[2]), mirrored_or_boundary=int(info[3]),
+                    wide_tile=int(info[4]))
+
     def tile_layout(self) -> dict:
         """Arrays of the subtree-tile layout, see rr_plan_tile_layout."""
         t = self.tile_info()
