@@ -99,7 +99,8 @@ int rr_plan_tile_info(const rr_plan *plan, int64_t info[8]);
  * records also routes the headwaters among them, and the time-tiled kernel never writes their records back.  info[0]=1 unless
  * RR_HW_INPASS=0 switched it off, [1]=eligible positions of the tile layout, [2]=positions that own a reach without an upstream
  * position in their tile, [3]=of those, left out because a ghost of another tile mirrors them or they are boundary ghosts of a
- * partitioned network, [4]=left out because their tile holds a reach with more than three upstream reaches. */
+ * partitioned network, [4]=left out because their tile holds a reach with more than three upstream reaches.  Once the plan has
+ * coefficients, a headwater whose c2 is not finite is left out of [1] as well (it is counted in [2] only). */
 int rr_plan_inpass_info(const rr_plan *plan, int64_t info[5]);
 int rr_plan_tile_layout(const rr_plan *plan, int32_t *tile_ptr, int32_t *tile_level, int32_t *perm, int32_t *lag,
                         int32_t *cfirst, uint32_t *ccnt, int32_t *xpos);

@@ -229,7 +229,7 @@ int rr_plan_inpass_info(const rr_plan *P, int64_t info[5])
     std::vector<int32_t> lag(P->tp.lag);      // with the boundary ghosts of a partitioned network, as rr_plan_set_boundary flags them
     for (int32_t i : P->ghost_reach) lag[P->tp.inv[i]] |= kGhostBit;
     std::vector<uint8_t> elig;
-    rr::mark_inpass_headwaters(P->tp, lag, kGhostBit, elig, info + 1);
+    rr::mark_inpass_headwaters(P->tp, lag, kGhostBit, elig, info + 1, P->h_coef.empty() ? nullptr : P->h_coef.data());
     return RR_OK;
 }
 
@@ -325,7 +325,9 @@ int rr_plan_set_coeffs(rr_plan *P, const double *lhs_off_data, const double *c2,
             const int32_t i = TP.perm[p];
             P->h_coef[3 * p] = c1row[H.inv[i]]; P->h_coef[3 * p + 1] = c2[i]; P->h_coef[3 * p + 2] = c3[i];
         }
-        rc = upload_tile_coef(P);
+        // which headwaters the in-pass routes depends on their coefficients: the position tables and column metadata again, then the coefficients
+        if (!P->meta_lag.empty()) rc = upload_tile_meta(P, P->meta_lag, P->meta_xpos, P->meta_flags);
+        if (!rc) rc = upload_tile_coef(P);
     }
     {   // direct row path: {c1row, c2, c3, c4dt} per column, kept on the host too (rr_plan_set_boundary lays the direct plan out again)
         P->h_dcoef.assign(4 * (size_t)n, 0.0);

@@ -178,6 +178,7 @@ struct rr_plan {
     bool hw_inpass = true;
     std::vector<uint8_t> hw_elig;    // [np] eligible positions, with the plan's boundary reaches
     int64_t hw_counts[4] = {0, 0, 0, 0};
+    std::vector<int32_t> meta_lag, meta_xpos, meta_flags;      // what upload_tile_meta last got (the boundary reaches' flags among them)
     int4 *d_pmeta_hw = nullptr;
     double *d_coef_hw = nullptr;
     double *d_hwcoef = nullptr;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
@@ -299,7 +300,9 @@ int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vec
     if (!rc) rc = dev_upload(P->d_tmeta, tm);
     if (!rc) rc = dev_upload(P->d_pmeta, pm);
     // the in-pass headwaters: a ghost's flag in the short tick's own position table, a flag in the column metadata for k_rec_in
-    rr::mark_inpass_headwaters(TP, lag, kGhostBit, P->hw_elig, P->hw_counts);
+    // (with the plan's coefficients once it has them: rr_plan_set_coeffs comes here again, mark_inpass_headwaters looks at c1row and c2)
+    rr::mark_inpass_headwaters(TP, lag, kGhostBit, P->hw_elig, P->hw_counts, P->h_coef.empty() ? nullptr : P->h_coef.data());
+    if (&lag != &P->meta_lag) { P->meta_lag = lag; P->meta_xpos = xpos; P->meta_flags = flags; }
     if (!P->hw_inpass) { P->hw_elig.assign((size_t)TP.np, 0); P->hw_counts[0] = 0; }
     for (int64_t p = 0; p < TP.np; ++p) if (P->hw_elig[p]) pm[p].x |= kTileGhostBit;
     const rr::HostPlan &H = P->h;

@@ -44,7 +44,7 @@ struct RecPermArgs {
     uint32_t in32_sel, out32_sel;   // byte selectors of the float32 rows (rr_plan_set_row_format): kSelNative, or kSelSwap for a big-endian file's rows
     int32_t batches;          // k_rec_in / k_rec_out: consecutive batches from `batch` on, walked by each workgroup (0 or 1: one)
     // k_rec_in<..., HW>: the columns flagged kColInpass leave as DISCHARGE records (see k_rec_in)
-    const double *hw_coef;    // per params column {c1row, c2, c3}: the coefficients k_tile's general table holds for the column's position
+    const double *hw_coef;    // per params column {c1row, c2, c3}: the coefficients k_tile's general table holds for the column's position (the walk reads c3)
     double *hw_carry;         // per params column: the discharge of the column's last routed row, from launch to launch (the call's initial state before the first)
 };
 
@@ -108,14 +108,16 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
         }
     }
     const uint32_t chunk_first = a.rec_chunks.mod((uint32_t)kRecBatch * (uint32_t)batch);
-#pragma unroll(LDSMETA ? (SUB ? 2 : 4) : IT)
+    // LDSMETA (k_rec_in): every column of the tile is one to store (a column past the end is a replica of the last), and without sub-steps
+    // the stores are one straight run that no lane skips: the waits for loads issued before them can count them
+#pragma unroll(LDSMETA ? (SUB ? 2 : IT) : IT)
     for (int it = 0; it < IT; ++it) {
         const int piece = it * THREADS + tid;       // (column, record, 16-byte part): 8 consecutive lanes = one record
         const int c = piece / (8 * BATCH), k = (piece >> 3) % BATCH, part = piece & 7;
         const int2 m = LDSMETA ? smeta[c] : meta[LDSMETA ? 0 : it];
         const double scale = LDSMETA ? sscale[c] : f[LDSMETA ? 0 : it];
         const int32_t p = m.x;
-        if (p < 0) continue;
+        if (!LDSMETA && p < 0) continue;
         const int32_t lag = m.y & kLagMask;
         const int o = lag & 15;
         const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)(lag >> 4) + k);
@@ -144,24 +146,47 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
 // are there): the 15 tick-rows before a later batch are the last 15 of the one before it, still in LDS -- moved to the tile's top,
 // not read from HBM again (131.75 rows read per 128 at four batches instead of 143).  A later batch's row loads are all in flight
 // before the previous batch's records leave; the column metadata and scale stay in LDS for the whole walk.
+// Nothing in the batch loop may wait for those stores before it has to (the memory counter retires loads and stores in the order
+// they were issued, and hipcc counts only what it can prove was issued), so, without sub-steps, every load and store of the pass is
+// issued by every lane on every path:
+//   * a column past the network's end is a REPLICA of column n - 1 (its loads are clamped there anyway): same rows, metadata, scale and
+//     walk, and the same records stored to the same addresses -- no lane skips a store, and only the last tile has replicas;
+//   * the tile is padded to a whole number of row groups (144 rows), so the first batch's last load is written by every lane instead of
+//     staying pending in the lanes past row 142 (a register with a load pending is waited for when it is next written: that was the
+//     wait at the top of the batch loop's load block);
+//   * the eight record stores of a batch are one straight run, so the waits for the next batch's sixteen loads count them: the first
+//     row is waited for with 23 operations still outstanding, the last with the eight stores.
+// What a thread derives from its number (column, row group, addresses) is rebuilt from fresh_tid(tid) where it is used: kept across the batch
+// loop those were 34 registers of hoisted row numbers, and the spills they caused were reloaded inside the loop -- a reload is a memory
+// operation too and returns behind every store before it.
 // HW (RapidMuskingum, one sub-step per row, the short tick): a headwater's discharge q+ = fma(c3, q, c4dt ql) depends on its own column
 // only, and the whole column of the batch is here in LDS.  One thread per flagged column (kColInpass) walks the column's 128 tick-rows of
 // the batch in time order and replaces the scaled lateral by the discharge, so the record k_tile receives is final: the position has zero
 // coefficients and a ghost's flag in k_tile's tables of this mode, publishes the slot and never stores the record (DESIGN.md section
-// 3c).  The arithmetic is the tick's own three nested multiply-adds with the sums of a reach without upstream reaches (0.0) written out:
-// the same bits, signed zeros included.  q is carried from batch to batch in LDS and from launch to launch in a.hw_carry; the call's
-// first row starts from the caller's state, which the call puts there.  Rows outside the call keep what every column gets (0.0 * scale).  The rows a later batch of the walk
-// keeps at the tile's top are exactly those the column has not routed yet (tile rows from 143 - o on, o = lag % 16).
+// 3c).  The arithmetic is the tick's own, q+ = fma(c1row, 0.0, fma(c2, 0.0, r)) with r = fma(c3, q, x) and the sums of a reach without
+// upstream reaches (0.0) written out, evaluated as q+ = r + 0.0 -- the same double, bit for bit, for the columns the plan flags
+// (mark_inpass_headwaters: c1row is +0.0 and c2 is finite, both tested on the bits):
+//   c2 finite: c2 * 0.0 is a zero of either sign, so the inner fma is r + (+-0.0): r itself when r is not a zero (an infinity stays, a
+//   NaN stays a NaN), a zero of some sign when r is one.  c1row = +0.0: c1row * 0.0 = +0.0, so the outer fma adds +0.0 to that: unchanged
+//   when it is not a zero, and +0.0 when it is (round to nearest: -0.0 + +0.0 = +0.0).  r + 0.0 is r when r is not a zero and +0.0 when it is.
+// Two dependent operations per row instead of three; nothing else is reassociated.  q is carried from batch to batch in LDS and from launch
+// to launch in a.hw_carry; the call's first row starts from the caller's state, which the call puts there.  Rows outside the call keep what
+// every column gets (0.0 * scale).  The rows a later batch of the walk keeps at the tile's top are exactly those the column has not routed
+// yet (tile rows from 143 - o on, o = lag % 16).
+__device__ __forceinline__ int32_t fresh_tid(int32_t v) { asm volatile("" : "+v"(v)); return v; }      // (rr_kernels_tile.hpp: fresh)
+
 template <bool SUB, bool IN32 = false, bool ENS = false, bool HW = false>
 __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS> args)
 {
     static_assert(!HW || (!SUB && !ENS), "headwaters are routed by the in-pass only with one sub-step per row, single member");
     const RecPermArgs &a = member_args(args);
     constexpr int R = kRecTileRows, G = kRecInThreads / kRecInCols;      // G rows of the tile loaded at once
-    __shared__ double tile[R * (kRecInCols + 1)];
+    constexpr int RPT = (R + G - 1) / G;
+    static_assert((kRecInCols & (kRecInCols - 1)) == 0 && (G & (G - 1)) == 0, "column and row group of a thread are bit fields of its number");
+    __shared__ double tile[RPT * G * (kRecInCols + 1)];      // R rows and the padding of the last row group
     __shared__ int2 smeta[kRecInCols];
     __shared__ double sscale[kRecInCols];
-    __shared__ double shw[5][HW ? kRecInCols : 1];      // HW: c1row, c2, c3, q, and the scale write_records applies (1.0 to a routed column)
+    __shared__ double shw[3][HW ? kRecInCols : 1];      // HW: c3, q, and the scale write_records applies (1.0 to a routed column)
     const int tid = threadIdx.x;
     auto first_row = [&](int64_t tick_first) -> int64_t {      // runoff row of the tile's first tick-row
         uint32_t sub_unused;
@@ -169,56 +194,51 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
     };
     int64_t tick_first = kRecRows * a.batch - 15;                 // may be negative in the first batch
     int64_t row_first = first_row(tick_first);
-    constexpr int RPT = (R + G - 1) / G;
-    const int c = tid % kRecInCols, r0 = tid / kRecInCols;
     const int need = SUB ? (int)((uint32_t)(R - 1) / a.nsub.d) + 2 : R;     // runoff rows behind the batch's tick-rows
     const uint32_t n_tiles = (uint32_t)((a.n + kRecInCols - 1) / kRecInCols);
     if (blockIdx.x >= n_tiles) return;
     const int64_t col0 = (int64_t)(a.swizzle ? xcd_swizzle(blockIdx.x, n_tiles) : blockIdx.x) * kRecInCols;
-    // branch-free: out-of-range rows / columns are clamped here and zeroed on the way into LDS
-    const int64_t i = min(col0 + c, a.n - 1);
-    const bool live = col0 + c < a.n;
-    auto load = [&](int64_t t) -> double {
+    // branch-free: out-of-range rows are clamped here and zeroed on the way into LDS; a column past the end is column n - 1 once more
+    auto col_of = [&](int t) -> int64_t { return min(col0 + (t & (kRecInCols - 1)), a.n - 1); };
+    auto group_of = [](int t) -> int { return (t / kRecInCols) & (G - 1); };
+    auto load = [&](int64_t t, int64_t i) -> double {
         const int64_t off = a.rows.offset(t < 0 ? 0 : (t >= a.T ? a.T - 1 : t)) + i;
         return IN32 ? (double)f32_from_file(a.rows_in32[off], a.in32_sel) : a.rows.base[off];
     };
     {
+        const int c = tid & (kRecInCols - 1), r0 = group_of(tid);
+        const int64_t i = col_of(tid);
         double v[RPT];
-        int2 cm = make_int2(-1, 0);
-        double cs = 1.0;
-        double hc1 = 0.0, hc2 = 0.0, hc3 = 0.0, hq = 0.0;
-        if (tid < kRecInCols) {
-            cm = live ? a.colmeta[i] : make_int2(-1, 0);
-            cs = a.scale ? a.scale[i] : 1.0;
-            if constexpr (HW) {      // (params order: these loads wait for nothing)
-                hc1 = a.hw_coef[3 * i]; hc2 = a.hw_coef[3 * i + 1]; hc3 = a.hw_coef[3 * i + 2];
-                hq = a.hw_carry[i];
-            }
-        }
+        // the column's words first, by every thread (the row loads' waits then cover them on every path); thread c puts them into LDS
+        const int2 cm = a.colmeta[i];
+        const double cs = a.scale ? a.scale[i] : 1.0;
+        double hc3 = 0.0, hq = 0.0;
+        if constexpr (HW) { hc3 = a.hw_coef[3 * i + 2]; hq = a.hw_carry[i]; }      // (params order: these loads wait for nothing)
 #pragma unroll
-        for (int q = 0; q < RPT; ++q) v[q] = load(row_first + min(r0 + q * G, need - 1));
+        for (int q = 0; q < RPT; ++q) v[q] = load(row_first + min(r0 + q * G, need - 1), i);
 #pragma unroll
         for (int q = 0; q < RPT; ++q) {
             const int r = r0 + q * G;
             const int64_t row = row_first + r;
-            if (r < R) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && live) ? v[q] : 0.0;
+            tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T) ? v[q] : 0.0;      // (r < RPT * G: the padding is written, never read)
         }
         if (tid < kRecInCols) {
             smeta[c] = cm; sscale[c] = cs;
-            if constexpr (HW) { shw[0][c] = hc1; shw[1][c] = hc2; shw[2][c] = hc3; shw[3][c] = hq; shw[4][c] = (cm.y & kColInpass) ? 1.0 : cs; }
+            if constexpr (HW) { shw[0][c] = hc3; shw[1][c] = hq; shw[2][c] = (cm.y & kColInpass) ? 1.0 : cs; }
         }
     }
     __syncthreads();
-    // HW: the flagged columns of the batch in the tile, lateral -> discharge.  Eight rows at a time through registers (sixteen spill), so that the
-    // serial chain is three multiply-adds per row and not an LDS round trip.
+    // HW: the flagged columns of the batch in the tile, lateral -> discharge.  Eight rows at a time through registers, so that the
+    // serial chain is a multiply-add and an add per row and not an LDS round trip.
     auto route_headwaters = [&](int64_t first) {      // first: tick-row of the tile's row 0
-        if (tid >= kRecInCols) return;
-        const int2 m = smeta[tid];
-        if (m.x < 0 || !(m.y & kColInpass)) return;
-        const double c1 = shw[0][tid], c2 = shw[1][tid], c3 = shw[2][tid], sc = sscale[tid];
-        double q = shw[3][tid];
+        const int t = fresh_tid(tid);
+        if (t >= kRecInCols) return;
+        const int2 m = smeta[t];
+        if (!(m.y & kColInpass)) return;
+        const double c3 = shw[0][t], sc = sscale[t];
+        double q = shw[1][t];
         const int r_first = 15 - (m.y & 15);      // the column's rows of the batch: [r_first, r_first + 128)
-        double *col = tile + r_first * (kRecInCols + 1) + tid;
+        double *col = tile + r_first * (kRecInCols + 1) + t;
         const int64_t t_first = first + r_first;
         constexpr int kBlk = 8;      // rows per register block
 #pragma unroll 1
@@ -229,23 +249,23 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
             const int64_t t0 = t_first + b;
             if (t0 >= 0 && t0 + kBlk <= a.T) {
 #pragma unroll
-                for (int k = 0; k < kBlk; ++k) { q = __builtin_fma(c1, 0.0, __builtin_fma(c2, 0.0, __builtin_fma(c3, q, x[k]))); x[k] = q; }
+                for (int k = 0; k < kBlk; ++k) { q = __builtin_fma(c3, q, x[k]) + 0.0; x[k] = q; }
             } else {      // the call's first and last rows: a row outside the call is not routed
 #pragma unroll
                 for (int k = 0; k < kBlk; ++k) {
                     const bool in = t0 + k >= 0 && t0 + k < a.T;
-                    const double qn = __builtin_fma(c1, 0.0, __builtin_fma(c2, 0.0, __builtin_fma(c3, q, x[k])));
+                    const double qn = __builtin_fma(c3, q, x[k]) + 0.0;
                     q = in ? qn : q; x[k] = in ? qn : x[k];
                 }
             }
 #pragma unroll
             for (int k = 0; k < kBlk; ++k) col[(b + k) * (kRecInCols + 1)] = x[k];
         }
-        shw[3][tid] = q;
+        shw[1][t] = q;
     };
-    const double *wscale = HW ? shw[4] : sscale;      // the scale on the way out
+    const double *wscale = HW ? shw[2] : sscale;      // the scale on the way out
     // (routed as soon as a batch's tile is whole, before the next batch's loads are issued: beside sixteen loads in flight the walk's
-    // registers do not fit, and a spilled load is waited for at once)
+    // registers do not fit)
     if constexpr (HW) { route_headwaters(tick_first); __syncthreads(); }
     const int nb = a.batches > 1 ? a.batches : 1;
     for (int b = 1; b < nb; ++b) {
@@ -254,11 +274,15 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
         constexpr int NPT = kRecRows / G, KPT = 3;      // new rows (at most 128) / kept rows per thread
         const int64_t tick_next = tick_first + kRecRows, row_next = first_row(tick_next);
         const int shift = (int)(row_next - row_first), keep = max(need - shift, 0);
+        const int t = fresh_tid(tid), c = t & (kRecInCols - 1), r0 = group_of(t);
         double v[NPT], kv[KPT];
+        {
+            const int64_t i = col_of(t);
 #pragma unroll
-        for (int q = 0; q < NPT; ++q) {
-            const int r = keep + r0 + q * G;
-            if (r < need) v[q] = load(row_next + r);
+            for (int q = 0; q < NPT; ++q) {
+                const int r = keep + r0 + q * G;      // without sub-steps 15 + r0 + 8 q < 143: every lane loads
+                if (!SUB || r < need) v[q] = load(row_next + r, i);
+            }
         }
         write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, wscale);
 #pragma unroll
@@ -276,14 +300,15 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
         for (int q = 0; q < NPT; ++q) {
             const int r = keep + r0 + q * G;
             const int64_t row = row_next + r;
-            if (r < need) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T && live) ? v[q] : 0.0;
+            if (!SUB || r < need) tile[r * (kRecInCols + 1) + c] = (row >= 0 && row < a.T) ? v[q] : 0.0;
         }
         __syncthreads();
         tick_first = tick_next; row_first = row_next;
         if constexpr (HW) { route_headwaters(tick_first); __syncthreads(); }
     }
     if constexpr (HW) {
-        if (tid < kRecInCols && live && (smeta[tid].y & kColInpass)) a.hw_carry[i] = shw[3][tid];      // (written by this thread)
+        const int t = fresh_tid(tid);
+        if (t < kRecInCols && col0 + t < a.n && (smeta[t].y & kColInpass)) a.hw_carry[col0 + t] = shw[1][t];      // (written by this thread; a replica writes nothing)
     }
     write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, wscale);
 }

@@ -1,7 +1,9 @@
 #include "rr_plan.hpp"
 
 #include <algorithm>
+#include <cstdint>
 #include <cstdlib>
+#include <cstring>
 #include <limits>
 #include <utility>
 #include <vector>
@@ -377,15 +379,21 @@ void build_tile_plan(const std::vector<int32_t> &down, const std::vector<int32_t
     T.ok = true;
 }
 
-int64_t mark_inpass_headwaters(const TilePlan &T, const std::vector<int32_t> &lag, int32_t boundary_ghost, std::vector<uint8_t> &eligible, int64_t counts[4])
+int64_t mark_inpass_headwaters(const TilePlan &T, const std::vector<int32_t> &lag, int32_t boundary_ghost, std::vector<uint8_t> &eligible, int64_t counts[4],
+                               const double *coef)
 {
     eligible.assign((size_t)T.np, 0);
     int64_t c[4] = {0, 0, 0, 0};
+    auto bits = [](double x) { uint64_t u; std::memcpy(&u, &x, sizeof u); return u; };
+    auto plain_coef = [&](int64_t p) {      // c1row is +0.0 (all bits clear) and c2 is finite (exponent not all ones)
+        return bits(coef[3 * p]) == 0 && (bits(coef[3 * p + 1]) & 0x7FF0000000000000ull) != 0x7FF0000000000000ull;
+    };
     for (int64_t p = 0; p < T.np; ++p) {
         if ((lag[p] & kTileGhost) || (T.ccnt[p] & 0xFFFFu) != 0) continue;      // a mirror position / a reach with an upstream position in its tile (a boundary ghost is one)
         ++c[1];
         if (lag[p] & (kTileExport | boundary_ghost)) { ++c[2]; continue; }
         if (T.tile_flags[T.tile_of[p]] & 1) { ++c[3]; continue; }
+        if (coef && !plain_coef(p)) continue;
         eligible[p] = 1;
         ++c[0];
     }

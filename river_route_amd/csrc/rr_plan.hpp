@@ -114,10 +114,14 @@ void build_tile_plan(const std::vector<int32_t> &down, const std::vector<int32_t
 //     ghost's record -- those few (a headwater that hangs directly off a skeleton reach) stay with k_tile;
 //   * does not sit in a tile with a reach of more than three upstream reaches (tile_flags & 1): the general kernel routes that tile.
 // A boundary export (its slot travels in xpos[]) stays eligible: k_tile stores the export series from the record it publishes.
+// coef (optional, [3 np] {c1row, c2, c3} per position, once the plan has coefficients): a position also needs
+//   * c1row == +0.0 and c2 finite, both tested on the bits: the in-pass evaluates the tick's fma(c1row, 0.0, fma(c2, 0.0, r)) as
+//     r + 0.0 (k_rec_in), which is the same double exactly under these two conditions -- a headwater's c1row always is +0.0
+//     (DESIGN.md section 3c); one that fails (a caller's non-finite c2) stays with k_tile and is counted as a headwater only.
 // lag[np]: TilePlan::lag with the boundary flags of the plan.  counts (optional): eligible, headwater positions, excluded as mirrored
 // or boundary ghost, excluded for their tile.  Returns the number of eligible positions.
 int64_t mark_inpass_headwaters(const TilePlan &tp, const std::vector<int32_t> &lag, int32_t boundary_ghost, std::vector<uint8_t> &eligible,
-                               int64_t counts[4] = nullptr);
+                               int64_t counts[4] = nullptr, const double *coef = nullptr);
 
 // ---- direct tiles: rows in params order read and written by the routing kernel itself ----
 //
