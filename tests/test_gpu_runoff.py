@@ -66,7 +66,8 @@ def test_large_block_and_bad_arguments():
     assert _lib.lib().rr_runoff_to_qlateral(0, 10, 10, 5, None, None, None, None, 0, 1, 5, None, 0, None) < 0
 
 
-@pytest.mark.parametrize('dtype,cumulative,clip', [(np.float32, False, False), (np.float64, True, True), (np.float32, True, False)])
+@pytest.mark.parametrize('dtype,cumulative,clip', [(np.float32, False, False), (np.float64, True, True), (np.float32, True, False),
+                                                   (np.float64, False, True)])
 @pytest.mark.parametrize('n_rivers,T,factor', [(60_000, 200, 1), (60_000, 256, 4)])
 def test_routing_fed_by_gridded_runoff_in_one_call(n_rivers, T, factor, dtype, cumulative, clip):
     """rr_rapid_route_runoff_dev: runoff.py:288-332 + RapidMuskingum._router with the catchment inflow computed on its way into

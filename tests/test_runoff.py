@@ -246,14 +246,44 @@ from test_routers import backend, case, drive  # noqa: E402,F401  (fixtures)
 import river_route_amd as rr  # noqa: E402
 
 
+def count_runoff_paths(monkeypatch):
+    """Plan.rapid_route_runoff_dev (the fused call) and engine.runoff_to_qlateral_dev (the first of the two steps) wrapped, not
+    replaced: {'fused': completed calls, 'refused': the codes of those that raised, 'two_step': completed calls}."""
+    from river_route_amd import engine
+    from river_route_amd._lib import RRError
+    calls = dict(fused=0, refused=[], two_step=0)
+    fused, two_step = engine.Plan.rapid_route_runoff_dev, engine.runoff_to_qlateral_dev
+
+    def fused_counted(self, *args, **kw):
+        try:
+            fused(self, *args, **kw)
+        except RRError as e:
+            calls['refused'].append(e.code)
+            raise
+        calls['fused'] += 1
+
+    def two_step_counted(*args, **kw):
+        two_step(*args, **kw)
+        calls['two_step'] += 1
+    monkeypatch.setattr(engine.Plan, 'rapid_route_runoff_dev', fused_counted)
+    monkeypatch.setattr(engine, 'runoff_to_qlateral_dev', two_step_counted)
+    return calls
+
+
 @pytest.mark.parametrize('router', ['rapid', 'rapid_one_step', 'unit'])
 def test_router_with_grid_runoff_files(backend, case, tmp_path, monkeypatch, router):
     """RapidMuskingum (UnitMuskingum) configured with grid_runoff_files + grid_weights_file routes exactly what it routes
     when handed the oracle's catchment volumes (depths) for the same grids."""
     from river_route_amd import engine
+    from river_route_amd._lib import RR_E_UNSUPPORTED
     from test_routers import _unit_files
     cls = rr.UnitMuskingum if router == 'unit' else rr.RapidMuskingum
-    extra = dict(dt_routing=900) if router == 'rapid' else {}      # one routing step per runoff step: the fused in-pass on the GPU
+    # 'rapid': four routing steps per (hourly) runoff step, the two-step form by design.  'rapid_one_step': one routing step per
+    # runoff step, where the router tries the fused in-pass -- but the case's files have 24 rows, fewer than the 32 ticks the
+    # time-tiled kernel needs: on the GPU the fused call answers RR_E_UNSUPPORTED and the router falls back to the two-step form
+    # (asserted below; test_router_grid_runoff_through_the_fused_call has files long enough for the fused call)
+    extra = dict(dt_routing=900) if router == 'rapid' else {}
+    calls = count_runoff_paths(monkeypatch) if backend == 'hip' else None
     if router == 'unit':
         kp, us = _unit_files(case)
         extra = dict(dt_routing=1200, uh_kernel_file=kp, uh_state_init_file=us)
@@ -300,3 +330,74 @@ def test_router_with_grid_runoff_files(backend, case, tmp_path, monkeypatch, rou
         np.testing.assert_allclose(q, qw, rtol=1.2e-7, atol=1e-10 * float(np.abs(qw).max()))
         assert rf in files and os.path.basename(f_).startswith('discharge_grid')
     np.testing.assert_allclose(r.channel_state, r_ref.channel_state, rtol=1e-10, atol=1e-10 * np.abs(r_ref.channel_state).max())
+    if calls is not None:      # which path ran, per file
+        want_calls = {'rapid': dict(fused=0, refused=[], two_step=2), 'unit': dict(fused=0, refused=[], two_step=2),
+                      'rapid_one_step': dict(fused=0, refused=[RR_E_UNSUPPORTED] * 2, two_step=2)}[router]
+        assert calls == want_calls
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('per,cumulative,fused', [(1, False, True), (4, True, True), (3, False, False)])
+def test_router_grid_runoff_through_the_fused_call(case, tmp_path, monkeypatch, per, cumulative, fused):
+    """RapidMuskingum on two grid-runoff files of 96 rows at dt_runoff = dt_routing = 900 s: long enough for the time-tiled kernel, so
+    RapidMuskingum._router_device_runoff returns from rr_rapid_route_runoff_dev (arena uploads, dtypes of the CSR arrays,
+    source.flags, float32 means of `per` rows, the final state's download) -- except with three rows per output row, which do not
+    divide a record batch of 128: the fused call answers RR_E_UNSUPPORTED and the two-step form runs.  The reference is the same
+    router with the oracle engine injected, driven with brute_force volumes for the same grids.  One fused case has
+    grid_accumulation_type='cumulative' (RUNOFF_CUMULATIVE in prepare_runoff); the router config has no option that sets
+    RUNOFF_FORCE_POSITIVE (prepare_runoff's force_positive_runoff is not reachable from Configs), so that flag reaches the fused call
+    in tests/test_gpu_runoff_inpass.py only."""
+    from river_route_amd._lib import RR_E_UNSUPPORTED
+    from test_routers import OraclePlan, musk_mod
+    river_ids = case['g']['river_ids']
+    rng = np.random.default_rng(22)
+    nx, ny, T, dt = 9, 6, 96, 900
+    rows = []
+    for rid in river_ids:                         # table in params order = the order the routers need
+        for c in rng.choice(nx * ny, size=int(rng.integers(1, 4)), replace=False):
+            rows.append((rid, c % nx, c // nx, float(rng.random()), float(rng.uniform(1e5, 1e7))))
+    tab = np.array(rows)
+    wfile = tmp_path / 'weights96.nc'
+    write_nc3(wfile, {'index': len(rows)}, {
+        'river_id': (('index',), tab[:, 0].astype(np.int64), {}), 'x_index': (('index',), tab[:, 1].astype(np.int64), {}),
+        'y_index': (('index',), tab[:, 2].astype(np.int64), {}), 'proportion': (('index',), tab[:, 3], {}),
+        'area_sqm': (('index',), tab[:, 4], {})})
+    start = case['dates'][0][0]
+    files, series, dates = [], [], []
+    for f in range(2):                            # time axes of their own: the case's dates cover 24 hourly rows
+        grid = (rng.random((T, ny, nx)) * 1e-3).astype(np.float32)
+        if cumulative:
+            grid = np.cumsum(grid, axis=0).astype(np.float32)
+        dates.append(start + (dt * (f * T + np.arange(T))).astype('timedelta64[s]'))
+        secs = (dates[f] - np.datetime64('1970-01-01T00:00:00')).astype('timedelta64[s]').astype(np.float64)
+        p = tmp_path / f'grid96_{f}.nc'
+        write_nc3(p, {'time': T, 'y': ny, 'x': nx}, {
+            'time': (('time',), secs, {'units': 'seconds since 1970-01-01 00:00:00'}),
+            'ro': (('time', 'y', 'x'), grid, {'units': 'm'})})
+        files.append(str(p))
+        series.append(brute_force(tab, grid, 1.0, cumulative, False, True)[1])
+    cfg = dict(channel_state_init_file=case['init'], dt_routing=dt, dt_discharge=per * dt)
+
+    calls = count_runoff_paths(monkeypatch)
+    got = []
+    r = rr.RapidMuskingum(params_file=case['params'], grid_runoff_files=files, grid_weights_file=str(wfile), discharge_dir=str(tmp_path),
+                          grid_accumulation_type='cumulative' if cumulative else 'incremental', log=False, **cfg)
+    r.set_write_discharges(lambda d, q, f_, rf='': got.append((np.asarray(d), np.asarray(q))))
+    r.route()
+    assert r.num_routing_steps_per_runoff == 1 and r.num_runoff_steps == T and r.num_runoff_steps_per_discharge == per
+    print(f'per={per} cumulative={cumulative}: {calls}, last kernel {r._plan.last_kernel()}')
+    if fused:
+        assert calls == dict(fused=2, refused=[], two_step=0)
+        assert r._plan.last_kernel() not in ('direct', 'tick')
+    else:
+        assert calls == dict(fused=0, refused=[RR_E_UNSUPPORTED] * 2, two_step=2)
+
+    with monkeypatch.context() as m:              # the reference: the oracle in the engine's place
+        m.setattr(musk_mod, 'Plan', OraclePlan)
+        r_ref, want = drive(rr.RapidMuskingum, dict(case, dates=dates), series, **cfg)
+    assert len(got) == len(want) == 2
+    for (d, q), (dw, qw, _, _) in zip(got, want):
+        assert q.dtype == np.float32 and q.shape == (T // per, len(river_ids))
+        np.testing.assert_array_equal(d, dw)
+        np.testing.assert_allclose(q, qw, rtol=1.2e-7, atol=1e-10 * float(np.abs(qw).max()))
+    assert_close(r.channel_state, r_ref.channel_state, 'final state after the second file')
