@@ -12,9 +12,11 @@ constexpr int64_t kAdjMaxMembers = 65535;     // members of a batched call: a gr
 // What differs between the two routers outside the kernels: the name of the sizing entry point (the errors name it) and two row counts
 // of the work memory: sums per reach in the reduction (c1..c4 / c1..c3) and scratch rows (the tick's running sum and its discarded
 // discharge row; Unit adds q_ch, updated in place, q_ch0, dL/d(q_ch final) and dL/d(q_full final) in engine order).
-struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; bool batch = false; };      // batch: the member-batched entry points
+// batch: the member-batched entry points; gauges: rr_rapid_adjoint_gauges_*, dL/d(discharge) at gauged reaches only
+struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; bool batch = false, gauges = false; };
 constexpr AdjointKind kRapidAdjoint{"rr_rapid_adjoint_work_bytes", 4, 2};
 constexpr AdjointKind kRapidAdjointBatch{"rr_rapid_adjoint_batch_work_bytes", 4, 2, true};
+constexpr AdjointKind kRapidAdjointGauges{"rr_rapid_adjoint_gauges_work_bytes", 4, 2, true, true};
 constexpr AdjointKind kUnitAdjoint{"rr_unit_adjoint_work_bytes", 3, 6};
 constexpr AdjointKind kUnitAdjointBatch{"rr_unit_adjoint_batch_work_bytes", 3, 6, true};
 
@@ -23,13 +25,18 @@ constexpr AdjointKind kUnitAdjointBatch{"rr_unit_adjoint_batch_work_bytes", 3, 6
 // order), lateral rows and gradient rows in engine order (T rows each), the permutation's intermediate rows, the reduction slab
 // (slab_rows x n per sub-step range), the scratch rows.  A batched call (members > 1) has every section but the permutation's rows
 // once per member, member m's part m pitches into the section: with one member this is the single call's layout, byte for byte.
+// A gauge call (n_gauges > 0) keeps its masked (T, n_gauges) blocks, members adjacent, in the permutation's rows, which grow to hold
+// them: the rows are idle from the lateral rows' permutation to the gradient rows', and the reverse ticks, which read the blocks, lie
+// between.  Its slot map (2 n int32) lives in member 0's scratch rows, idle once the replay is done.  Without grad_rows (no
+// grad_lateral) it has no gradient rows.
 struct AdjointLayout {
     int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
     int64_t chunk, splits, steps_per_split;
     int64_t qtape_pitch, mtape_pitch, row_pitch, slab_pitch, scratch_pitch;      // doubles from one member's part to the next
 };
 
-AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, const AdjointKind &K, int64_t members = 1)
+AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, const AdjointKind &K, int64_t members = 1,
+                             int64_t n_gauges = 0, bool grad_rows = true)
 {
     AdjointLayout L{};
     const int64_t S = T * nsub;
@@ -45,8 +52,8 @@ AdjointLayout adjoint_layout(int64_t n, int64_t depth, int64_t T, int64_t nsub, 
     L.mtape = L.qtape + members * L.qtape_pitch;
     L.lat = L.mtape + members * L.mtape_pitch;
     L.grad = L.lat + members * L.row_pitch;
-    L.mrows = L.grad + members * L.row_pitch;
-    L.slab = L.mrows + L.chunk * n;
+    L.mrows = L.grad + (grad_rows ? members * L.row_pitch : 0);
+    L.slab = L.mrows + std::max(L.chunk * n, members * T * n_gauges);
     L.scratch = L.slab + members * L.slab_pitch;
     L.total = L.scratch + members * L.scratch_pitch;
     return L;
@@ -85,6 +92,9 @@ struct AdjointCall {
     // for all), lateral / grad_lateral rows and discharge / grad_out rows to the next's; for UnitMuskingum, whose states have n_inner
     // values, state_pitch instead of q0_pitch (0: one q_ch0 and one q_full0 for all).  The single-member entry points leave these as they are.
     int64_t members = 1, q0_pitch = 0, lat_pitch = 0, out_pitch = 0, state_pitch = 0;
+    // a gauge call (rr_rapid_adjoint_gauges_*): discharge and grad_out are (T, n_gauges) at reaches gauges[] (out_pitch: the gauge pitch);
+    // grad_rows: the work memory has gradient rows (the sizer's with_grad_lateral; in a *_dev call, grad_lateral is given)
+    int64_t n_gauges = 0; const int32_t *gauges = nullptr; bool grad_rows = true;
     // set by adjoint_check
     int64_t n, S, dmax, ticks;
     bool one;                                                       // nsub == 1: the kernels' SINGLE_SUBSTEP forms
@@ -99,7 +109,11 @@ struct AdjointCall {
                 permute_rows_via(P, which, RowView{const_cast<double *>(src) + m * src_pitch, n, 0, (uint32_t)T},
                                  RowView{dst + m * dst_pitch, n, 0, (uint32_t)T}, t0, (int)std::min<int64_t>(L.chunk, T - t0), mrows, st);
     }
-    const double *egrad_out() const { return grad_out ? egrad : nullptr; }      // masked dL/d(discharge) in engine order
+    // masked dL/d(discharge): (T, n) in engine order, or a gauge call's (T, n_gauges) blocks
+    const double *egrad_out() const { return !grad_out ? nullptr : n_gauges ? gblock() : egrad; }
+    double *gblock() const { return mrows; }
+    int32_t *pslot() const { return reinterpret_cast<int32_t *>(scratch); }      // params order; the engine-order map follows it
+    int32_t *slot() const { return pslot() + n; }
     dim3 reduce_grid() const { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits, (unsigned)members); }
 };
 
@@ -139,13 +153,14 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     const int64_t n = H.n, T = c.T, nsub = c.nsub;
     if (T < 1 || nsub < 1 || nsub > 0x7FFFFFFF) return no(RR_E_INVALID, ": need T >= 1 and sub-steps >= 1");
     if (T * nsub + H.depth > 0x7FFFFFFFLL) return no(RR_E_INVALID, ": too many sub-steps for one call: split the series into windows");
+    if (K.gauges && (c.n_gauges < 1 || c.n_gauges > n)) return no(RR_E_INVALID, ": need 1 <= n_gauges <= n");
     const auto members_ok = [&] { return c.members >= 1 && c.members <= kAdjMaxMembers; };
     if (sizing) {
         if (!members_ok()) return no(RR_E_INVALID, ": need 1 <= members <= 65535");
         HIPCHK(hipSetDevice(P->device));
         if (n == 0) return RR_OK;
         if (int rc = adjoint_ready(P)) return rc;
-        *bytes = adjoint_layout(n, H.depth, T, nsub, K, c.members).total * (int64_t)sizeof(double);
+        *bytes = adjoint_layout(n, H.depth, T, nsub, K, c.members, c.n_gauges, c.grad_rows).total * (int64_t)sizeof(double);
         return RR_OK;
     }
     if (int rc = own(AdjOwn::Wanted)) return rc;
@@ -154,10 +169,12 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     if (c.grad_out && !c.discharge) return no(RR_E_INVALID, ": grad_out needs the discharge of the forward call (its clamp mask)");
     if (int rc = own(AdjOwn::GradOut)) return rc;
     if (!members_ok()) return no(RR_E_INVALID, ": need 1 <= members <= 65535");
-    if (K.batch && ((c.q0_pitch != 0 && c.q0_pitch < n) || (c.lateral && c.lat_pitch < T * n) || ((c.discharge || c.grad_out) && c.out_pitch < T * n)))
-        return no(RR_E_INVALID, ": a member pitch shorter than one member's rows (q0_pitch: 0 or >= n; lat_pitch, out_pitch >= T * n)");
+    const bool out_short = K.gauges ? c.members > 1 && c.out_pitch < T * c.n_gauges : c.out_pitch < T * n;
+    if (K.batch && ((c.q0_pitch != 0 && c.q0_pitch < n) || (c.lateral && c.lat_pitch < T * n) || ((c.discharge || c.grad_out) && out_short)))
+        return no(RR_E_INVALID, K.gauges ? ": a member pitch shorter than one member's rows (q0_pitch: 0 or >= n; lat_pitch >= T * n; gauge_pitch >= T * n_gauges)"
+                                         : ": a member pitch shorter than one member's rows (q0_pitch: 0 or >= n; lat_pitch, out_pitch >= T * n)");
     if (int rc = own(AdjOwn::Pitch)) return rc;
-    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K, c.members);
+    const AdjointLayout L = adjoint_layout(n, H.depth, T, nsub, K, c.members, c.n_gauges, c.grad_rows);
     const int64_t need = L.total * (int64_t)sizeof(double);
     if (!c.work || c.work_bytes < need)
         return fail(RR_E_INVALID, std::string(who) + ": work memory smaller than " + K.sizer + " (" + std::to_string(need) + " bytes)");
@@ -171,11 +188,12 @@ int adjoint_check(const char *who, const AdjointKind &K, AdjointCall &c, int64_t
     return RR_OK;
 }
 
-int adjoint_work_bytes(const AdjointKind &K, rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes, int64_t members = 1)
+int adjoint_work_bytes(const AdjointKind &K, rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes, int64_t members = 1, int64_t n_gauges = 0,
+                       bool grad_rows = true)
 {
     if (!bytes) return fail(RR_E_INVALID, std::string(K.sizer) + ": null argument");
     AdjointCall c{};
-    c.P = P; c.T = T; c.nsub = nsub; c.members = members;
+    c.P = P; c.T = T; c.nsub = nsub; c.members = members; c.n_gauges = n_gauges; c.grad_rows = grad_rows;
     return adjoint_check(K.sizer, K, c, bytes, {});
 }
 
@@ -235,7 +253,9 @@ void adjoint_reduce_args(const AdjointCall &c, Args &r)
 
 // What a checked call enqueues.  ENS: a batched call (rr_rapid_adjoint_batch_dev) -- the member-batched kernels on grids with a member
 // dimension, so the two sweeps launch once per tick whatever the member count; otherwise the single-member kernels, launched as ever.
-template <bool ENS>
+// GAUGES: a gauge call (rr_rapid_adjoint_gauges_dev) -- the mask runs over the (T, n_gauges) blocks, no cotangent is permuted and the
+// reverse tick is its gauge form; the replay, the reduction, the merge and the row pass are the dense call's.
+template <bool ENS, bool GAUGES = false>
 void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double *grad_qfinal, double *grad_lateral, double *grad_q0,
                            double *grad_coef)
 {
@@ -247,7 +267,7 @@ void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double 
     const unsigned M = (unsigned)c.members;
     const int64_t lat_pitch = ENS ? c.lat_pitch : 0, out_pitch = ENS ? c.out_pitch : 0;
     // dL/d(discharge): clamp mask and mean in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
+    if (grad_out && !GAUGES) {
         const int64_t count = T * n;
         const dim3 g((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192), M);
         if constexpr (ENS)
@@ -269,12 +289,26 @@ void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double 
         const auto tick = lateral ? (c.one ? k_tick<true, true, ENS> : k_tick<true, false, ENS>) : (c.one ? k_tick<false, true, ENS> : k_tick<false, false, ENS>);
         adjoint_replay(c, a, [&](dim3 g) { g.y = M; hipLaunchKernelGGL(tick, g, dim3(kBlock), 0, st, a); });
     }
-    AdjTickArgsOf<ENS> ra{};
+    // a gauge call's dL/d(discharge): clamp mask and mean over the (T, n_gauges) blocks, and the slot map.  The blocks lie in the
+    // permutation's rows and the map in scratch rows: what used them, the lateral rows' permutation and the replay, is enqueued already
+    if (GAUGES && grad_out) {
+        const int64_t count = T * c.n_gauges;
+        const dim3 g((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192), M);
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_mask_batch, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, count, 1.0 / (double)nsub, count, out_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_mask, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, count, 1.0 / (double)nsub);
+        hipLaunchKernelGGL(k_adj_gauge_fill, grid1(n), dim3(kBlock), 0, st, c.pslot(), n);
+        hipLaunchKernelGGL(k_adj_gauge_scatter, grid1(c.n_gauges), dim3(kBlock), 0, st, c.pslot(), c.gauges, c.n_gauges);
+        hipLaunchKernelGGL(k_adj_gauge_slots, grid1(n), dim3(kBlock), 0, st, c.slot(), (const int32_t *)c.pslot(), (const int32_t *)P->d_perm, n);
+    }
+    AdjTickArgsOf<ENS, GAUGES> ra{};
     ra.gf = grad_qfinal; ra.perm = P->d_perm;
-    if constexpr (ENS) { ra.tape_pitch = L.mtape_pitch; ra.g_pitch = L.row_pitch; ra.gf_pitch = n; }
+    if constexpr (ENS) { ra.tape_pitch = L.mtape_pitch; ra.g_pitch = GAUGES ? T * c.n_gauges : L.row_pitch; ra.gf_pitch = n; }
+    if constexpr (GAUGES) { ra.slot = c.slot(); ra.n_gauges = c.n_gauges; }
     adjoint_reverse(c, ra, [&](dim3 g) {
         g.y = M;
-        hipLaunchKernelGGL((c.one ? k_adj_tick<true, ENS> : k_adj_tick<false, ENS>), g, dim3(kBlock), 0, st, ra);
+        hipLaunchKernelGGL((c.one ? k_adj_tick<true, ENS, GAUGES> : k_adj_tick<false, ENS, GAUGES>), g, dim3(kBlock), 0, st, ra);
     });
     if (grad_coef) {
         AdjReduceArgsOf<ENS> r{};
@@ -314,9 +348,14 @@ int rapid_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const d
         {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_q0 && !grad_coef)), kAdjNothing, ""},
         {AdjOwn::Wanted, grad_coef && !q0, RR_E_INVALID, ": the coefficient gradients need q0"},
         {AdjOwn::Lateral, P && lateral && !P->has_c4, RR_E_STATE, ": lateral rows but no c4_dt (rr_plan_set_coeffs got NULL)"},
+        {AdjOwn::Wanted, K.gauges && !c.gauges, RR_E_INVALID, ": null gauges"},
+        {AdjOwn::GradOut, K.gauges && c.discharge && !c.grad_out, RR_E_INVALID, ": discharge_g and grad_out_g come together or not at all"},
         {AdjOwn::GradOut, grad_lateral && !lateral, RR_E_INVALID, ": grad_lateral of a channel-only call (lateral is NULL)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-    if (K.batch) rapid_adjoint_enqueue<true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    if (K.gauges) {      // one member: the single-member kernels, so the single call's bits
+        if (c.members > 1) rapid_adjoint_enqueue<true, true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+        else rapid_adjoint_enqueue<false, true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    } else if (K.batch) rapid_adjoint_enqueue<true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
     else rapid_adjoint_enqueue<false>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
     HIPCHK(hipGetLastError());
     return RR_OK;

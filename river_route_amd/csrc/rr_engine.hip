@@ -1144,6 +1144,21 @@ int rr_rapid_adjoint_batch_dev(rr_plan *P, int64_t members, const double *q0, in
     return rapid_adjoint("rr_rapid_adjoint_batch_dev", kRapidAdjointBatch, c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
 }
 
+int rr_rapid_adjoint_gauges_work_bytes(rr_plan *P, int64_t members, int64_t n_gauges, int64_t T, int64_t nsub, int with_grad_lateral, int64_t *bytes)
+{
+    return adjoint_work_bytes(kRapidAdjointGauges, P, T, nsub, bytes, members, n_gauges, with_grad_lateral != 0);
+}
+
+int rr_rapid_adjoint_gauges_dev(rr_plan *P, int64_t members, int64_t n_gauges, const int32_t *gauges, const double *q0, int64_t q0_pitch,
+                                const double *lateral, int64_t lat_rows, int64_t lat_pitch, const double *discharge_g, const double *grad_out_g,
+                                int64_t gauge_pitch, const double *grad_qfinal, double *grad_lateral, double *grad_q0, double *grad_coef, void *work,
+                                int64_t work_bytes, int64_t T, int64_t nsub, void *stream)
+{
+    AdjointCall c{P, lateral, lat_rows, discharge_g, grad_out_g, work, work_bytes, T, nsub, (hipStream_t)stream, members, q0_pitch, lat_pitch,
+                  gauge_pitch, 0, n_gauges, gauges, grad_lateral != nullptr};
+    return rapid_adjoint("rr_rapid_adjoint_gauges_dev", kRapidAdjointGauges, c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+}
+
 int rr_unit_adjoint_work_bytes(rr_plan *P, int64_t T, int64_t nsub, int64_t *bytes) { return adjoint_work_bytes(kUnitAdjoint, P, T, nsub, bytes); }
 
 int rr_unit_adjoint_dev(rr_plan *P, const double *q_ch0, const double *q_full0, const double *lateral, int64_t lat_rows,

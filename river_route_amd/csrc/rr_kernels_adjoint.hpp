@@ -17,6 +17,11 @@
 // struct with the pitches appended, and form every index as (ENS ? index + offset : index), so their single-member instantiations
 // are the code they were (rr_kernels_tick.hpp: TickEnsArgs); the member is blockIdx.y, in the reduction, whose y is the sub-step
 // range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling that runs the same body on the member's pointers.
+//
+// Gauge form (rr_rapid_adjoint_gauges_dev): dL/d(discharge) is given at G gauged reaches only.  The reverse
+// tick takes a trailing GAUGES flag and an args struct with the slot map appended: a position reads slot[p] and, where that is >= 0,
+// the masked (T, G) block; every other position starts from 0.0, which is what the dense form reads there.  k_adj_gauge_fill,
+// k_adj_gauge_scatter and k_adj_gauge_slots build the map; the mask over the block is k_adj_mask itself on T * G elements.
 #pragma once
 
 namespace {
@@ -44,7 +49,18 @@ struct AdjTickArgs {
 struct AdjTickEnsArgs : AdjTickArgs {
     int64_t tape_pitch, g_pitch, gf_pitch;
 };
-template <bool ENS> using AdjTickArgsOf = typename std::conditional<ENS, AdjTickEnsArgs, AdjTickArgs>::type;
+// The gauge form of either: g is the masked (T, n_gauges) block (member blockIdx.y's at g_pitch), read where slot[p] >= 0.
+struct AdjTickGaugeArgs : AdjTickArgs {
+    const int32_t *slot;       // [n] engine order: the gauge column of position p, -1 where the reach has no gauge
+    int64_t n_gauges;
+};
+struct AdjTickGaugeEnsArgs : AdjTickEnsArgs {
+    const int32_t *slot;
+    int64_t n_gauges;
+};
+template <bool ENS, bool GAUGES = false> using AdjTickArgsOf =
+    typename std::conditional<GAUGES, typename std::conditional<ENS, AdjTickGaugeEnsArgs, AdjTickGaugeArgs>::type,
+                              typename std::conditional<ENS, AdjTickEnsArgs, AdjTickArgs>::type>::type;
 __device__ __forceinline__ int64_t member_tape0(const AdjTickArgs &) { return 0; }
 __device__ __forceinline__ int64_t member_tape0(const AdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
 __device__ __forceinline__ int64_t member_g0(const AdjTickArgs &) { return 0; }
@@ -54,9 +70,10 @@ __device__ __forceinline__ int64_t member_gf0(const AdjTickEnsArgs &e) { return 
 
 // One reverse tick: mu of every active position.  One reach per lane over lag-ordered positions, like k_tick; the downstream
 // reads hit a handful of cache lines per wave (the downstream reaches of consecutive positions are consecutive positions).
-// ENS: the member-batched form; the fma sequence of a member is the single call's.
-template <bool SINGLE_SUBSTEP, bool ENS = false>
-__global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgsOf<ENS> a)
+// ENS: the member-batched form; the fma sequence of a member is the single call's.  GAUGES: dL/d(discharge) comes from the gauge
+// block through the slot map (one dependent load per position); the fma sequence is the dense form's on the same values.
+template <bool SINGLE_SUBSTEP, bool ENS = false, bool GAUGES = false>
+__global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgsOf<ENS, GAUGES> a)
 {
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (p >= a.p_hi) return;
@@ -69,7 +86,15 @@ __global__ __launch_bounds__(kBlock) void k_adj_tick(const AdjTickArgsOf<ENS> a)
     else { uint32_t rem; t = a.nsub.div(ts, rem); }
 
     const int64_t mt = member_tape0(a), mg = member_g0(a), mf = member_gf0(a);
-    double m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
+    double m;
+    if constexpr (GAUGES) {
+        m = 0.0;
+        if (a.g) {
+            const int32_t j = a.slot[p];
+            if (j >= 0) m = a.g[ENS ? (int64_t)t * a.n_gauges + j + mg : (int64_t)t * a.n_gauges + j];
+        }
+    } else
+        m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
     if (r == 0 && a.gf) m += a.gf[ENS ? a.perm[p] + mf : a.perm[p]];
     if (r > 0) m = __builtin_fma(a.c3[p], a.ma[ENS ? p + mt : p], m);
     const int32_t d = a.down[p];
@@ -118,6 +143,24 @@ __global__ __launch_bounds__(kBlock) void k_adj_mask_batch(double *dst, const do
 {
     const int64_t m = blockIdx.y;
     adj_mask(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, count, inv_nsub);
+}
+
+// The slot map of a gauge call, three launches in stream order: pslot[n] (params order) filled with -1, pslot[gauges[j]] = j, then
+// slot[p] = pslot[perm[p]] in engine order.  gauges[] is not range-checked here: the caller vouches for distinct indices in [0, n).
+__global__ __launch_bounds__(kBlock) void k_adj_gauge_fill(int32_t *pslot, int64_t n)
+{
+    const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (i < n) pslot[i] = -1;
+}
+__global__ __launch_bounds__(kBlock) void k_adj_gauge_scatter(int32_t *pslot, const int32_t *gauges, int64_t n_gauges)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j < n_gauges) pslot[gauges[j]] = (int32_t)j;
+}
+__global__ __launch_bounds__(kBlock) void k_adj_gauge_slots(int32_t *slot, const int32_t *pslot, const int32_t *perm, int64_t n)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p < n) slot[p] = pslot[perm[p]];
 }
 
 struct AdjReduceArgs {

@@ -266,6 +266,25 @@ class Plan:
                                                     ptr(grad_q0), ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps),
                                                     stream))
 
+    def rapid_adjoint_gauges_work_bytes(self, members: int, n_gauges: int, T: int, num_substeps: int = 1, with_grad_lateral: bool = False) -> int:
+        """rr_rapid_adjoint_gauges_work_bytes: bytes of work memory rapid_adjoint_gauges_dev needs for `members` series of T rows x
+        num_substeps sub-steps with dL/d(discharge) at n_gauges reaches; with_grad_lateral: the call will be given a grad_lateral
+        (readies the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_rapid_adjoint_gauges_work_bytes(self._h, int(members), int(n_gauges), int(T), int(num_substeps),
+                                                            int(bool(with_grad_lateral)), C.byref(out)))
+        return int(out.value)
+
+    def rapid_adjoint_gauges_dev(self, members, n_gauges, gauges, q0, q0_pitch, lateral, lat_rows, lat_pitch, discharge_g, grad_out_g,
+                                 gauge_pitch, grad_qfinal, grad_lateral, grad_q0, grad_coef, work, work_bytes, T, num_substeps,
+                                 stream=None) -> None:
+        """rr_rapid_adjoint_gauges_dev (enqueue only): rapid_adjoint_batch_dev with the discharge and its gradient given as
+        [members, T, n_gauges] at the reaches gauges[n_gauges] (device int32, params order, distinct; not range-checked)."""
+        check(_lib.lib().rr_rapid_adjoint_gauges_dev(self._h, int(members), int(n_gauges), ptr(gauges), ptr(q0), int(q0_pitch), ptr(lateral),
+                                                     int(lat_rows), int(lat_pitch), ptr(discharge_g), ptr(grad_out_g), int(gauge_pitch),
+                                                     ptr(grad_qfinal), ptr(grad_lateral), ptr(grad_q0), ptr(grad_coef), ptr(work),
+                                                     int(work_bytes), int(T), int(num_substeps), stream))
+
     # -- adjoint of unit_route_dev (rr.grad) --
     def unit_adjoint_work_bytes(self, T: int, num_substeps: int = 1) -> int:
         """rr_unit_adjoint_work_bytes: bytes of work memory unit_adjoint_dev needs for T rows x num_substeps sub-steps (readies

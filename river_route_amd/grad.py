@@ -29,6 +29,13 @@ by member: the convolution's adjoint is a few launches per member, not one per t
 
     Q, q_ch, q_full, uh_state = rr.grad.unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state0, k, x, 900.0, 3600.0)
 
+A calibration reads the discharge at a few thousand gauged reaches of a large network.  rapid_route and rapid_route_batch take those
+reaches as gauges=: they then return and keep the (T, G) gauge columns only, and the backward pass is
+rr_rapid_adjoint_gauges_dev, which takes the (T, G) cotangent as it is -- no (T, n) cotangent is allocated, zero-filled or permuted:
+
+    Qg, q_final = rr.grad.rapid_route(plan, q0, qlateral, k, x, 900.0, 3600.0, gauges=gauges)      # Qg[T, G], column j is reach gauges[j]
+    (1 - rr.grad.scores(observed, Qg)['kge2012']).mean().backward()
+
 Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, partitioned plans and plans with
 set_unit_weights edge data are refused, and so are 3-D rows everywhere but in the *_batch functions.
 
@@ -46,7 +53,7 @@ import torch
 from . import engine, metrics
 from .engine import Plan
 
-__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
+__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'RapidRouteGauges', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
            'unit_muskingum', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores']
 
 
@@ -201,16 +208,128 @@ def _in_windows(T, rows_per_window, state, route, axis=0):
     return (parts[0] if len(parts) == 1 else torch.cat(parts, axis)), *state
 
 
-def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None):
+def _check_gauges(gauges, n):
+    """gauges= of rapid_route and rapid_route_batch: a 1-D integer array or tensor of distinct params-order reach indices in [0, n).
+    Returns them as an int64 host array; for a tensor on a GPU only its shape and type are checked, and None is returned: its values
+    are read (by _gauge_values) after the device checks."""
+    if isinstance(gauges, torch.Tensor):
+        if gauges.dim() != 1 or gauges.is_floating_point() or gauges.is_complex() or gauges.dtype == torch.bool:
+            raise ValueError('gauges must be a 1-D integer array or tensor of reach indices')
+        if int(gauges.shape[0]) < 1:
+            raise ValueError('gauges is empty')
+        if gauges.device.type != 'cpu':
+            return None
+        gauges = gauges.detach().numpy()
+    return _gauge_values(gauges, n)
+
+
+def _gauge_values(gauges, n):
+    g = np.asarray(gauges)
+    if g.ndim != 1 or not np.issubdtype(g.dtype, np.integer):
+        raise ValueError('gauges must be a 1-D integer array or tensor of reach indices')
+    if g.size < 1:
+        raise ValueError('gauges is empty')
+    g = g.astype(np.int64)
+    if g.min() < 0 or g.max() >= n:
+        raise ValueError(f'gauges refers to reach {int(g.min() if g.min() < 0 else g.max())}: the plan has reaches 0 .. {n - 1}')
+    if np.unique(g).size != g.size:
+        raise ValueError('gauges holds a reach more than once (the indices must be distinct)')
+    return g
+
+
+def _upload_gauges(plan, gauges, host):
+    """The gauge indices on the plan's device, once per call: (int32 for the adjoint, int64 for the forward's gather)."""
+    if host is None:
+        host = _gauge_values(gauges.detach().cpu().numpy(), plan.n)
+    g32 = torch.from_numpy(host.astype(np.int32)).to(torch.device('cuda', plan.device))
+    return g32, g32.long()
+
+
+class RapidRouteGauges(torch.autograd.Function):
+    """(discharge[B, T, G], q_final[B, n]) = RapidRouteBatch with the discharge at the reaches `gauges` only (a pair of device tensors,
+    int32 and int64, of G distinct params-order indices).  Forward: RapidRoute's call, member by member, into one (T, n) scratch tensor
+    that is not kept, the gauge columns gathered out of it; every value is RapidRoute's.  Only q0, qlateral and the (B, T, G) gauge
+    discharge are kept.  Backward: rr_rapid_adjoint_gauges_dev on groups of `per_sweep` members (None: all) in ascending order, the
+    groups' coefficient gradients added in that order; its work memory has gradient rows only when qlateral requires grad."""
+
+    @staticmethod
+    def forward(ctx, plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt):
+        dev = plan.device
+        g32, g64 = gauges
+        B, T, G = int(q0.shape[0]), int(rows), int(g32.shape[0])
+        _set_coeffs(plan, c1, c2, c3, c4dt if qlateral is not None else None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        q = q0.detach().clone(memory_format=torch.contiguous_format)
+        scratch = torch.empty((T, plan.n), dtype=torch.float64, device=q0.device)
+        discharge = torch.empty((B, T, G), dtype=torch.float64, device=q0.device)
+        ql = None if qlateral is None else qlateral.detach()
+        for m in range(B):
+            if ql is not None:
+                plan.rapid_route_dev(q[m], ql[m], T, scratch, T, T, nsub, stream)
+            else:
+                plan.muskingum_route_dev(q[m], scratch, T, T, nsub, stream)
+            torch.index_select(scratch, 1, g64, out=discharge[m])
+        ctx.plan, ctx.nsub, ctx.rows, ctx.per_sweep, ctx.g32 = plan, int(nsub), T, per_sweep, g32
+        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach(), None if c4dt is None else c4dt.detach())
+        ctx.save_for_backward(q0, qlateral, discharge)
+        ctx.set_materialize_grads(False)
+        return discharge, q
+
+    @staticmethod
+    def backward(ctx, grad_discharge, grad_qfinal):
+        plan, nsub, T, g32 = ctx.plan, ctx.nsub, ctx.rows, ctx.g32
+        q0, qlateral, discharge = ctx.saved_tensors
+        need = ctx.needs_input_grad      # plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt
+        want_q0, want_ql = need[5], need[6] and qlateral is not None
+        want_coef = any(need[7:10]) or (need[10] and qlateral is not None)
+        if (grad_discharge is None and grad_qfinal is None) or not (want_q0 or want_ql or want_coef):
+            return (None,) * 11
+        B, n, G = int(q0.shape[0]), plan.n, int(g32.shape[0])
+        _set_coeffs(plan, *ctx.coeffs[:3], ctx.coeffs[3] if qlateral is not None else None, plan.device)
+        stream = torch.cuda.current_stream(plan.device).cuda_stream
+        f64 = dict(dtype=torch.float64, device=discharge.device)
+        g_out = None if grad_discharge is None else grad_discharge.to(**f64).contiguous()
+        g_fin = None if grad_qfinal is None else grad_qfinal.to(**f64).contiguous()
+        g_q0 = torch.empty((B, n), **f64) if want_q0 else None
+        g_ql = torch.empty((B, T, n), **f64) if want_ql else None
+        ql = None if qlateral is None else qlateral.detach()
+        q0_pitch = int(q0.stride(0)) if B > 1 else n
+        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
+        nbytes = max(plan.rapid_adjoint_gauges_work_bytes(g, G, T, nsub, want_ql) for g in {group, B % group or group})
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
+        g_coef = None
+
+        def members(t, m0, m1):
+            return None if t is None else t[m0:m1]
+
+        for m0 in range(0, B, group):
+            m1 = min(B, m0 + group)
+            part = torch.empty((4, n), **f64) if want_coef else None
+            plan.rapid_adjoint_gauges_dev(m1 - m0, G, g32, q0.data_ptr() + 8 * m0 * q0_pitch, q0_pitch, members(ql, m0, m1), T, T * n,
+                                          None if g_out is None else discharge[m0:m1], members(g_out, m0, m1), T * G, members(g_fin, m0, m1),
+                                          members(g_ql, m0, m1), members(g_q0, m0, m1), part, work, nbytes, T, nsub, stream)
+            if want_coef:
+                g_coef = part if g_coef is None else g_coef + part
+        coef = [g_coef[j].to(c.device) if want_coef and need[7 + j] and c is not None else None for j, c in enumerate(ctx.coeffs)]
+        return (None, None, None, None, None, g_q0, g_ql, *coef)
+
+
+def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, gauges=None):
     """Differentiable RapidMuskingum routing: (discharge[T, n], q_final[n]) as torch tensors on the plan's device.
 
     q0[n] and qlateral[T, n] are float64 tensors on the plan's GPU (qlateral in the reference's volume units per runoff step;
     None routes channel-only, and then `rows` gives T); k and x are float64 tensors of n values on any device.  c1, c2, c3 come
     from muskingum_coefficients(k, x, dt_routing) and c4dt = (c1 + c2) / dt_runoff; dt_runoff must be a whole number of routing
     steps.  Gradients reach q0, qlateral, k and x (whichever require grad).  rows_per_window routes the series in windows chained
-    through q_final -> q0, so the tape memory of the backward pass is one window's.  Every argument is checked before the GPU is
-    touched."""
+    through q_final -> q0, so the tape memory of the backward pass is one window's.
+
+    gauges (a 1-D integer array or tensor of G distinct params-order reach indices) makes the first result discharge[T, G], column
+    j being reach gauges[j], for a loss that reads gauged reaches only: the values and every gradient are those of the call without
+    it and discharge[:, gauges], bit for bit, but only the gauge columns are kept for the backward pass, which takes the (T, G)
+    cotangent as it is (rr_rapid_adjoint_gauges_dev), so nothing (T, n) is allocated for it unless qlateral requires grad.  Every
+    argument is checked before the GPU is touched."""
     nsub = _check_call(plan, 'n', ((q0, 'q0'),), k, x, dt_routing, dt_runoff, rows_per_window)
+    host_gauges = None if gauges is None else _check_gauges(gauges, plan.n)
     if qlateral is None:
         if rows is None or int(rows) < 1:
             raise ValueError('channel-only routing (qlateral=None) needs rows >= 1')
@@ -220,6 +339,11 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
     _check_device(plan, ((q0, 'q0'), (qlateral, 'qlateral')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
     c4dt = (c1 + c2) / float(dt_runoff)
+    if gauges is not None:      # the one-member case of the batched gauge call
+        on_device = _upload_gauges(plan, gauges, host_gauges)
+        d, q = _in_windows(T, rows_per_window, (q0.unsqueeze(0),), lambda t0, t1, q: RapidRouteGauges.apply(
+            plan, nsub, t1 - t0, None, on_device, q, None if qlateral is None else qlateral[t0:t1].unsqueeze(0), c1, c2, c3, c4dt), axis=1)
+        return d[0], q[0]
     return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRoute.apply(
         plan, nsub, t1 - t0, q, None if qlateral is None else qlateral[t0:t1], c1, c2, c3, c4dt))
 
@@ -325,7 +449,7 @@ class RapidRouteBatch(torch.autograd.Function):
         return (None, None, None, None, g_q0, g_ql, *coef)
 
 
-def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, members_per_sweep=None):
+def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, members_per_sweep=None, gauges=None):
     """rapid_route for B forcing series on one network and one set of coefficients: (discharge[B, T, n], q_final[B, n]).
 
     qlateral[B, T, n] is a contiguous float64 tensor on the plan's GPU (None routes channel-only: then `rows` gives T and q0 gives B);
@@ -335,9 +459,11 @@ def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_
     members.  The backward pass is one rr_rapid_adjoint_batch_dev call: its tick launches do not grow with B.  members_per_sweep (None:
     all members in one sweep) bounds the tape memory: the backward then runs groups of that many members in ascending order and adds
     the groups' coefficient gradients in that order.  rows_per_window chains windows through q_final -> q0 as rapid_route does.
-    Every argument is checked before the GPU is touched."""
+    gauges makes the first result discharge[B, T, G] at the reaches gauges[j], as in rapid_route: each member's values and gradients
+    are those of rapid_route(..., gauges=gauges) for that member alone.  Every argument is checked before the GPU is touched."""
     nsub = _check_call(plan, 'n', (), k, x, dt_routing, dt_runoff, rows_per_window)
     n = plan.n
+    host_gauges = None if gauges is None else _check_gauges(gauges, n)
     _check_members_per_sweep(members_per_sweep)
     if not isinstance(q0, torch.Tensor) or q0.ndim not in (1, 2):
         raise ValueError('q0 must be a (B, n) tensor, or (n,) for one state shared by every member')
@@ -358,6 +484,11 @@ def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_
     if q0.ndim == 1:
         q0 = q0.unsqueeze(0).expand(B, n)      # autograd sums the members' rows into the one q0
     whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
+    if gauges is not None:
+        on_device = _upload_gauges(plan, gauges, host_gauges)
+        return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRouteGauges.apply(
+            plan, nsub, t1 - t0, members_per_sweep, on_device, q,
+            None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(), c1, c2, c3, c4dt), axis=1)
     return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRouteBatch.apply(
         plan, nsub, t1 - t0, members_per_sweep, q, None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(),
         c1, c2, c3, c4dt), axis=1)
