@@ -16,7 +16,8 @@
  *   rr_unit_adjoint_dev <- the gradient of a loss through unit_route (same lines), rr_uh_adjoint_dev <- through
  *                          UnitHydrograph.convolve (same lines); rr_rapid_adjoint_dev <- through rapid_route;
  *                          rr_rapid_adjoint_batch_dev, rr_unit_adjoint_batch_dev <- through several such calls at once;
- *                          rr_rapid_adjoint_gauges_dev <- through rapid_route with a loss at gauged reaches only
+ *                          rr_rapid_adjoint_gauges_dev, rr_unit_adjoint_gauges_dev <- through rapid_route / unit_route with a loss
+ *                          at gauged reaches only
  *   rr_plan_create      <- the CSC structure the routers take from tools.adjacency_matrix
  *                          (river_route/tools.py:75-109; river_route/routers/Muskingum.py:189-192)
  *   rr_plan_set_coeffs  <- the coefficient vectors of Muskingum._set_muskingum_coefficients
@@ -541,6 +542,38 @@ int rr_unit_adjoint_batch_dev(rr_plan *plan, int64_t members, const double *q_ch
                               int64_t out_pitch, const double *grad_qch_final, const double *grad_qfull_final, double *grad_lateral,
                               double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes, int64_t T,
                               int64_t nsub, void *stream);
+
+/* ---- the same with dL/d(discharge) at gauged reaches only ----
+ * rr_unit_adjoint_batch_dev (unit_route, river_route/routers/_numba_kernels.py:88-171, call site
+ * river_route/routers/UnitMuskingum.py:82-92) for a loss that reads the discharge at n_gauges reaches: no (T, n) cotangent is read,
+ * written or permuted.
+ *   gauges[n_gauges]          device int32 reach indices in params order, distinct, in any order, headwaters and inner reaches alike;
+ *   discharge_g[T*n_gauges]   the forward call's discharge at those reaches, column j being reach gauges[j] (the clamp mask of an inner
+ *                             reach: a value <= 0 passes no gradient, as in the dense call; a headwater's column is not read);
+ *   grad_out_g[T*n_gauges]    dL/d(that discharge); both or neither (NULL: the loss reads the final states only);
+ * member m's discharge_g and grad_out_g lie m * gauge_pitch doubles further on (gauge_pitch >= T*n_gauges; anything when members == 1).
+ * Every other argument means what it means in rr_unit_adjoint_batch_dev, NULLs included.  One call form: with members == 1 the
+ * single-member kernels run and every output has the bits rr_unit_adjoint_dev gives for the cotangent scattered to full width.
+ * On the device a slot map (engine order, -1 or the gauge column) is built from gauges[] per call and the forward's output rule is
+ * applied over the (T, n_gauges) blocks: an inner reach's column takes the clamp mask and the 1 / nsub mean, a headwater's passes as it
+ * is.  A reverse tick reads, per position, its slot and, at a gauge, one value of the block; so does the row pass that writes
+ * grad_lateral, where a headwater's cotangent arrives undivided.  gauges[] is not range-checked on the device: the caller vouches for
+ * distinct indices in [0, n).
+ * Work memory (rr_unit_adjoint_gauges_work_bytes; caller-provided, the call allocates nothing and only enqueues on `stream`):
+ *   8 (n members (2 S + (with_grad_lateral ? 2 : 1) T + 2 depth + 3 splits + 6) + max(n min(T, 16), members T n_gauges)) bytes,
+ *   splits as in rr_unit_adjoint_batch_work_bytes: the batch call's memory without the engine-order gradient rows unless
+ *   grad_lateral is asked for; the masked blocks share the permutation's rows, the slot map the replay's first scratch row.
+ * with_grad_lateral says which layout is meant: a non-NULL grad_lateral on work memory sized without it is refused (RR_E_INVALID, too
+ * little work memory).  rr_unit_adjoint_gauges_work_bytes readies the plan as rr_unit_adjoint_work_bytes does.  No atomics.
+ * Refused: what rr_unit_adjoint_batch_dev refuses (general edge data: RR_E_UNSUPPORTED), then RR_E_INVALID for n_gauges < 1 or > n, a
+ * NULL gauges, discharge_g without grad_out_g or the reverse, and a gauge_pitch shorter than T*n_gauges when members > 1. */
+int rr_unit_adjoint_gauges_work_bytes(rr_plan *plan, int64_t members, int64_t n_gauges, int64_t T, int64_t nsub, int with_grad_lateral,
+                                      int64_t *bytes);
+int rr_unit_adjoint_gauges_dev(rr_plan *plan, int64_t members, int64_t n_gauges, const int32_t *gauges, const double *q_ch0,
+                               const double *q_full0, int64_t state_pitch, const double *lateral, int64_t lat_rows, int64_t lat_pitch,
+                               const double *discharge_g, const double *grad_out_g, int64_t gauge_pitch, const double *grad_qch_final,
+                               const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0,
+                               double *grad_coef, void *work, int64_t work_bytes, int64_t T, int64_t nsub, void *stream);
 
 /* ---- adjoint of the unit-hydrograph convolution ----
  * The gradient through one rr_uh_convolve_dev call (UnitHydrograph.convolve, river_route/uhkernels/UnitHydrograph.py:93-107):

@@ -150,6 +150,9 @@ _SIGNATURES = {
     'rr_unit_adjoint_batch_work_bytes': (C.c_int, [_vp, _i64, _i64, _i64, C.POINTER(_i64)]),
     'rr_unit_adjoint_batch_dev': (C.c_int, [_vp, _i64, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64,
                                             _i64, _i64, _vp]),
+    'rr_unit_adjoint_gauges_work_bytes': (C.c_int, [_vp, _i64, _i64, _i64, _i64, C.c_int, C.POINTER(_i64)]),
+    'rr_unit_adjoint_gauges_dev': (C.c_int, [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                             _i64, _i64, _i64, _vp]),
     'rr_uh_adjoint_work_bytes': (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64)]),
     'rr_uh_adjoint_dev': (C.c_int, [C.c_int, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp]),
     'rr_metrics_adjoint_work_bytes': (C.c_int, [_i64, C.POINTER(_i64)]),

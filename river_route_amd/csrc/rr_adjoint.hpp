@@ -12,13 +12,15 @@ constexpr int64_t kAdjMaxMembers = 65535;     // members of a batched call: a gr
 // What differs between the two routers outside the kernels: the name of the sizing entry point (the errors name it) and two row counts
 // of the work memory: sums per reach in the reduction (c1..c4 / c1..c3) and scratch rows (the tick's running sum and its discarded
 // discharge row; Unit adds q_ch, updated in place, q_ch0, dL/d(q_ch final) and dL/d(q_full final) in engine order).
-// batch: the member-batched entry points; gauges: rr_rapid_adjoint_gauges_*, dL/d(discharge) at gauged reaches only
+// batch: the member-batched entry points; gauges: rr_rapid_adjoint_gauges_* and rr_unit_adjoint_gauges_*, dL/d(discharge) at gauged
+// reaches only
 struct AdjointKind { const char *sizer; int64_t slab_rows, scratch_rows; bool batch = false, gauges = false; };
 constexpr AdjointKind kRapidAdjoint{"rr_rapid_adjoint_work_bytes", 4, 2};
 constexpr AdjointKind kRapidAdjointBatch{"rr_rapid_adjoint_batch_work_bytes", 4, 2, true};
 constexpr AdjointKind kRapidAdjointGauges{"rr_rapid_adjoint_gauges_work_bytes", 4, 2, true, true};
 constexpr AdjointKind kUnitAdjoint{"rr_unit_adjoint_work_bytes", 3, 6};
 constexpr AdjointKind kUnitAdjointBatch{"rr_unit_adjoint_batch_work_bytes", 3, 6, true};
+constexpr AdjointKind kUnitAdjointGauges{"rr_unit_adjoint_gauges_work_bytes", 3, 6, true, true};
 
 // The work memory of one adjoint call, in doubles, front to back: q tape (S + depth + 1 rows: ticks -2 .. S + Dmax - 1), mu tape
 // (S + depth - 1 rows: reverse ticks 0 .. S + Dmax - 1; before the reverse ticks it holds the masked dL/d(discharge) in params
@@ -27,7 +29,8 @@ constexpr AdjointKind kUnitAdjointBatch{"rr_unit_adjoint_batch_work_bytes", 3, 6
 // once per member, member m's part m pitches into the section: with one member this is the single call's layout, byte for byte.
 // A gauge call (n_gauges > 0) keeps its masked (T, n_gauges) blocks, members adjacent, in the permutation's rows, which grow to hold
 // them: the rows are idle from the lateral rows' permutation to the gradient rows', and the reverse ticks, which read the blocks, lie
-// between.  Its slot map (2 n int32) lives in member 0's scratch rows, idle once the replay is done.  Without grad_rows (no
+// between (so does UnitMuskingum's row pass, which reads them too).  Its slot map (2 n int32) lives in member 0's first scratch row,
+// the replay's, idle once the replay is enqueued; the rows Unit adds are not idle and lie behind it.  Without grad_rows (no
 // grad_lateral) it has no gradient rows.
 struct AdjointLayout {
     int64_t qtape, mtape, lat, grad, mrows, slab, scratch, total;      // offsets and total in doubles
@@ -92,7 +95,7 @@ struct AdjointCall {
     // for all), lateral / grad_lateral rows and discharge / grad_out rows to the next's; for UnitMuskingum, whose states have n_inner
     // values, state_pitch instead of q0_pitch (0: one q_ch0 and one q_full0 for all).  The single-member entry points leave these as they are.
     int64_t members = 1, q0_pitch = 0, lat_pitch = 0, out_pitch = 0, state_pitch = 0;
-    // a gauge call (rr_rapid_adjoint_gauges_*): discharge and grad_out are (T, n_gauges) at reaches gauges[] (out_pitch: the gauge pitch);
+    // a gauge call (rr_rapid_adjoint_gauges_*, rr_unit_adjoint_gauges_*): discharge and grad_out are (T, n_gauges) at reaches gauges[] (out_pitch: the gauge pitch);
     // grad_rows: the work memory has gradient rows (the sizer's with_grad_lateral; in a *_dev call, grad_lateral is given)
     int64_t n_gauges = 0; const int32_t *gauges = nullptr; bool grad_rows = true;
     // set by adjoint_check
@@ -365,7 +368,9 @@ int rapid_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const d
 
 // What a checked call enqueues, as rapid_adjoint_enqueue: ENS is a batched call (rr_unit_adjoint_batch_dev) on grids with a member
 // dimension; otherwise the single-member kernels, launched as ever.  ni: the plan's inner reaches (0: no state and no tick).
-template <bool ENS>
+// GAUGES: a gauge call (rr_unit_adjoint_gauges_dev) -- the output rule is applied over the (T, n_gauges) blocks, no cotangent is staged
+// in the mu tape or permuted, and the reverse tick and the row pass are their gauge forms; the rest is the dense call's.
+template <bool ENS, bool GAUGES = false>
 void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
                           const double *grad_qfull_final, double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef)
 {
@@ -380,7 +385,7 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
     const bool tape = grad_coef && ni > 0;
     const unsigned col_blocks = (unsigned)((n + kBlock - 1) / kBlock), row_blocks = (unsigned)std::min<int64_t>(T, 65535);
     // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
-    if (grad_out) {
+    if (grad_out && !GAUGES) {
         if constexpr (ENS)
             hipLaunchKernelGGL(k_adj_mask_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
                                (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub, L.mtape_pitch, out_pitch);
@@ -410,13 +415,30 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
             hipLaunchKernelGGL((c.one ? k_tick_unit<true, ENS> : k_tick_unit<false, ENS>), g, dim3(kBlock), 0, st, ua);
         });
     }
+    // a gauge call's dL/d(discharge): the output rule over the (T, n_gauges) blocks, and the slot map.  The blocks lie in the
+    // permutation's rows and the map in the replay's first scratch row: what used them, the lateral rows' permutation and the replay, is
+    // enqueued already.  With no inner reach the row pass still reads both.
+    if (GAUGES && grad_out) {
+        const dim3 g((unsigned)((c.n_gauges + kBlock - 1) / kBlock), row_blocks, M);
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_mask_unit_gauges_batch, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, c.gauges,
+                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, c.n_gauges, T, 1.0 / (double)nsub, T * c.n_gauges,
+                               out_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_mask_unit_gauges, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, c.gauges,
+                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, c.n_gauges, T, 1.0 / (double)nsub);
+        hipLaunchKernelGGL(k_adj_gauge_fill, grid1(n), dim3(kBlock), 0, st, c.pslot(), n);
+        hipLaunchKernelGGL(k_adj_gauge_scatter, grid1(c.n_gauges), dim3(kBlock), 0, st, c.pslot(), c.gauges, c.n_gauges);
+        hipLaunchKernelGGL(k_adj_gauge_slots, grid1(n), dim3(kBlock), 0, st, c.slot(), (const int32_t *)c.pslot(), (const int32_t *)P->d_perm, n);
+    }
     if (ni > 0) {      // with no inner reach there is no state and no tick
-        UnitAdjTickArgsOf<ENS> a{};
+        UnitAdjTickArgsOf<ENS, GAUGES> a{};
         a.child_ptr = P->d_child_ptr; a.gcf = grad_qch_final ? gcf : nullptr; a.gff = grad_qfull_final ? gff : nullptr;
-        if constexpr (ENS) { a.tape_pitch = L.mtape_pitch; a.g_pitch = L.row_pitch; a.gf_pitch = L.scratch_pitch; }
+        if constexpr (ENS) { a.tape_pitch = L.mtape_pitch; a.g_pitch = GAUGES ? T * c.n_gauges : L.row_pitch; a.gf_pitch = L.scratch_pitch; }
+        if constexpr (GAUGES) { a.slot = c.slot(); a.n_gauges = c.n_gauges; }
         adjoint_reverse(c, a, [&](dim3 g) {
             g.y = M;
-            hipLaunchKernelGGL((c.one ? k_adj_tick_unit<true, ENS> : k_adj_tick_unit<false, ENS>), g, dim3(kBlock), 0, st, a);
+            hipLaunchKernelGGL((c.one ? k_adj_tick_unit<true, ENS, GAUGES> : k_adj_tick_unit<false, ENS, GAUGES>), g, dim3(kBlock), 0, st, a);
         });
     }
     if (tape) {
@@ -449,7 +471,19 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
                                (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
                                (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax);
     }
-    if (grad_lateral) {
+    if (grad_lateral && GAUGES) {      // the blocks are read here for the last time: the permutation after it takes their rows back
+        const double *const gff_rows = grad_qfull_final ? (const double *)gff : nullptr;
+        if constexpr (ENS)
+            hipLaunchKernelGGL(k_adj_rows_unit_gauges_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
+                               (const int32_t *)c.slot(), c.n_gauges, gff_rows, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
+                               nsub, S, (int32_t)c.dmax, L.row_pitch, L.scratch_pitch, L.mtape_pitch);
+        else
+            hipLaunchKernelGGL(k_adj_rows_unit_gauges, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
+                               (const int32_t *)c.slot(), c.n_gauges, gff_rows, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
+                               nsub, S, (int32_t)c.dmax);
+    } else if (grad_lateral) {
         if constexpr (ENS)
             hipLaunchKernelGGL(k_adj_rows_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
                                grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
@@ -460,8 +494,8 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
                                grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
                                (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
                                nsub, S, (int32_t)c.dmax);
-        c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
     }
+    if (grad_lateral) c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
 }
 
 int unit_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
@@ -479,11 +513,19 @@ int unit_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const do
         {AdjOwn::Wanted, P && (P->h.n == 0 || (!grad_lateral && !grad_qch0 && !grad_qfull0 && !grad_coef)), kAdjNothing, ""},
         {AdjOwn::Wanted, grad_coef && ni > 0 && (!q_ch0 || !q_full0 || !lateral), RR_E_INVALID,
          ": the coefficient gradients need q_ch0, q_full0 and the lateral rows"},
+        {AdjOwn::Wanted, K.gauges && !c.gauges, RR_E_INVALID, ": null gauges"},
+        {AdjOwn::GradOut, K.gauges && c.discharge && !c.grad_out, RR_E_INVALID, ": discharge_g and grad_out_g come together or not at all"},
         {AdjOwn::Pitch, K.batch && P && rows_ok && (c.state_pitch < 0 || (c.state_pitch != 0 && c.state_pitch < ni) ||
                                                     (grad_lateral && c.lat_pitch < c.T * P->h.n)), RR_E_INVALID,
-         ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch, out_pitch >= T * n)"}});
+         K.gauges ? ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch >= T * n)"
+                  : ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch, out_pitch >= T * n)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-    if (K.batch) unit_adjoint_enqueue<true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+    if (K.gauges) {      // one member: the single-member kernels, so the single call's bits
+        if (c.members > 1)
+            unit_adjoint_enqueue<true, true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+        else
+            unit_adjoint_enqueue<false, true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+    } else if (K.batch) unit_adjoint_enqueue<true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
     else unit_adjoint_enqueue<false>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
     HIPCHK(hipGetLastError());
     return RR_OK;

@@ -1186,6 +1186,23 @@ int rr_unit_adjoint_batch_dev(rr_plan *P, int64_t members, const double *q_ch0, 
                         grad_qfull0, grad_coef);
 }
 
+int rr_unit_adjoint_gauges_work_bytes(rr_plan *P, int64_t members, int64_t n_gauges, int64_t T, int64_t nsub, int with_grad_lateral, int64_t *bytes)
+{
+    return adjoint_work_bytes(kUnitAdjointGauges, P, T, nsub, bytes, members, n_gauges, with_grad_lateral != 0);
+}
+
+int rr_unit_adjoint_gauges_dev(rr_plan *P, int64_t members, int64_t n_gauges, const int32_t *gauges, const double *q_ch0, const double *q_full0,
+                               int64_t state_pitch, const double *lateral, int64_t lat_rows, int64_t lat_pitch, const double *discharge_g,
+                               const double *grad_out_g, int64_t gauge_pitch, const double *grad_qch_final, const double *grad_qfull_final,
+                               double *grad_lateral, double *grad_qch0, double *grad_qfull0, double *grad_coef, void *work, int64_t work_bytes,
+                               int64_t T, int64_t nsub, void *stream)
+{
+    AdjointCall c{P, lateral, lat_rows, discharge_g, grad_out_g, work, work_bytes, T, nsub, (hipStream_t)stream, members, 0, lat_pitch,
+                  gauge_pitch, state_pitch, n_gauges, gauges, grad_lateral != nullptr};
+    return unit_adjoint("rr_unit_adjoint_gauges_dev", kUnitAdjointGauges, c, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral,
+                        grad_qch0, grad_qfull0, grad_coef);
+}
+
 // ---- adjoint of the unit-hydrograph convolution (rr_kernels_adjoint_unit.hpp) ----
 
 namespace {

@@ -22,6 +22,14 @@
 // appended and form every index as (ENS ? index + offset : index); the member is blockIdx.y, in the reduction, whose y is the
 // sub-step range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling on the member's pointers: three share a
 // __forceinline__ body with their kernel, two (rows, merge) repeat its statements (see k_adj_merge_unit_batch).
+//
+// Gauge form (rr_unit_adjoint_gauges_dev): dL/d(discharge) is given at G gauged reaches only, as masked (T, G)
+// blocks, and the slot map of rr_kernels_adjoint.hpp (k_adj_gauge_fill / _scatter / _slots) says which column a position reads.  What
+// differs from the Rapid gauge form is the headwater: its cotangent passes into dL/d(lateral) as it is, so the mask
+// (k_adj_mask_unit_gauges) needs the position of every gauge and the row pass (k_adj_rows_unit_gauges) reads the block too, not only
+// the reverse tick (k_adj_tick_unit with a trailing GAUGES flag).  Every other position starts from 0.0, which is what the dense form
+// reads there, so the sums are the dense call's on the same values.  The existing kernels are not touched: the gauge kernels repeat
+// the statements of theirs (section 12e: a shared inlined body reordered the single-member kernels).
 #pragma once
 
 namespace {
@@ -45,7 +53,18 @@ struct UnitAdjTickArgs {
 struct UnitAdjTickEnsArgs : UnitAdjTickArgs {
     int64_t tape_pitch, g_pitch, gf_pitch;
 };
-template <bool ENS> using UnitAdjTickArgsOf = typename std::conditional<ENS, UnitAdjTickEnsArgs, UnitAdjTickArgs>::type;
+// The gauge form of either: g is the masked (T, n_gauges) block (member blockIdx.y's at g_pitch), read where slot[p] >= 0.
+struct UnitAdjTickGaugeArgs : UnitAdjTickArgs {
+    const int32_t *slot;       // [n] engine order: the gauge column of position p, -1 where the reach has no gauge
+    int64_t n_gauges;
+};
+struct UnitAdjTickGaugeEnsArgs : UnitAdjTickEnsArgs {
+    const int32_t *slot;
+    int64_t n_gauges;
+};
+template <bool ENS, bool GAUGES = false> using UnitAdjTickArgsOf =
+    typename std::conditional<GAUGES, typename std::conditional<ENS, UnitAdjTickGaugeEnsArgs, UnitAdjTickGaugeArgs>::type,
+                              typename std::conditional<ENS, UnitAdjTickEnsArgs, UnitAdjTickArgs>::type>::type;
 __device__ __forceinline__ int64_t member_tape0(const UnitAdjTickArgs &) { return 0; }
 __device__ __forceinline__ int64_t member_tape0(const UnitAdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.tape_pitch; }
 __device__ __forceinline__ int64_t member_g0(const UnitAdjTickArgs &) { return 0; }
@@ -54,9 +73,10 @@ __device__ __forceinline__ int64_t member_gf0(const UnitAdjTickArgs &) { return 
 __device__ __forceinline__ int64_t member_gf0(const UnitAdjTickEnsArgs &e) { return (int64_t)blockIdx.y * e.gf_pitch; }
 
 // One reverse tick: mu of every active inner position (k_adj_tick with the two-state recurrence).
-// ENS: the member-batched form; the fma sequence of a member is the single call's.
-template <bool SINGLE_SUBSTEP, bool ENS = false>
-__global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgsOf<ENS> a)
+// ENS: the member-batched form; the fma sequence of a member is the single call's.  GAUGES: dL/d(discharge) comes from the gauge
+// block through the slot map (one dependent load per position); the fma sequence is the dense form's on the same values.
+template <bool SINGLE_SUBSTEP, bool ENS = false, bool GAUGES = false>
+__global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgsOf<ENS, GAUGES> a)
 {
     const int32_t p = a.p_lo + (int32_t)(blockIdx.x * kBlock + threadIdx.x);
     if (p >= a.p_hi) return;
@@ -70,7 +90,15 @@ __global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgsO
     else { uint32_t rem; t = a.nsub.div(ts, rem); }
 
     const int64_t mt = member_tape0(a), mg = member_g0(a), mf = member_gf0(a);
-    double m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
+    double m;
+    if constexpr (GAUGES) {
+        m = 0.0;
+        if (a.g) {
+            const int32_t j = a.slot[p];
+            if (j >= 0) m = a.g[ENS ? (int64_t)t * a.n_gauges + j + mg : (int64_t)t * a.n_gauges + j];
+        }
+    } else
+        m = a.g ? a.g[ENS ? (int64_t)t * a.n + p + mg : (int64_t)t * a.n + p] : 0.0;
     if (r == 0) {
         if (a.gff) m += a.gff[ENS ? p + mf : p];
         if (a.gcf) m += a.gcf[ENS ? p + mf : p];
@@ -111,6 +139,40 @@ __global__ __launch_bounds__(kBlock) void k_adj_mask_unit_batch(double *dst, con
 {
     const int64_t m = blockIdx.z;
     adj_mask_unit(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, inv, child_ptr, n, T, inv_nsub);
+}
+
+// The gauge form: grad_out and discharge are (T, n_gauges), column j being reach gauges[j]; the masked block (dst, dense, T x
+// n_gauges) stays in gauge order.  One gauge per lane, rows strided over blockIdx.y; the expression per element is adj_mask_unit's.
+// gauges[] is not range-checked here: the caller vouches for distinct indices in [0, n).
+__device__ __forceinline__ void adj_mask_unit_gauges(double *dst, const double *grad_out, const double *discharge, const int32_t *gauges,
+                                                     const int32_t *inv, const int32_t *child_ptr, int64_t n_gauges, int64_t T, double inv_nsub)
+{
+    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (j >= n_gauges) return;
+    const int32_t p = inv[gauges[j]];
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const int64_t k = t * n_gauges + j;
+        const double g = grad_out[k];
+        dst[k] = hw ? g : (discharge[k] > 0.0 ? g * inv_nsub : 0.0);
+    }
+}
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_gauges(double *dst, const double *grad_out, const double *discharge,
+                                                                 const int32_t *gauges, const int32_t *inv, const int32_t *child_ptr,
+                                                                 int64_t n_gauges, int64_t T, double inv_nsub)
+{
+    adj_mask_unit_gauges(dst, grad_out, discharge, gauges, inv, child_ptr, n_gauges, T, inv_nsub);
+}
+// member blockIdx.z (y walks the rows): its block at dst_pitch (T * n_gauges: the blocks are adjacent), its discharge_g and grad_out_g
+// at gauge_pitch
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_gauges_batch(double *dst, const double *grad_out, const double *discharge,
+                                                                       const int32_t *gauges, const int32_t *inv, const int32_t *child_ptr,
+                                                                       int64_t n_gauges, int64_t T, double inv_nsub, int64_t dst_pitch,
+                                                                       int64_t gauge_pitch)
+{
+    const int64_t m = blockIdx.z;
+    adj_mask_unit_gauges(dst + m * dst_pitch, grad_out + m * gauge_pitch, discharge + m * gauge_pitch, gauges, inv, child_ptr, n_gauges, T,
+                         inv_nsub);
 }
 
 // Inner-indexed vectors to engine positions: the tape's first rows (q_full0 where the reach below reads its "old" value), the
@@ -339,6 +401,88 @@ __global__ __launch_bounds__(kBlock) void k_adj_rows_unit_batch(double *dst, con
     const double *md = mtape + (d >= 0 ? d : 0);
     for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
         const double gv = g ? g[t * n + p] : 0.0;
+        double v;
+        if (hw) {
+            double m = 0.0;
+            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
+            v = __builtin_fma(c1d + c2d, m, gv);
+        } else {
+            v = 0.0;
+            for (int64_t k = 0; k < nsub; ++k) {
+                const int64_t ts = t * nsub + k;
+                double phi = gv;
+                if (ts == total_substeps - 1 && gff) phi += gff[p];
+                if (d >= 0) {
+                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
+                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
+                }
+                v += phi;
+            }
+        }
+        dst[t * n + p] = v;
+    }
+}
+
+// The gauge form of the row pass: g is the masked (T, n_gauges) block and slot the engine-order map, so a position's dL/d(discharge)
+// is the block's element at (t, slot[p]) or 0.0; a headwater needs it as much as an inner reach (its row is dL/dout + ...).  dst and
+// the block are different memory here.  k_adj_rows_unit's statements otherwise (repeated, not shared: see k_adj_merge_unit_batch).
+__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_gauges(double *dst, const double *g, const int32_t *slot, int64_t n_gauges, const double *gff,
+                                                                 const double *mtape, const int32_t *lag, const int32_t *child_ptr, const int32_t *down,
+                                                                 const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
+                                                                 int64_t total_substeps, int32_t dmax)
+{
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    const int32_t d = down[p];
+    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
+    const double *md = mtape + (d >= 0 ? d : 0);
+    const int32_t j = g ? slot[p] : -1;      // the gauge column of this position
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const double gv = j >= 0 ? g[t * n_gauges + j] : 0.0;
+        double v;
+        if (hw) {
+            double m = 0.0;
+            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
+            v = __builtin_fma(c1d + c2d, m, gv);
+        } else {
+            v = 0.0;
+            for (int64_t k = 0; k < nsub; ++k) {
+                const int64_t ts = t * nsub + k;
+                double phi = gv;
+                if (ts == total_substeps - 1 && gff) phi += gff[p];
+                if (d >= 0) {
+                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
+                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
+                }
+                v += phi;
+            }
+        }
+        dst[t * n + p] = v;
+    }
+}
+// member blockIdx.z: its gradient rows at row_pitch, its block T * n_gauges doubles after the previous member's, the rest as in
+// k_adj_rows_unit_batch
+__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_gauges_batch(double *dst, const double *g, const int32_t *slot, int64_t n_gauges,
+                                                                       const double *gff, const double *mtape, const int32_t *lag, const int32_t *child_ptr,
+                                                                       const int32_t *down, const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
+                                                                       int64_t total_substeps, int32_t dmax, int64_t row_pitch, int64_t gf_pitch, int64_t tape_pitch)
+{
+    const int64_t member = blockIdx.z;
+    dst += member * row_pitch; mtape += member * tape_pitch;
+    if (g) g += member * T * n_gauges;
+    if (gff) gff += member * gf_pitch;
+    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+    if (p >= n) return;
+    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
+    const bool hw = child_ptr[p] == child_ptr[p + 1];
+    const int32_t d = down[p];
+    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
+    const double *md = mtape + (d >= 0 ? d : 0);
+    const int32_t j = g ? slot[p] : -1;      // the gauge column of this position
+    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
+        const double gv = j >= 0 ? g[t * n_gauges + j] : 0.0;
         double v;
         if (hw) {
             double m = 0.0;

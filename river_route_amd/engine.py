@@ -320,6 +320,26 @@ class Plan:
                                                    ptr(grad_qfull0), ptr(grad_coef), ptr(work), int(work_bytes), int(T), int(num_substeps),
                                                    stream))
 
+    def unit_adjoint_gauges_work_bytes(self, members: int, n_gauges: int, T: int, num_substeps: int = 1, with_grad_lateral: bool = False) -> int:
+        """rr_unit_adjoint_gauges_work_bytes: bytes of work memory unit_adjoint_gauges_dev needs for `members` series of T rows x
+        num_substeps sub-steps with dL/d(discharge) at n_gauges reaches; with_grad_lateral: the call will be given a grad_lateral
+        (readies the plan for adjoint calls on first use)."""
+        out = C.c_int64(0)
+        check(_lib.lib().rr_unit_adjoint_gauges_work_bytes(self._h, int(members), int(n_gauges), int(T), int(num_substeps),
+                                                           int(bool(with_grad_lateral)), C.byref(out)))
+        return int(out.value)
+
+    def unit_adjoint_gauges_dev(self, members, n_gauges, gauges, q_ch0, q_full0, state_pitch, lateral, lat_rows, lat_pitch, discharge_g,
+                                grad_out_g, gauge_pitch, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef,
+                                work, work_bytes, T, num_substeps, stream=None) -> None:
+        """rr_unit_adjoint_gauges_dev (enqueue only): unit_adjoint_batch_dev with the discharge and its gradient given as
+        [members, T, n_gauges] at the reaches gauges[n_gauges] (device int32, params order, distinct; not range-checked)."""
+        check(_lib.lib().rr_unit_adjoint_gauges_dev(self._h, int(members), int(n_gauges), ptr(gauges), ptr(q_ch0), ptr(q_full0),
+                                                    int(state_pitch), ptr(lateral), int(lat_rows), int(lat_pitch), ptr(discharge_g),
+                                                    ptr(grad_out_g), int(gauge_pitch), ptr(grad_qch_final), ptr(grad_qfull_final),
+                                                    ptr(grad_lateral), ptr(grad_qch0), ptr(grad_qfull0), ptr(grad_coef), ptr(work),
+                                                    int(work_bytes), int(T), int(num_substeps), stream))
+
     def muskingum_route_dev(self, q_t, discharge, out_rows, num_output_steps, num_routing_per_output,
                             stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output)

@@ -36,6 +36,9 @@ rr_rapid_adjoint_gauges_dev, which takes the (T, G) cotangent as it is -- no (T,
     Qg, q_final = rr.grad.rapid_route(plan, q0, qlateral, k, x, 900.0, 3600.0, gauges=gauges)      # Qg[T, G], column j is reach gauges[j]
     (1 - rr.grad.scores(observed, Qg)['kge2012']).mean().backward()
 
+unit_route, unit_route_batch, unit_muskingum and unit_muskingum_batch take gauges= in the same way (backward:
+rr_unit_adjoint_gauges_dev, where a gauged headwater passes its cotangent to the lateral rows as it is).
+
 Float64 rows, one plan on one GPU, the edge data of the reference's callers: float32 rows, partitioned plans and plans with
 set_unit_weights edge data are refused, and so are 3-D rows everywhere but in the *_batch functions.
 
@@ -54,7 +57,7 @@ from . import engine, metrics
 from .engine import Plan
 
 __all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'RapidRouteGauges', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
-           'unit_muskingum', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores']
+           'unit_muskingum', 'UnitRouteGauges', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores']
 
 
 def muskingum_coefficients(k, x, dt_routing):
@@ -209,7 +212,7 @@ def _in_windows(T, rows_per_window, state, route, axis=0):
 
 
 def _check_gauges(gauges, n):
-    """gauges= of rapid_route and rapid_route_batch: a 1-D integer array or tensor of distinct params-order reach indices in [0, n).
+    """gauges= of the routing functions: a 1-D integer array or tensor of distinct params-order reach indices in [0, n).
     Returns them as an int64 host array; for a tensor on a GPU only its shape and type are checked, and None is returned: its values
     are read (by _gauge_values) after the device checks."""
     if isinstance(gauges, torch.Tensor):
@@ -593,7 +596,13 @@ def uh_convolve(kernel, state, depth):
     return UhConvolve.apply(kernel, state, depth)
 
 
-def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None):
+def _unit_gauges_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3):
+    """UnitRouteGauges for one series: the one-member case of the batched gauge call."""
+    d, q_ch, q_full = UnitRouteGauges.apply(plan, nsub, None, on_device, q_ch.unsqueeze(0), q_full.unsqueeze(0), lateral.unsqueeze(0), c1, c2, c3)
+    return d[0], q_ch[0], q_full[0]
+
+
+def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None, gauges=None):
     """Differentiable unit_route (river_route/routers/_numba_kernels.py:88-171) on an already convolved lateral:
     (discharge[T, n], q_ch[n_inner], q_full[n_inner]) as torch tensors on the plan's device.
 
@@ -601,23 +610,36 @@ def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_
     the plan's GPU; k and x are float64 tensors of n values on any device.  c1, c2, c3 come from muskingum_coefficients(k, x,
     dt_routing) and go onto the plan without c4; the forward is Plan.unit_route_dev, bit for bit.  Gradients reach q_ch0, q_full0,
     lateral, k and x (a headwater's k and x get 0: its coefficients are never read).  rows_per_window routes the series in windows
-    chained through the states, so the tape memory of the backward pass is one window's.  Every argument is checked before the GPU
-    is touched."""
+    chained through the states, so the tape memory of the backward pass is one window's.
+
+    gauges (a 1-D integer array or tensor of G distinct params-order reach indices, headwaters and inner reaches alike) makes the
+    first result discharge[T, G], column j being reach gauges[j], for a loss that reads gauged reaches only: the values and every
+    gradient are those of the call without it and discharge[:, gauges], bit for bit, but only the gauge columns are kept for the
+    backward pass, which takes the (T, G) cotangent as it is (rr_unit_adjoint_gauges_dev), so nothing (T, n) is allocated for it
+    unless lateral requires grad.  Every argument is checked before the GPU is touched."""
     nsub = _check_call(plan, 'n_inner', ((q_ch0, 'q_ch0'), (q_full0, 'q_full0')), k, x, dt_routing, dt_runoff, rows_per_window)
+    host_gauges = None if gauges is None else _check_gauges(gauges, plan.n)
     T = _check_rows(lateral, 'lateral', plan.n)
     _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    if gauges is not None:
+        on_device = _upload_gauges(plan, gauges, host_gauges)
+        return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: _unit_gauges_one(
+            plan, nsub, on_device, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
     return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: UnitRoute.apply(
         plan, nsub, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
 
 
-def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None):
+def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None, gauges=None):
     """Differentiable UnitMuskingum (the router's _router, river_route/routers/UnitMuskingum.py:72-98): the runoff depths are
     convolved with the unit-hydrograph kernel (uh_convolve) and the result is routed (unit_route).  Returns (discharge[T, n],
     q_ch[n_inner], q_full[n_inner], uh_state_out[n_ks, n]); gradients reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x.
     With rows_per_window each window convolves its own rows and hands q_ch, q_full and the convolution's state to the next, as the
-    router does from file to file."""
+    router does from file to file.  gauges makes the first result discharge[T, G] at the reaches gauges[j], as in unit_route: the
+    routing step keeps and differentiates the gauge columns only (each window gathers its own rows), the convolution is unchanged,
+    and every value and gradient is that of the call without it and discharge[:, gauges], bit for bit."""
     nsub = _check_call(plan, 'n_inner', ((q_ch0, 'q_ch0'), (q_full0, 'q_full0')), k, x, dt_routing, dt_runoff, rows_per_window)
+    host_gauges = None if gauges is None else _check_gauges(gauges, plan.n)
     T = _check_rows(depth, 'depth', plan.n)
     if not isinstance(uh_kernel, torch.Tensor) or uh_kernel.ndim != 2 or int(uh_kernel.shape[0]) < 1:
         raise ValueError('uh_kernel must be a 2-D (n_ks, n) tensor')
@@ -626,9 +648,12 @@ def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_ro
     _check_tensor(uh_state, 'uh_state', (n_ks, plan.n))
     _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
+    on_device = None if gauges is None else _upload_gauges(plan, gauges, host_gauges)
 
     def route(t0, t1, q_ch, q_full, state):
         lateral, state = UhConvolve.apply(uh_kernel, state, depth[t0:t1])
+        if on_device is not None:
+            return (*_unit_gauges_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
         return (*UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (q_ch0, q_full0, uh_state), route)
@@ -758,6 +783,81 @@ class UnitRouteBatch(torch.autograd.Function):
         return (None, None, None, g_qch0, g_qfull0, g_lat, *coef)
 
 
+class UnitRouteGauges(torch.autograd.Function):
+    """(discharge[B, T, G], q_ch[B, n_inner], q_full[B, n_inner]) = UnitRouteBatch with the discharge at the reaches `gauges` only (a
+    pair of device tensors, int32 and int64, of G distinct params-order indices).  Forward: UnitRoute's call, member by member, into one
+    (T, n) scratch tensor that is not kept, the gauge columns gathered out of it; every value is UnitRoute's.  Only q_ch0, q_full0,
+    lateral and the (B, T, G) gauge discharge are kept.  Backward: rr_unit_adjoint_gauges_dev on groups of `per_sweep` members (None:
+    all) in ascending order, the groups' coefficient gradients added in that order; its work memory has gradient rows only when lateral
+    requires grad."""
+
+    @staticmethod
+    def forward(ctx, plan, nsub, per_sweep, gauges, q_ch0, q_full0, lateral, c1, c2, c3):
+        dev = plan.device
+        g32, g64 = gauges
+        B, T, G = int(lateral.shape[0]), int(lateral.shape[1]), int(g32.shape[0])
+        _set_coeffs(plan, c1, c2, c3, None, dev)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        q_ch = q_ch0.detach().clone(memory_format=torch.contiguous_format)
+        q_full = q_full0.detach().clone(memory_format=torch.contiguous_format)
+        scratch = torch.empty((T, plan.n), dtype=torch.float64, device=lateral.device)
+        discharge = torch.empty((B, T, G), dtype=torch.float64, device=lateral.device)
+        lat = lateral.detach()
+        for m in range(B):
+            plan.unit_route_dev(q_ch[m], q_full[m], lat[m], T, scratch, T, T, nsub, stream)
+            torch.index_select(scratch, 1, g64, out=discharge[m])
+        ctx.plan, ctx.nsub, ctx.per_sweep, ctx.g32 = plan, int(nsub), per_sweep, g32
+        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach())
+        ctx.save_for_backward(q_ch0, q_full0, lateral, discharge)
+        ctx.set_materialize_grads(False)
+        return discharge, q_ch, q_full
+
+    @staticmethod
+    def backward(ctx, grad_discharge, grad_qch, grad_qfull):
+        plan, nsub, g32 = ctx.plan, ctx.nsub, ctx.g32
+        q_ch0, q_full0, lateral, discharge = ctx.saved_tensors
+        need = ctx.needs_input_grad      # plan, nsub, per_sweep, gauges, q_ch0, q_full0, lateral, c1, c2, c3
+        want_coef, want_lat = any(need[7:10]), need[6]
+        if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[4:7]) or want_coef):
+            return (None,) * 10
+        B, T, n, ni, G = int(lateral.shape[0]), int(lateral.shape[1]), plan.n, plan.n_inner, int(g32.shape[0])
+        _set_coeffs(plan, *ctx.coeffs, None, plan.device)
+        stream = torch.cuda.current_stream(plan.device).cuda_stream
+        f64 = dict(dtype=torch.float64, device=discharge.device)
+        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
+        g_qch0 = torch.empty((B, ni), **f64) if need[4] else None
+        g_qfull0 = torch.empty((B, ni), **f64) if need[5] else None
+        g_lat = torch.empty((B, T, n), **f64) if want_lat else None
+        lat = lateral.detach()
+        # one pitch serves both states: one of them shared and the other not, or no inner reach at all, and they go as dense rows
+        qc, qf = q_ch0.detach(), q_full0.detach()
+        if ni == 0 or B == 1 or qc.stride(0) != qf.stride(0):
+            qc, qf = qc.contiguous(), qf.contiguous()
+        pitch = int(qc.stride(0)) if B > 1 and ni > 0 else ni
+        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
+        nbytes = max(plan.unit_adjoint_gauges_work_bytes(g, G, T, nsub, want_lat) for g in {group, B % group or group})
+        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
+        g_coef = None
+
+        def members(t, m0, m1):
+            return None if t is None else t[m0:m1]
+
+        def state(t, m0):
+            return t.data_ptr() + 8 * m0 * pitch if ni > 0 else None
+
+        for m0 in range(0, B, group):
+            m1 = min(B, m0 + group)
+            part = torch.empty((3, n), **f64) if want_coef else None
+            plan.unit_adjoint_gauges_dev(m1 - m0, G, g32, state(qc, m0), state(qf, m0), pitch, lat[m0:m1], T, T * n,
+                                         None if g_out is None else discharge[m0:m1], members(g_out, m0, m1), T * G, members(g_c, m0, m1),
+                                         members(g_f, m0, m1), members(g_lat, m0, m1), members(g_qch0, m0, m1), members(g_qfull0, m0, m1),
+                                         part, work, nbytes, T, nsub, stream)
+            if want_coef:
+                g_coef = part if g_coef is None else g_coef + part
+        coef = [g_coef[j].to(c.device) if want_coef and need[7 + j] else None for j, c in enumerate(ctx.coeffs)]
+        return (None, None, None, None, g_qch0, g_qfull0, g_lat, *coef)
+
+
 def _check_unit_batch(plan, q_ch0, q_full0, rows, rows_name, single, k, x, dt_routing, dt_runoff, rows_per_window, members_per_sweep):
     """The checks unit_route_batch and unit_muskingum_batch share.  Returns nsub, B, T."""
     nsub = _check_call(plan, 'n_inner', (), k, x, dt_routing, dt_runoff, rows_per_window)
@@ -792,7 +892,7 @@ def uh_convolve_batch(kernel, state, depth):
     return UhConvolveBatch.apply(kernel, _per_member(state, B, (n_ks, n)), depth)
 
 
-def unit_route_batch(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None, members_per_sweep=None):
+def unit_route_batch(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_per_window=None, members_per_sweep=None, gauges=None):
     """unit_route for B series of convolved lateral inflow on one network and one set of coefficients: (discharge[B, T, n],
     q_ch[B, n_inner], q_full[B, n_inner]).
 
@@ -802,27 +902,37 @@ def unit_route_batch(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff,
     member), and so are its dL/dlateral, dL/dq_ch0 and dL/dq_full0; k and x get the sum over the members.  The backward pass is one
     rr_unit_adjoint_batch_dev call: its tick launches do not grow with B.  members_per_sweep (None: all members in one sweep) bounds the
     tape memory: the backward then runs groups of that many members in ascending order and adds the groups' coefficient gradients in
-    that order.  rows_per_window chains windows through the states as unit_route does.  Every argument is checked before the GPU is
-    touched."""
+    that order.  rows_per_window chains windows through the states as unit_route does.  gauges makes the first result
+    discharge[B, T, G] at the reaches gauges[j], as in unit_route: each member's values and gradients are those of unit_route(...,
+    gauges=gauges) for that member alone (backward: rr_unit_adjoint_gauges_dev).  Every argument is checked before the GPU is touched."""
     nsub, B, T = _check_unit_batch(plan, q_ch0, q_full0, lateral, 'lateral', 'unit_route', k, x, dt_routing, dt_runoff, rows_per_window,
                                    members_per_sweep)
+    host_gauges = None if gauges is None else _check_gauges(gauges, plan.n)
     _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
     ni = plan.n_inner
     whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
+    if gauges is not None:
+        on_device = _upload_gauges(plan, gauges, host_gauges)
+        return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,))),
+                           lambda t0, t1, q_ch, q_full: UnitRouteGauges.apply(
+                               plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(),
+                               c1, c2, c3), axis=1)
     return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,))),
                        lambda t0, t1, q_ch, q_full: UnitRouteBatch.apply(
                            plan, nsub, members_per_sweep, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(), c1, c2, c3), axis=1)
 
 
 def unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None,
-                         members_per_sweep=None):
+                         members_per_sweep=None, gauges=None):
     """unit_muskingum for B series of runoff depths: uh_convolve_batch and unit_route_batch chained per window, as unit_muskingum chains
     uh_convolve and unit_route.  depth is (B, T, n); uh_state is (B, n_ks, n), or (n_ks, n) for one shared by every member, as q_ch0 and
     q_full0 may be (n_inner,).  Returns (discharge[B, T, n], q_ch[B, n_inner], q_full[B, n_inner], uh_state_out[B, n_ks, n]); gradients
-    reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x, the shared ones summed over the members."""
+    reach q_ch0, q_full0, depth, uh_kernel, uh_state, k and x, the shared ones summed over the members.  gauges makes the first result
+    discharge[B, T, G] at the reaches gauges[j], as in unit_route_batch; the convolution is unchanged."""
     nsub, B, T = _check_unit_batch(plan, q_ch0, q_full0, depth, 'depth', 'unit_muskingum', k, x, dt_routing, dt_runoff, rows_per_window,
                                    members_per_sweep)
+    host_gauges = None if gauges is None else _check_gauges(gauges, plan.n)
     if not isinstance(uh_kernel, torch.Tensor) or uh_kernel.ndim != 2 or int(uh_kernel.shape[0]) < 1:
         raise ValueError('uh_kernel must be a 2-D (n_ks, n) tensor')
     n_ks, n, ni = int(uh_kernel.shape[0]), plan.n, plan.n_inner
@@ -831,8 +941,12 @@ def unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x,
     _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (depth, 'depth'), (uh_kernel, 'uh_kernel'), (uh_state, 'uh_state')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
 
+    on_device = None if gauges is None else _upload_gauges(plan, gauges, host_gauges)
+
     def route(t0, t1, q_ch, q_full, state):      # a member's rows of a window are adjacent: the convolution reads them in place
         lateral, state = UhConvolveBatch.apply(uh_kernel, state, depth[:, t0:t1])
+        if on_device is not None:
+            return (*UnitRouteGauges.apply(plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
         return (*UnitRouteBatch.apply(plan, nsub, members_per_sweep, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,)), _per_member(uh_state, B, (n_ks, n))),
