@@ -612,6 +612,34 @@ int rr_metrics_adjoint_dev(int device, int64_t n, int64_t rows, const void *y_tr
                            int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
                            void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream);
 
+/* ---- adjoint of gridded runoff -> catchment inflow (rr.grad.runoff_to_qlateral) ----
+ * The gradient of a scalar loss L through one rr_runoff_to_qlateral_dev call with respect to the runoff block and to the weights.
+ * n_rivers, n_points, T, the CSR arrays, runoff with its type and strides, area and flags are those of the forward call;
+ * grad_qlateral[T * n_rivers] is dL/dqlateral.  With S[t, r] = sum_k weights[k] runoff(t, indices[k]) over the CSR row of river r and
+ * V = S[t] - S[t - 1] (RR_RUNOFF_CUMULATIVE, t > 0) or S[t], both rounded as the forward rounds them:
+ *   M[t, r]  = V is not NaN and (no RR_RUNOFF_FORCE_POSITIVE or V >= 0)      -- V == 0 passes its gradient, as torch.clamp does
+ *   Gb[t, r] = M ? grad_qlateral[t, r] * area[r] : 0                          -- area NULL: 1
+ *   Gs[t, r] = Gb[t, r] - Gb[t + 1, r] (cumulative; row T - 1 has no t + 1 term), else Gb[t, r]
+ *   grad_runoff[t, p] = sum over the pairs k with indices[k] = p, k ascending, of weights[k] * Gs[t, r_k]
+ *   grad_weights[k]   = sum over t ascending of Gs[t, r_k] * runoff(t, indices[k])
+ * in float64, each product and each sum rounded separately; terms with Gs == 0 are skipped, so a NaN in the runoff (whose Gs is 0)
+ * poisons nothing and both gradients are finite whenever grad_qlateral is.  area gets no gradient.
+ * t_indptr[n_points + 1], t_pairs[nnz]: the transposed (CSC) structure -- t_pairs[t_indptr[p] .. t_indptr[p + 1]) are the pair indices k
+ * with indices[k] = p, ascending (a stable sort of the pairs by point).  Neither structure is range-checked on the device.
+ * grad_runoff (may be NULL) has the runoff's element type, element (t, p) at grad_runoff[t * grad_stride_t + p], grad_stride_t >=
+ * n_points; every element of its T x n_points is written (a point no river uses gets 0), the float64 sum rounded once on the store.
+ * grad_weights (may be NULL) has nnz values.  An output that is NULL costs no pass; both NULL is RR_E_INVALID.
+ * Work memory: rr_runoff_adjoint_work_bytes = 8 * n_rivers * T_pad bytes, T_pad = T rounded up to a multiple of 16 (Gs, river-major),
+ * 16-byte aligned.  Enqueue only, allocates nothing, no atomics: the same inputs give the same bits.
+ * RR_E_INVALID: a null structure array, a negative size or stride, RR_RUNOFF_KEEP_NAN, both outputs NULL (all refused before a
+ * device is looked for); RR_E_STATE, with the byte count in rr_last_error(): work_bytes too small; RR_E_UNSUPPORTED: more than
+ * 1,048,560 rows in one call. */
+int rr_runoff_adjoint_work_bytes(int64_t n_rivers, int64_t n_points, int64_t T, int64_t *bytes);
+int rr_runoff_adjoint_dev(int device, int64_t n_rivers, int64_t n_points, int64_t T, const int32_t *indptr, const int32_t *indices,
+                          const double *weights, const int32_t *t_indptr, const int32_t *t_pairs, const void *runoff, int runoff_is_f32,
+                          int64_t stride_t, int64_t stride_p, const double *area, int flags, const double *grad_qlateral,
+                          void *grad_runoff, int64_t grad_stride_t, double *grad_weights, void *work, int64_t work_bytes, void *stream);
+
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);

@@ -15,8 +15,9 @@
 // One translation unit, in this order: rr_common.hpp (constants, index helpers), rr_kernels_tick.hpp, rr_kernels_tile.hpp,
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
 // rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp, rr_kernels_adjoint_unit.hpp (device code), rr_exec.hpp (plan object, executor),
-// then the C ABI below; rr_adjoint.hpp (the adjoints' host side) and rr_kernels_metrics_adjoint.hpp (the adjoint of the skill
-// scores, device code) are included where their entry points are.
+// then the C ABI below; rr_adjoint.hpp (the adjoints' host side), rr_kernels_metrics_adjoint.hpp (the adjoint of the skill
+// scores, device code) and rr_kernels_runoff_adjoint.hpp (the adjoint of the gridded-runoff inflow, device code) are included where
+// their entry points are.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
 #include "rr_kernels_tile.hpp"
@@ -1659,6 +1660,83 @@ int rr_metrics_adjoint_dev(int device, int64_t n, int64_t rows, const void *y_tr
     else { if (pred_is_f32) RR_METRICS_ADJ_LAUNCH(double, float); else RR_METRICS_ADJ_LAUNCH(double, double); }
 #undef RR_METRICS_ADJ_LAUNCH
     HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+}  // extern "C"
+
+// ---- adjoint of gridded runoff -> catchment inflow (rr_kernels_runoff_adjoint.hpp) ----
+
+#include "rr_kernels_runoff_adjoint.hpp"      // here, at the end: the kernels above keep their place in the code object
+
+extern "C" {
+
+int rr_runoff_adjoint_work_bytes(int64_t n_rivers, int64_t n_points, int64_t T, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, "rr_runoff_adjoint_work_bytes: null out");
+    *bytes = 0;
+    if (n_rivers < 0 || n_points < 0 || T < 0 || n_rivers > 0x7FFFFFFFLL || n_points > 0x7FFFFFFFLL)
+        return fail(RR_E_INVALID, "rr_runoff_adjoint_work_bytes: sizes out of range");
+    const int64_t t_pad = (T + kRunoffRows - 1) / kRunoffRows * kRunoffRows;
+    *bytes = n_rivers * t_pad * (int64_t)sizeof(double);      // Gs, river-major
+    return RR_OK;
+}
+
+int rr_runoff_adjoint_dev(int device, int64_t n_rivers, int64_t n_points, int64_t T, const int32_t *indptr, const int32_t *indices,
+                          const double *weights, const int32_t *t_indptr, const int32_t *t_pairs, const void *runoff, int runoff_is_f32,
+                          int64_t stride_t, int64_t stride_p, const double *area, int flags, const double *grad_qlateral, void *grad_runoff,
+                          int64_t grad_stride_t, double *grad_weights, void *work, int64_t work_bytes, void *stream)
+{
+    // what the arguments alone decide comes first, so that it is refused with or without a GPU
+    if (n_rivers < 0 || n_points < 0 || T < 0 || n_rivers > 0x7FFFFFFFLL || n_points > 0x7FFFFFFFLL)
+        return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: sizes out of range");
+    if (flags & RR_RUNOFF_KEEP_NAN) return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: RR_RUNOFF_KEEP_NAN has no adjoint (the NaN fill is part of the mask)");
+    if (!grad_runoff && !grad_weights) return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: neither grad_runoff nor grad_weights is asked for");
+    if (!indptr || !indices || !weights || !t_indptr || !t_pairs) return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: null structure array");
+    if (stride_t < 0 || stride_p < 0 || (grad_runoff && grad_stride_t < n_points))
+        return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: negative stride, or grad_stride_t shorter than n_points");
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_runoff_adjoint_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    if (T == 0) return RR_OK;
+    if (!runoff || !grad_qlateral) return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: null array");
+    const int64_t chunks = (T + kRunoffRows - 1) / kRunoffRows, t_pad = chunks * kRunoffRows;
+    if (chunks > 65535) return fail(RR_E_UNSUPPORTED, "rr_runoff_adjoint_dev: more than 1,048,560 time steps in one call");
+    const int64_t need = n_rivers * t_pad * (int64_t)sizeof(double);
+    if (need > 0 && (!work || work_bytes < need))
+        return fail(RR_E_STATE, "rr_runoff_adjoint_dev: work memory smaller than rr_runoff_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    if ((uintptr_t)work & 15) return fail(RR_E_INVALID, "rr_runoff_adjoint_dev: work memory must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    double *gs = static_cast<double *>(work);
+    const unsigned river_blocks = (unsigned)((n_rivers + kBlock - 1) / kBlock), point_blocks = (unsigned)((n_points + kBlock - 1) / kBlock);
+    const bool vec = stride_t == 1 && stride_p % kRunoffRows == 0 && stride_p >= t_pad && ((uintptr_t)runoff & 15) == 0;
+    if (n_rivers > 0) {
+#define RR_RUNOFF_ADJ_RIVER(RT_, VEC_)                                                                                                        \
+    hipLaunchKernelGGL((k_runoff_adjoint_river<RT_, VEC_>), dim3(river_blocks, (unsigned)chunks), dim3(kBlock), 0, st, indptr, indices, weights, \
+                       (const RT_ *)runoff, stride_t, stride_p, area, flags, grad_qlateral, gs, n_rivers, T, t_pad)
+        if (runoff_is_f32) { if (vec) RR_RUNOFF_ADJ_RIVER(float, true); else RR_RUNOFF_ADJ_RIVER(float, false); }
+        else { if (vec) RR_RUNOFF_ADJ_RIVER(double, true); else RR_RUNOFF_ADJ_RIVER(double, false); }
+#undef RR_RUNOFF_ADJ_RIVER
+        HIPCHK(hipGetLastError());
+    }
+    if (grad_runoff && n_points > 0) {      // without rivers every column is empty and the pass writes the zeros
+        const dim3 g(point_blocks, (unsigned)((chunks + kRunoffAdjChunks - 1) / kRunoffAdjChunks));
+        if (runoff_is_f32)
+            hipLaunchKernelGGL(k_runoff_adjoint_point<float>, g, dim3(kBlock), 0, st, indptr, weights, t_indptr, t_pairs, gs, (float *)grad_runoff,
+                               grad_stride_t, n_rivers, n_points, T, t_pad);
+        else
+            hipLaunchKernelGGL(k_runoff_adjoint_point<double>, g, dim3(kBlock), 0, st, indptr, weights, t_indptr, t_pairs, gs, (double *)grad_runoff,
+                               grad_stride_t, n_rivers, n_points, T, t_pad);
+        HIPCHK(hipGetLastError());
+    }
+    if (grad_weights && n_rivers > 0) {
+#define RR_RUNOFF_ADJ_WEIGHT(RT_, VEC_)                                                                                                       \
+    hipLaunchKernelGGL((k_runoff_adjoint_weight<RT_, VEC_>), dim3(river_blocks), dim3(kBlock), 0, st, indptr, indices, (const RT_ *)runoff,      \
+                       stride_t, stride_p, gs, grad_weights, n_rivers, T, t_pad)
+        if (runoff_is_f32) { if (vec) RR_RUNOFF_ADJ_WEIGHT(float, true); else RR_RUNOFF_ADJ_WEIGHT(float, false); }
+        else { if (vec) RR_RUNOFF_ADJ_WEIGHT(double, true); else RR_RUNOFF_ADJ_WEIGHT(double, false); }
+#undef RR_RUNOFF_ADJ_WEIGHT
+        HIPCHK(hipGetLastError());
+    }
     return RR_OK;
 }
 

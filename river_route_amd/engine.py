@@ -12,7 +12,7 @@ from . import _lib
 from ._lib import RRError, check, ptr
 
 __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'uh_adjoint_work_bytes', 'uh_adjoint_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
-           'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
+           'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'runoff_adjoint_work_bytes', 'runoff_adjoint_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
            'metrics_update_dev', 'metrics_finish_dev', 'metrics_adjoint_work_bytes', 'metrics_adjoint_dev', 'grid_overlap_area',
            'grid_overlap_area_dev']
 
@@ -589,6 +589,23 @@ def runoff_to_qlateral_dev(n_rivers, n_points, T, indptr, indices, weights, runo
     check(_lib.lib().rr_runoff_to_qlateral_dev(int(device), int(n_rivers), int(n_points), int(T), ptr(indptr), ptr(indices), ptr(weights),
                                                ptr(runoff), int(bool(runoff_is_f32)), int(stride_t), int(stride_p),
                                                ptr(area) if area is not None else None, int(flags), ptr(out), stream))
+
+
+def runoff_adjoint_work_bytes(n_rivers: int, n_points: int, T: int) -> int:
+    """rr_runoff_adjoint_work_bytes: device work memory one rr_runoff_adjoint_dev of T rows needs (Gs, river-major)."""
+    out = C.c_int64(0)
+    check(_lib.lib().rr_runoff_adjoint_work_bytes(int(n_rivers), int(n_points), int(T), C.byref(out)))
+    return int(out.value)
+
+
+def runoff_adjoint_dev(n_rivers, n_points, T, indptr, indices, weights, t_indptr, t_pairs, runoff, runoff_is_f32, stride_t, stride_p, area,
+                       flags, grad_qlateral, grad_runoff, grad_stride_t, grad_weights, work, work_bytes, device: int = 0, stream=None) -> None:
+    """rr_runoff_adjoint_dev: dL/drunoff (the runoff's type, (T, n_points) rows grad_stride_t elements apart) and dL/dweights from
+    dL/dqlateral of one runoff_to_qlateral_dev call; either output may be None; only enqueues."""
+    check(_lib.lib().rr_runoff_adjoint_dev(int(device), int(n_rivers), int(n_points), int(T), ptr(indptr), ptr(indices), ptr(weights),
+                                           ptr(t_indptr), ptr(t_pairs), ptr(runoff), int(bool(runoff_is_f32)), int(stride_t), int(stride_p),
+                                           ptr(area), int(flags), ptr(grad_qlateral), ptr(grad_runoff), int(grad_stride_t),
+                                           ptr(grad_weights), ptr(work), int(work_bytes), stream))
 
 
 def resample_cast_dev(discharge, num_rows, n, factor, out, device: int = 0, stream=None) -> None:

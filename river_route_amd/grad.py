@@ -47,6 +47,14 @@ section 12c): the same five values, bit for bit, and a backward pass that writes
 
     kge = rr.grad.scores(observed, Q, columns=gauges)['kge2012']      # observed[T, n_gauges] against Q[:, gauges], no gather copy
     (1 - kge).mean().backward()
+
+The router's chain starts one step before the catchment inflow when it is fed gridded runoff, and runoff_to_qlateral is that step with
+a gradient: the forward is rr_runoff_to_qlateral_dev, bit for bit what engine.runoff_to_qlateral computes
+(weights product, cumulative -> incremental, clip, NaN fill, area), the backward rr_runoff_adjoint_dev, which reaches the runoff field
+and the weights of the catchment / grid-cell table; a RunoffMap holds the table's structure on the GPU for a whole training loop:
+
+    rmap = rr.grad.RunoffMap.from_source(src)                          # src: rr.runoff.prepare_runoff(...)
+    qlateral = rr.grad.runoff_to_qlateral(rmap, runoff * bias, weights, area, force_positive=True)      # runoff[T, n_points] -> [T, n]
 """
 from __future__ import annotations
 
@@ -57,7 +65,8 @@ from . import engine, metrics
 from .engine import Plan
 
 __all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'RapidRouteGauges', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
-           'unit_muskingum', 'UnitRouteGauges', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores']
+           'unit_muskingum', 'UnitRouteGauges', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores',
+           'RunoffMap', 'RunoffToQlateral', 'runoff_to_qlateral']
 
 
 def muskingum_coefficients(k, x, dt_routing):
@@ -1090,3 +1099,151 @@ def scores(y_true, y_pred, columns=None) -> dict:
         cols = _sorted_columns(columns.detach().cpu(), n, m)
     out = Scores.apply(y_pred, metrics._Rows(y_true, 'y_true').tensor, cols)
     return {k: out[i] for i, k in enumerate(metrics.SCORES)}
+
+
+class RunoffMap:
+    """The structure of a catchment / grid-cell weight table for runoff_to_qlateral: the CSR arrays of rr_runoff_to_qlateral_dev
+    (indptr[n + 1], indices[nnz]: river r owns the pairs indptr[r] .. indptr[r + 1] - 1, pair k reads grid point indices[k]) and the
+    transposed (CSC) structure the backward pass walks, derived here once by a stable sort of the pairs by point: t_indptr[n_points + 1]
+    and t_pairs[nnz], the pair indices of point p, ascending, at t_pairs[t_indptr[p] : t_indptr[p + 1]].  All four are int32 host arrays
+    and attributes, with pair_river[nnz], n_rivers, n_points, nnz and device.  Building one needs no GPU; the device copy (one int32
+    tensor) is uploaded by the first call that uses it and kept, so a training loop uploads the structure once."""
+
+    def __init__(self, indptr, indices, n_points, device: int = 0):
+        indptr, indices = np.asarray(indptr), np.asarray(indices)
+        for a, name in ((indptr, 'indptr'), (indices, 'indices')):
+            if a.ndim != 1 or not np.issubdtype(a.dtype, np.integer):
+                raise ValueError(f'{name} must be a 1-D integer array')
+        n_points = int(n_points)
+        imax = np.iinfo(np.int32).max
+        if indptr.shape[0] < 1 or indptr[0] != 0 or np.any(np.diff(indptr) < 0) or int(indptr[-1]) != indices.shape[0]:
+            raise ValueError('indptr must start at 0, not decrease and end at len(indices)')
+        if n_points < 0 or max(n_points, indptr.shape[0] - 1, indices.shape[0]) > imax:
+            raise ValueError('n_points must be >= 0 and the table must fit int32 indices')
+        if indices.shape[0] and (indices.min() < 0 or indices.max() >= n_points):
+            bad = int(indices.min() if indices.min() < 0 else indices.max())
+            raise ValueError(f'n_points is {n_points}, but indices refers to grid point {bad}')
+        self.indptr = np.ascontiguousarray(indptr, dtype=np.int32)
+        self.indices = np.ascontiguousarray(indices, dtype=np.int32)
+        self.n_rivers, self.n_points, self.nnz, self.device = int(indptr.shape[0]) - 1, n_points, int(indices.shape[0]), int(device)
+        self.t_pairs = np.argsort(self.indices, kind='stable').astype(np.int32)
+        self.t_indptr = np.concatenate(([0], np.cumsum(np.bincount(self.indices, minlength=n_points)))).astype(np.int32)
+        self.pair_river = np.repeat(np.arange(self.n_rivers, dtype=np.int32), np.diff(self.indptr))
+        self._tables = None
+
+    @classmethod
+    def from_source(cls, src, device: int | None = None):
+        """The map of a rr.runoff.RunoffSource (prepare_runoff): its CSR structure over the points of its runoff block."""
+        return cls(src.indptr, src.indices, int(np.shape(src.runoff_tp)[1]), src.device if device is None else device)
+
+    def device_pointers(self):
+        """Device addresses of (indptr, indices, t_indptr, t_pairs), uploading them on the first call."""
+        if self._tables is None:
+            host = np.concatenate((self.indptr, self.indices, self.t_indptr, self.t_pairs))
+            self._tables = torch.from_numpy(host).to(f'cuda:{self.device}')
+        base, n, nnz = self._tables.data_ptr(), self.n_rivers + 1, self.nnz
+        return tuple(base + 4 * k for k in (0, n, n + nnz, n + nnz + self.n_points + 1))
+
+
+class RunoffToQlateral(torch.autograd.Function):
+    """qlateral[T, n] = rr_runoff_to_qlateral_dev of runoff[T, n_points] (float32 or float64, any strides) with weights[nnz], area[n] or
+    None and the RR_RUNOFF_* flags, on torch's current stream.  Backward: rr_runoff_adjoint_dev, which computes the weighted sums and
+    the mask again, so beside references to the inputs only the point-major working copy of the runoff is kept (none where the runoff
+    came point-major); an output nobody needs is passed as NULL and costs no pass."""
+
+    @staticmethod
+    def forward(ctx, rmap, flags, runoff, weights, area):
+        dev = rmap.device
+        T = int(runoff.shape[0])
+        r, w = _vector_layout(runoff.detach()), weights.detach().contiguous()
+        a = None if area is None else area.detach().contiguous()
+        indptr, indices, _, _ = rmap.device_pointers()
+        out = torch.empty((T, rmap.n_rivers), dtype=torch.float64, device=runoff.device)
+        engine.runoff_to_qlateral_dev(rmap.n_rivers, rmap.n_points, T, indptr, indices, w, r.data_ptr(), r.dtype == torch.float32, r.stride(0),
+                                      r.stride(1), a, flags, out, device=dev, stream=torch.cuda.current_stream(dev).cuda_stream)
+        ctx.rmap, ctx.flags = rmap, int(flags)
+        ctx.point_major = r if ctx.needs_input_grad[2] or ctx.needs_input_grad[3] else None      # the working copy, once for both passes
+        ctx.save_for_backward(runoff, weights, area)      # a change of the runoff in place between the two passes is noticed
+        ctx.set_materialize_grads(False)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad_q):
+        need = ctx.needs_input_grad      # rmap, flags, runoff, weights, area
+        if grad_q is None or not (need[2] or need[3]):
+            return (None,) * 5
+        rmap, dev = ctx.rmap, ctx.rmap.device
+        runoff, weights, area = ctx.saved_tensors
+        T, P = int(runoff.shape[0]), rmap.n_points
+        where = runoff.device
+        r, w = ctx.point_major, weights.detach().contiguous()
+        a = None if area is None else area.detach().contiguous()
+        g = grad_q.to(dtype=torch.float64, device=where).contiguous()
+        grad_runoff = torch.empty((T, P), dtype=runoff.dtype, device=where) if need[2] else None
+        grad_weights = torch.empty(rmap.nnz, dtype=torch.float64, device=where) if need[3] else None
+        nbytes = engine.runoff_adjoint_work_bytes(rmap.n_rivers, P, T)
+        work = torch.empty(max(nbytes, 16), dtype=torch.uint8, device=where)
+        indptr, indices, t_indptr, t_pairs = rmap.device_pointers()
+        engine.runoff_adjoint_dev(rmap.n_rivers, P, T, indptr, indices, w, t_indptr, t_pairs, r.data_ptr(), r.dtype == torch.float32, r.stride(0),
+                                  r.stride(1), a, ctx.flags, g, grad_runoff, P, grad_weights, work, nbytes, device=dev,
+                                  stream=torch.cuda.current_stream(dev).cuda_stream)
+        return None, None, grad_runoff, grad_weights, None
+
+
+def _vector_layout(r):
+    """The (T, P) runoff as the kernels read it fastest: point-major with rows of a multiple of 16 elements, allocated in full and
+    zero-padded (stride_t = 1), so each gathered grid point is a run of 16-byte vectors.  A tensor that already lies so is returned as
+    it is; any other is copied once (sums in stored order do not depend on the layout: the values are the same bits)."""
+    T, P = (int(v) for v in r.shape)
+    t_pad = -(-T // 16) * 16
+    if r.stride(0) == 1 and r.stride(1) % 16 == 0 and r.stride(1) >= t_pad and r.data_ptr() % 16 == 0:
+        return r
+    block = torch.empty((P, t_pad), dtype=r.dtype, device=r.device)
+    block[:, T:] = 0
+    block[:, :T] = r.t()
+    return block[:, :T].t()
+
+
+def runoff_to_qlateral(rmap, runoff, weights, area=None, *, cumulative: bool = False, force_positive: bool = False):
+    """Gridded runoff -> catchment lateral inflow with autograd: qlateral (T, n) float64 on the GPU, bit for bit what
+    engine.runoff_to_qlateral computes from the same data -- S[t, r] = sum_k weights[k] runoff[t, indices[k]] over river r's pairs in
+    stored order, then cumulative -> incremental (row t minus row t - 1, row 0 kept), force_positive -> clip at 0, NaN -> 0, and
+    times area[r] when area is given -- carrying a graph to runoff and weights, whichever require grad.
+
+    rmap: a RunoffMap (the table's structure, uploaded once); runoff: (T, n_points) float32 or float64 tensor on the map's GPU, any
+    strides (a point-major tensor whose rows are a multiple of 16 elements long and allocated in full, block[:, :T].T, is read in
+    place; any other is copied into that layout once per call, which the kernels' vector path repays); weights: (nnz,) float64; area: None or (n,) float64, a constant (one that requires grad is refused).
+
+    The backward pass (rr_runoff_adjoint_dev, on torch's current stream) writes dL/drunoff in runoff's dtype and dL/dweights in
+    float64.  The clip passes the gradient where the unclipped value is >= 0 (torch.clamp's rule: an exactly dry catchment can be
+    learned wet); a NaN of the runoff passes none and poisons nothing, so both gradients are finite whenever the incoming one is.
+    Grid points no river uses get exact zeros.  No atomics: two backward passes give the same bits.  The irregular-time resampling of
+    rr.runoff.runoff_to_qlateral stays on the host and is not part of this.  Every argument is checked before the GPU is touched."""
+    if not isinstance(rmap, RunoffMap):
+        raise TypeError('rmap must be a rr.grad.RunoffMap')
+    for t, name, kinds in ((runoff, 'runoff', (torch.float32, torch.float64)), (weights, 'weights', (torch.float64,)), (area, 'area', (torch.float64,))):
+        if t is None and name == 'area':
+            continue
+        if not isinstance(t, torch.Tensor):
+            raise TypeError(f'{name} must be a torch tensor on the GPU')
+        if t.dtype not in kinds:
+            raise TypeError(f"{name} must be {' or '.join(str(k).replace('torch.', '') for k in kinds)} (it is {t.dtype})")
+    if runoff.dim() != 2:
+        raise ValueError('runoff must be a 2-D (time, points) tensor (members have no axis here: loop over them)')
+    if int(runoff.shape[0]) < 1:
+        raise ValueError('runoff has no rows')
+    if int(runoff.shape[1]) != rmap.n_points or rmap.n_points < 1:
+        raise ValueError(f'runoff has {int(runoff.shape[1])} grid points, rmap has {rmap.n_points} (at least one is needed)')
+    if tuple(weights.shape) != (rmap.nnz,):
+        raise ValueError(f'weights has shape {tuple(weights.shape)}, expected ({rmap.nnz},): one value per pair of rmap')
+    if area is not None:
+        if tuple(area.shape) != (rmap.n_rivers,):
+            raise ValueError(f'area has shape {tuple(area.shape)}, expected ({rmap.n_rivers},): one value per river')
+        if area.requires_grad:
+            raise ValueError('area is a constant here: it must not require grad (detach it)')
+    for t, name in ((runoff, 'runoff'), (weights, 'weights'), (area, 'area')):
+        if t is not None and (t.device.type != 'cuda' or (t.device.index or 0) != rmap.device):
+            raise ValueError(f"{name} must be on cuda:{rmap.device}, rmap's device (it is on {t.device})")
+    flags = (engine.RUNOFF_CUMULATIVE if cumulative else 0) | (engine.RUNOFF_FORCE_POSITIVE if force_positive else 0)
+    return RunoffToQlateral.apply(rmap, flags, runoff, weights, area)
