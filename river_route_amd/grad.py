@@ -64,8 +64,8 @@ import torch
 from . import engine, metrics
 from .engine import Plan
 
-__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'RapidRouteGauges', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
-           'unit_muskingum', 'UnitRouteGauges', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores',
+__all__ = ['muskingum_coefficients', 'RapidRoute', 'rapid_route', 'RapidRouteBatch', 'rapid_route_batch', 'UhConvolve', 'uh_convolve', 'UnitRoute', 'unit_route',
+           'unit_muskingum', 'UnitRouteBatch', 'unit_route_batch', 'UhConvolveBatch', 'uh_convolve_batch', 'unit_muskingum_batch', 'Scores', 'scores',
            'RunoffMap', 'RunoffToQlateral', 'runoff_to_qlateral']
 
 
@@ -114,6 +114,31 @@ def _route_backward(plan, coeffs, c4dt, device, grads, shapes, want_coef, need_c
     nbytes = work_bytes()
     work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)
     adjoint(*grads, *outs, g_coef, work, nbytes, stream)
+    coef = [g_coef[j].to(c.device) if want_coef and want else None for j, (c, want) in enumerate(zip(coeffs, need_coef))]
+    return (*outs, *coef)
+
+
+def _members_backward(plan, coeffs, c4dt, device, B, per_sweep, grads, shapes, want_coef, need_coef, work_bytes, adjoint):
+    """_route_backward for the B members of RapidRouteBatch and UnitRouteBatch: `grads` and the outputs (one per entry of `shapes`, a
+    member's shape) have a leading member axis.  The members go in groups of min(B, kMaxMembers, per_sweep) (per_sweep None: all) in
+    ascending order: `work_bytes(group_size)` sizes the one work buffer for the largest group, adjoint(m0, m1, *grads[m0:m1],
+    *outputs[m0:m1], part, work, nbytes, stream) makes the engine's call for members [m0, m1), and the groups' coefficient rows `part`
+    are added in that order."""
+    _set_coeffs(plan, *coeffs[:3], c4dt, plan.device)
+    stream = torch.cuda.current_stream(plan.device).cuda_stream
+    f64 = dict(dtype=torch.float64, device=device)
+    grads = [None if g is None else g.to(**f64).contiguous() for g in grads]
+    outs = [None if shape is None else torch.empty((B, *shape), **f64) for shape in shapes]
+    group = min(B, kMaxMembers, B if per_sweep is None else int(per_sweep))
+    nbytes = max(work_bytes(g) for g in {group, B % group or group})
+    work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=device)      # torch's allocator owns the tapes
+    g_coef = None
+    for m0 in range(0, B, group):
+        m1 = min(B, m0 + group)
+        part = torch.empty((len(coeffs), plan.n), **f64) if want_coef else None
+        adjoint(m0, m1, *(None if t is None else t[m0:m1] for t in (*grads, *outs)), part, work, nbytes, stream)
+        if want_coef:
+            g_coef = part if g_coef is None else g_coef + part
     coef = [g_coef[j].to(c.device) if want_coef and want else None for j, (c, want) in enumerate(zip(coeffs, need_coef))]
     return (*outs, *coef)
 
@@ -257,75 +282,6 @@ def _upload_gauges(plan, gauges, host):
     return g32, g32.long()
 
 
-class RapidRouteGauges(torch.autograd.Function):
-    """(discharge[B, T, G], q_final[B, n]) = RapidRouteBatch with the discharge at the reaches `gauges` only (a pair of device tensors,
-    int32 and int64, of G distinct params-order indices).  Forward: RapidRoute's call, member by member, into one (T, n) scratch tensor
-    that is not kept, the gauge columns gathered out of it; every value is RapidRoute's.  Only q0, qlateral and the (B, T, G) gauge
-    discharge are kept.  Backward: rr_rapid_adjoint_gauges_dev on groups of `per_sweep` members (None: all) in ascending order, the
-    groups' coefficient gradients added in that order; its work memory has gradient rows only when qlateral requires grad."""
-
-    @staticmethod
-    def forward(ctx, plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt):
-        dev = plan.device
-        g32, g64 = gauges
-        B, T, G = int(q0.shape[0]), int(rows), int(g32.shape[0])
-        _set_coeffs(plan, c1, c2, c3, c4dt if qlateral is not None else None, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        q = q0.detach().clone(memory_format=torch.contiguous_format)
-        scratch = torch.empty((T, plan.n), dtype=torch.float64, device=q0.device)
-        discharge = torch.empty((B, T, G), dtype=torch.float64, device=q0.device)
-        ql = None if qlateral is None else qlateral.detach()
-        for m in range(B):
-            if ql is not None:
-                plan.rapid_route_dev(q[m], ql[m], T, scratch, T, T, nsub, stream)
-            else:
-                plan.muskingum_route_dev(q[m], scratch, T, T, nsub, stream)
-            torch.index_select(scratch, 1, g64, out=discharge[m])
-        ctx.plan, ctx.nsub, ctx.rows, ctx.per_sweep, ctx.g32 = plan, int(nsub), T, per_sweep, g32
-        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach(), None if c4dt is None else c4dt.detach())
-        ctx.save_for_backward(q0, qlateral, discharge)
-        ctx.set_materialize_grads(False)
-        return discharge, q
-
-    @staticmethod
-    def backward(ctx, grad_discharge, grad_qfinal):
-        plan, nsub, T, g32 = ctx.plan, ctx.nsub, ctx.rows, ctx.g32
-        q0, qlateral, discharge = ctx.saved_tensors
-        need = ctx.needs_input_grad      # plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt
-        want_q0, want_ql = need[5], need[6] and qlateral is not None
-        want_coef = any(need[7:10]) or (need[10] and qlateral is not None)
-        if (grad_discharge is None and grad_qfinal is None) or not (want_q0 or want_ql or want_coef):
-            return (None,) * 11
-        B, n, G = int(q0.shape[0]), plan.n, int(g32.shape[0])
-        _set_coeffs(plan, *ctx.coeffs[:3], ctx.coeffs[3] if qlateral is not None else None, plan.device)
-        stream = torch.cuda.current_stream(plan.device).cuda_stream
-        f64 = dict(dtype=torch.float64, device=discharge.device)
-        g_out = None if grad_discharge is None else grad_discharge.to(**f64).contiguous()
-        g_fin = None if grad_qfinal is None else grad_qfinal.to(**f64).contiguous()
-        g_q0 = torch.empty((B, n), **f64) if want_q0 else None
-        g_ql = torch.empty((B, T, n), **f64) if want_ql else None
-        ql = None if qlateral is None else qlateral.detach()
-        q0_pitch = int(q0.stride(0)) if B > 1 else n
-        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
-        nbytes = max(plan.rapid_adjoint_gauges_work_bytes(g, G, T, nsub, want_ql) for g in {group, B % group or group})
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
-        g_coef = None
-
-        def members(t, m0, m1):
-            return None if t is None else t[m0:m1]
-
-        for m0 in range(0, B, group):
-            m1 = min(B, m0 + group)
-            part = torch.empty((4, n), **f64) if want_coef else None
-            plan.rapid_adjoint_gauges_dev(m1 - m0, G, g32, q0.data_ptr() + 8 * m0 * q0_pitch, q0_pitch, members(ql, m0, m1), T, T * n,
-                                          None if g_out is None else discharge[m0:m1], members(g_out, m0, m1), T * G, members(g_fin, m0, m1),
-                                          members(g_ql, m0, m1), members(g_q0, m0, m1), part, work, nbytes, T, nsub, stream)
-            if want_coef:
-                g_coef = part if g_coef is None else g_coef + part
-        coef = [g_coef[j].to(c.device) if want_coef and need[7 + j] and c is not None else None for j, c in enumerate(ctx.coeffs)]
-        return (None, None, None, None, None, g_q0, g_ql, *coef)
-
-
 def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, gauges=None):
     """Differentiable RapidMuskingum routing: (discharge[T, n], q_final[n]) as torch tensors on the plan's device.
 
@@ -353,7 +309,7 @@ def rapid_route(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window
     c4dt = (c1 + c2) / float(dt_runoff)
     if gauges is not None:      # the one-member case of the batched gauge call
         on_device = _upload_gauges(plan, gauges, host_gauges)
-        d, q = _in_windows(T, rows_per_window, (q0.unsqueeze(0),), lambda t0, t1, q: RapidRouteGauges.apply(
+        d, q = _in_windows(T, rows_per_window, (q0.unsqueeze(0),), lambda t0, t1, q: RapidRouteBatch.apply(
             plan, nsub, t1 - t0, None, on_device, q, None if qlateral is None else qlateral[t0:t1].unsqueeze(0), c1, c2, c3, c4dt), axis=1)
         return d[0], q[0]
     return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRoute.apply(
@@ -400,23 +356,33 @@ class RapidRouteBatch(torch.autograd.Function):
     """(discharge[B, T, n], q_final[B, n]) = RapidRoute for B series at once: q0[B, n] (rows of n adjacent values, any pitch: an
     expanded (n,) q0 has pitch 0), qlateral[B, T, n] or None, one set of coefficients.  Forward: RapidRoute's call, member by member,
     so every member's values are RapidRoute's bits.  Backward: rr_rapid_adjoint_batch_dev on groups of `per_sweep` members (None: all) in
-    ascending order, the groups' coefficient gradients added in that order."""
+    ascending order, the groups' coefficient gradients added in that order.
+
+    With `gauges` (None, or a pair of device tensors, int32 and int64, of G distinct params-order indices) the discharge is
+    (B, T, G), at those reaches only: the forward routes every member into one (T, n) scratch tensor that is not kept and gathers the
+    gauge columns out of it, so only q0, qlateral and the (B, T, G) gauge discharge are kept; the backward is
+    rr_rapid_adjoint_gauges_dev, whose work memory has gradient rows only when qlateral requires grad."""
 
     @staticmethod
-    def forward(ctx, plan, nsub, rows, per_sweep, q0, qlateral, c1, c2, c3, c4dt):
+    def forward(ctx, plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt):
         dev = plan.device
+        g32, g64 = (None, None) if gauges is None else gauges
         B, T = int(q0.shape[0]), int(rows)
         _set_coeffs(plan, c1, c2, c3, c4dt if qlateral is not None else None, dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         q = q0.detach().clone(memory_format=torch.contiguous_format)
-        discharge = torch.empty((B, T, plan.n), dtype=torch.float64, device=q0.device)
+        scratch = None if gauges is None else torch.empty((T, plan.n), dtype=torch.float64, device=q0.device)
+        discharge = torch.empty((B, T, plan.n if gauges is None else int(g32.shape[0])), dtype=torch.float64, device=q0.device)
         ql = None if qlateral is None else qlateral.detach()
         for m in range(B):
+            routed = discharge[m] if gauges is None else scratch
             if ql is not None:
-                plan.rapid_route_dev(q[m], ql[m], T, discharge[m], T, T, nsub, stream)
+                plan.rapid_route_dev(q[m], ql[m], T, routed, T, T, nsub, stream)
             else:
-                plan.muskingum_route_dev(q[m], discharge[m], T, T, nsub, stream)
-        ctx.plan, ctx.nsub, ctx.rows, ctx.per_sweep = plan, int(nsub), T, per_sweep
+                plan.muskingum_route_dev(q[m], routed, T, T, nsub, stream)
+            if gauges is not None:
+                torch.index_select(scratch, 1, g64, out=discharge[m])
+        ctx.plan, ctx.nsub, ctx.rows, ctx.per_sweep, ctx.g32 = plan, int(nsub), T, per_sweep, g32
         ctx.coeffs = (c1.detach(), c2.detach(), c3.detach(), None if c4dt is None else c4dt.detach())
         ctx.save_for_backward(q0, qlateral, discharge)
         ctx.set_materialize_grads(False)
@@ -424,41 +390,34 @@ class RapidRouteBatch(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, grad_discharge, grad_qfinal):
-        plan, nsub, T = ctx.plan, ctx.nsub, ctx.rows
+        plan, nsub, T, g32 = ctx.plan, ctx.nsub, ctx.rows, ctx.g32
         q0, qlateral, discharge = ctx.saved_tensors
-        need = ctx.needs_input_grad      # plan, nsub, rows, per_sweep, q0, qlateral, c1, c2, c3, c4dt
-        want_q0, want_ql = need[4], need[5] and qlateral is not None
-        want_coef = any(need[6:9]) or (need[9] and qlateral is not None)
+        need = ctx.needs_input_grad      # plan, nsub, rows, per_sweep, gauges, q0, qlateral, c1, c2, c3, c4dt
+        want_q0, want_ql = need[5], need[6] and qlateral is not None
+        want_coef = any(need[7:10]) or (need[10] and qlateral is not None)
         if (grad_discharge is None and grad_qfinal is None) or not (want_q0 or want_ql or want_coef):
-            return (None,) * 10
-        B, n = int(q0.shape[0]), plan.n
-        _set_coeffs(plan, *ctx.coeffs[:3], ctx.coeffs[3] if qlateral is not None else None, plan.device)
-        stream = torch.cuda.current_stream(plan.device).cuda_stream
-        f64 = dict(dtype=torch.float64, device=discharge.device)
-        g_out = None if grad_discharge is None else grad_discharge.to(**f64).contiguous()
-        g_fin = None if grad_qfinal is None else grad_qfinal.to(**f64).contiguous()
-        g_q0 = torch.empty((B, n), **f64) if want_q0 else None
-        g_ql = torch.empty((B, T, n), **f64) if want_ql else None
+            return (None,) * 11
+        B, n, G = int(q0.shape[0]), plan.n, int(discharge.shape[2])
         ql = None if qlateral is None else qlateral.detach()
         q0_pitch = int(q0.stride(0)) if B > 1 else n
-        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
-        nbytes = max(plan.rapid_adjoint_batch_work_bytes(g, T, nsub) for g in {group, B % group or group})
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
-        g_coef = None
 
-        def members(t, m0, m1):
-            return None if t is None else t[m0:m1]
+        def work_bytes(members):
+            if g32 is None:
+                return plan.rapid_adjoint_batch_work_bytes(members, T, nsub)
+            return plan.rapid_adjoint_gauges_work_bytes(members, G, T, nsub, want_ql)
 
-        for m0 in range(0, B, group):
-            m1 = min(B, m0 + group)
-            part = torch.empty((4, n), **f64) if want_coef else None
-            plan.rapid_adjoint_batch_dev(m1 - m0, q0.data_ptr() + 8 * m0 * q0_pitch, q0_pitch, members(ql, m0, m1), T, T * n,
-                                         discharge[m0:m1], members(g_out, m0, m1), T * n, members(g_fin, m0, m1), members(g_ql, m0, m1),
-                                         members(g_q0, m0, m1), part, work, nbytes, T, nsub, stream)
-            if want_coef:
-                g_coef = part if g_coef is None else g_coef + part
-        coef = [g_coef[j].to(c.device) if want_coef and need[6 + j] and c is not None else None for j, c in enumerate(ctx.coeffs)]
-        return (None, None, None, None, g_q0, g_ql, *coef)
+        def adjoint(m0, m1, g_out, g_fin, g_q0, g_ql, g_coef, work, nbytes, stream):
+            inputs = (q0.data_ptr() + 8 * m0 * q0_pitch, q0_pitch, None if ql is None else ql[m0:m1], T, T * n)
+            rest = (g_fin, g_ql, g_q0, g_coef, work, nbytes, T, nsub, stream)
+            if g32 is None:
+                plan.rapid_adjoint_batch_dev(m1 - m0, *inputs, discharge[m0:m1], g_out, T * n, *rest)
+            else:      # the gauge discharge goes with its cotangent only: the engine refuses one without the other
+                plan.rapid_adjoint_gauges_dev(m1 - m0, G, g32, *inputs, None if g_out is None else discharge[m0:m1], g_out, T * G, *rest)
+
+        return (None, None, None, None, None, *_members_backward(
+            plan, ctx.coeffs, ctx.coeffs[3] if qlateral is not None else None, discharge.device, B, ctx.per_sweep,
+            (grad_discharge, grad_qfinal), ((n,) if want_q0 else None, (T, n) if want_ql else None), want_coef,
+            [need[7 + j] and c is not None for j, c in enumerate(ctx.coeffs)], work_bytes, adjoint))
 
 
 def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_window=None, rows=None, members_per_sweep=None, gauges=None):
@@ -496,14 +455,10 @@ def rapid_route_batch(plan, q0, qlateral, k, x, dt_routing, dt_runoff, rows_per_
     if q0.ndim == 1:
         q0 = q0.unsqueeze(0).expand(B, n)      # autograd sums the members' rows into the one q0
     whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
-    if gauges is not None:
-        on_device = _upload_gauges(plan, gauges, host_gauges)
-        return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRouteGauges.apply(
-            plan, nsub, t1 - t0, members_per_sweep, on_device, q,
-            None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(), c1, c2, c3, c4dt), axis=1)
+    on_device = None if gauges is None else _upload_gauges(plan, gauges, host_gauges)
     return _in_windows(T, rows_per_window, (q0,), lambda t0, t1, q: RapidRouteBatch.apply(
-        plan, nsub, t1 - t0, members_per_sweep, q, None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(),
-        c1, c2, c3, c4dt), axis=1)
+        plan, nsub, t1 - t0, members_per_sweep, on_device, q,
+        None if qlateral is None else qlateral if whole else qlateral[:, t0:t1].contiguous(), c1, c2, c3, c4dt), axis=1)
 
 
 # ---- UnitMuskingum ----
@@ -605,9 +560,11 @@ def uh_convolve(kernel, state, depth):
     return UhConvolve.apply(kernel, state, depth)
 
 
-def _unit_gauges_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3):
-    """UnitRouteGauges for one series: the one-member case of the batched gauge call."""
-    d, q_ch, q_full = UnitRouteGauges.apply(plan, nsub, None, on_device, q_ch.unsqueeze(0), q_full.unsqueeze(0), lateral.unsqueeze(0), c1, c2, c3)
+def _unit_route_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3):
+    """One series through UnitRoute or, with gauges on the device, through the one-member case of the batched gauge call."""
+    if on_device is None:
+        return UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3)
+    d, q_ch, q_full = UnitRouteBatch.apply(plan, nsub, None, on_device, q_ch.unsqueeze(0), q_full.unsqueeze(0), lateral.unsqueeze(0), c1, c2, c3)
     return d[0], q_ch[0], q_full[0]
 
 
@@ -631,12 +588,9 @@ def unit_route(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff, rows_
     T = _check_rows(lateral, 'lateral', plan.n)
     _check_device(plan, ((q_ch0, 'q_ch0'), (q_full0, 'q_full0'), (lateral, 'lateral')))
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
-    if gauges is not None:
-        on_device = _upload_gauges(plan, gauges, host_gauges)
-        return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: _unit_gauges_one(
-            plan, nsub, on_device, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
-    return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: UnitRoute.apply(
-        plan, nsub, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
+    on_device = None if gauges is None else _upload_gauges(plan, gauges, host_gauges)
+    return _in_windows(T, rows_per_window, (q_ch0, q_full0), lambda t0, t1, q_ch, q_full: _unit_route_one(
+        plan, nsub, on_device, q_ch, q_full, lateral[t0:t1], c1, c2, c3))
 
 
 def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None, gauges=None):
@@ -661,9 +615,7 @@ def unit_muskingum(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_ro
 
     def route(t0, t1, q_ch, q_full, state):
         lateral, state = UhConvolve.apply(uh_kernel, state, depth[t0:t1])
-        if on_device is not None:
-            return (*_unit_gauges_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
-        return (*UnitRoute.apply(plan, nsub, q_ch, q_full, lateral, c1, c2, c3), state)
+        return (*_unit_route_one(plan, nsub, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (q_ch0, q_full0, uh_state), route)
 
@@ -727,94 +679,29 @@ class UnitRouteBatch(torch.autograd.Function):
     """(discharge[B, T, n], q_ch[B, n_inner], q_full[B, n_inner]) = UnitRoute for B series at once: q_ch0, q_full0[B, n_inner] (rows of
     n_inner adjacent values, any pitch: an expanded (n_inner,) state has pitch 0), lateral[B, T, n], one set of coefficients.  Forward:
     UnitRoute's call, member by member, so every member's values are UnitRoute's bits.  Backward: rr_unit_adjoint_batch_dev on groups of
-    `per_sweep` members (None: all) in ascending order, the groups' coefficient gradients added in that order."""
+    `per_sweep` members (None: all) in ascending order, the groups' coefficient gradients added in that order.
+
+    With `gauges` (None, or a pair of device tensors, int32 and int64, of G distinct params-order indices) the discharge is
+    (B, T, G), at those reaches only: the forward routes every member into one (T, n) scratch tensor that is not kept and gathers the
+    gauge columns out of it, so only q_ch0, q_full0, lateral and the (B, T, G) gauge discharge are kept; the backward is
+    rr_unit_adjoint_gauges_dev, whose work memory has gradient rows only when lateral requires grad."""
 
     @staticmethod
-    def forward(ctx, plan, nsub, per_sweep, q_ch0, q_full0, lateral, c1, c2, c3):
+    def forward(ctx, plan, nsub, per_sweep, gauges, q_ch0, q_full0, lateral, c1, c2, c3):
         dev = plan.device
+        g32, g64 = (None, None) if gauges is None else gauges
         B, T = int(lateral.shape[0]), int(lateral.shape[1])
         _set_coeffs(plan, c1, c2, c3, None, dev)
         stream = torch.cuda.current_stream(dev).cuda_stream
         q_ch = q_ch0.detach().clone(memory_format=torch.contiguous_format)
         q_full = q_full0.detach().clone(memory_format=torch.contiguous_format)
-        discharge = torch.empty((B, T, plan.n), dtype=torch.float64, device=lateral.device)
+        scratch = None if gauges is None else torch.empty((T, plan.n), dtype=torch.float64, device=lateral.device)
+        discharge = torch.empty((B, T, plan.n if gauges is None else int(g32.shape[0])), dtype=torch.float64, device=lateral.device)
         lat = lateral.detach()
         for m in range(B):
-            plan.unit_route_dev(q_ch[m], q_full[m], lat[m], T, discharge[m], T, T, nsub, stream)
-        ctx.plan, ctx.nsub, ctx.per_sweep = plan, int(nsub), per_sweep
-        ctx.coeffs = (c1.detach(), c2.detach(), c3.detach())
-        ctx.save_for_backward(q_ch0, q_full0, lateral, discharge)
-        ctx.set_materialize_grads(False)
-        return discharge, q_ch, q_full
-
-    @staticmethod
-    def backward(ctx, grad_discharge, grad_qch, grad_qfull):
-        plan, nsub = ctx.plan, ctx.nsub
-        q_ch0, q_full0, lateral, discharge = ctx.saved_tensors
-        need = ctx.needs_input_grad      # plan, nsub, per_sweep, q_ch0, q_full0, lateral, c1, c2, c3
-        want_coef = any(need[6:9])
-        if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[3:6]) or want_coef):
-            return (None,) * 9
-        B, T, n, ni = int(lateral.shape[0]), int(lateral.shape[1]), plan.n, plan.n_inner
-        _set_coeffs(plan, *ctx.coeffs, None, plan.device)
-        stream = torch.cuda.current_stream(plan.device).cuda_stream
-        f64 = dict(dtype=torch.float64, device=discharge.device)
-        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
-        g_qch0 = torch.empty((B, ni), **f64) if need[3] else None
-        g_qfull0 = torch.empty((B, ni), **f64) if need[4] else None
-        g_lat = torch.empty((B, T, n), **f64) if need[5] else None
-        lat = lateral.detach()
-        # one pitch serves both states: one of them shared and the other not, or no inner reach at all, and they go as dense rows
-        qc, qf = q_ch0.detach(), q_full0.detach()
-        if ni == 0 or B == 1 or qc.stride(0) != qf.stride(0):
-            qc, qf = qc.contiguous(), qf.contiguous()
-        pitch = int(qc.stride(0)) if B > 1 and ni > 0 else ni
-        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
-        nbytes = max(plan.unit_adjoint_batch_work_bytes(g, T, nsub) for g in {group, B % group or group})
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
-        g_coef = None
-
-        def members(t, m0, m1):
-            return None if t is None else t[m0:m1]
-
-        def state(t, m0):
-            return t.data_ptr() + 8 * m0 * pitch if ni > 0 else None
-
-        for m0 in range(0, B, group):
-            m1 = min(B, m0 + group)
-            part = torch.empty((3, n), **f64) if want_coef else None
-            plan.unit_adjoint_batch_dev(m1 - m0, state(qc, m0), state(qf, m0), pitch, lat[m0:m1], T, T * n, discharge[m0:m1],
-                                        members(g_out, m0, m1), T * n, members(g_c, m0, m1), members(g_f, m0, m1), members(g_lat, m0, m1),
-                                        members(g_qch0, m0, m1), members(g_qfull0, m0, m1), part, work, nbytes, T, nsub, stream)
-            if want_coef:
-                g_coef = part if g_coef is None else g_coef + part
-        coef = [g_coef[j].to(c.device) if want_coef and need[6 + j] else None for j, c in enumerate(ctx.coeffs)]
-        return (None, None, None, g_qch0, g_qfull0, g_lat, *coef)
-
-
-class UnitRouteGauges(torch.autograd.Function):
-    """(discharge[B, T, G], q_ch[B, n_inner], q_full[B, n_inner]) = UnitRouteBatch with the discharge at the reaches `gauges` only (a
-    pair of device tensors, int32 and int64, of G distinct params-order indices).  Forward: UnitRoute's call, member by member, into one
-    (T, n) scratch tensor that is not kept, the gauge columns gathered out of it; every value is UnitRoute's.  Only q_ch0, q_full0,
-    lateral and the (B, T, G) gauge discharge are kept.  Backward: rr_unit_adjoint_gauges_dev on groups of `per_sweep` members (None:
-    all) in ascending order, the groups' coefficient gradients added in that order; its work memory has gradient rows only when lateral
-    requires grad."""
-
-    @staticmethod
-    def forward(ctx, plan, nsub, per_sweep, gauges, q_ch0, q_full0, lateral, c1, c2, c3):
-        dev = plan.device
-        g32, g64 = gauges
-        B, T, G = int(lateral.shape[0]), int(lateral.shape[1]), int(g32.shape[0])
-        _set_coeffs(plan, c1, c2, c3, None, dev)
-        stream = torch.cuda.current_stream(dev).cuda_stream
-        q_ch = q_ch0.detach().clone(memory_format=torch.contiguous_format)
-        q_full = q_full0.detach().clone(memory_format=torch.contiguous_format)
-        scratch = torch.empty((T, plan.n), dtype=torch.float64, device=lateral.device)
-        discharge = torch.empty((B, T, G), dtype=torch.float64, device=lateral.device)
-        lat = lateral.detach()
-        for m in range(B):
-            plan.unit_route_dev(q_ch[m], q_full[m], lat[m], T, scratch, T, T, nsub, stream)
-            torch.index_select(scratch, 1, g64, out=discharge[m])
+            plan.unit_route_dev(q_ch[m], q_full[m], lat[m], T, discharge[m] if gauges is None else scratch, T, T, nsub, stream)
+            if gauges is not None:
+                torch.index_select(scratch, 1, g64, out=discharge[m])
         ctx.plan, ctx.nsub, ctx.per_sweep, ctx.g32 = plan, int(nsub), per_sweep, g32
         ctx.coeffs = (c1.detach(), c2.detach(), c3.detach())
         ctx.save_for_backward(q_ch0, q_full0, lateral, discharge)
@@ -829,42 +716,34 @@ class UnitRouteGauges(torch.autograd.Function):
         want_coef, want_lat = any(need[7:10]), need[6]
         if (grad_discharge is None and grad_qch is None and grad_qfull is None) or not (any(need[4:7]) or want_coef):
             return (None,) * 10
-        B, T, n, ni, G = int(lateral.shape[0]), int(lateral.shape[1]), plan.n, plan.n_inner, int(g32.shape[0])
-        _set_coeffs(plan, *ctx.coeffs, None, plan.device)
-        stream = torch.cuda.current_stream(plan.device).cuda_stream
-        f64 = dict(dtype=torch.float64, device=discharge.device)
-        g_out, g_c, g_f = (None if g is None else g.to(**f64).contiguous() for g in (grad_discharge, grad_qch, grad_qfull))
-        g_qch0 = torch.empty((B, ni), **f64) if need[4] else None
-        g_qfull0 = torch.empty((B, ni), **f64) if need[5] else None
-        g_lat = torch.empty((B, T, n), **f64) if want_lat else None
+        B, T, n, ni, G = int(lateral.shape[0]), int(lateral.shape[1]), plan.n, plan.n_inner, int(discharge.shape[2])
         lat = lateral.detach()
         # one pitch serves both states: one of them shared and the other not, or no inner reach at all, and they go as dense rows
         qc, qf = q_ch0.detach(), q_full0.detach()
         if ni == 0 or B == 1 or qc.stride(0) != qf.stride(0):
             qc, qf = qc.contiguous(), qf.contiguous()
         pitch = int(qc.stride(0)) if B > 1 and ni > 0 else ni
-        group = min(B, kMaxMembers, B if ctx.per_sweep is None else int(ctx.per_sweep))
-        nbytes = max(plan.unit_adjoint_gauges_work_bytes(g, G, T, nsub, want_lat) for g in {group, B % group or group})
-        work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=discharge.device)      # torch's allocator owns the tapes
-        g_coef = None
-
-        def members(t, m0, m1):
-            return None if t is None else t[m0:m1]
 
         def state(t, m0):
             return t.data_ptr() + 8 * m0 * pitch if ni > 0 else None
 
-        for m0 in range(0, B, group):
-            m1 = min(B, m0 + group)
-            part = torch.empty((3, n), **f64) if want_coef else None
-            plan.unit_adjoint_gauges_dev(m1 - m0, G, g32, state(qc, m0), state(qf, m0), pitch, lat[m0:m1], T, T * n,
-                                         None if g_out is None else discharge[m0:m1], members(g_out, m0, m1), T * G, members(g_c, m0, m1),
-                                         members(g_f, m0, m1), members(g_lat, m0, m1), members(g_qch0, m0, m1), members(g_qfull0, m0, m1),
-                                         part, work, nbytes, T, nsub, stream)
-            if want_coef:
-                g_coef = part if g_coef is None else g_coef + part
-        coef = [g_coef[j].to(c.device) if want_coef and need[7 + j] else None for j, c in enumerate(ctx.coeffs)]
-        return (None, None, None, None, g_qch0, g_qfull0, g_lat, *coef)
+        def work_bytes(members):
+            if g32 is None:
+                return plan.unit_adjoint_batch_work_bytes(members, T, nsub)
+            return plan.unit_adjoint_gauges_work_bytes(members, G, T, nsub, want_lat)
+
+        def adjoint(m0, m1, g_out, g_c, g_f, g_qch0, g_qfull0, g_lat, g_coef, work, nbytes, stream):
+            inputs = (state(qc, m0), state(qf, m0), pitch, lat[m0:m1], T, T * n)
+            rest = (g_c, g_f, g_lat, g_qch0, g_qfull0, g_coef, work, nbytes, T, nsub, stream)
+            if g32 is None:
+                plan.unit_adjoint_batch_dev(m1 - m0, *inputs, discharge[m0:m1], g_out, T * n, *rest)
+            else:      # the gauge discharge goes with its cotangent only: the engine refuses one without the other
+                plan.unit_adjoint_gauges_dev(m1 - m0, G, g32, *inputs, None if g_out is None else discharge[m0:m1], g_out, T * G, *rest)
+
+        return (None, None, None, None, *_members_backward(
+            plan, ctx.coeffs, None, discharge.device, B, ctx.per_sweep, (grad_discharge, grad_qch, grad_qfull),
+            ((ni,) if need[4] else None, (ni,) if need[5] else None, (T, n) if want_lat else None), want_coef, need[7:10],
+            work_bytes, adjoint))
 
 
 def _check_unit_batch(plan, q_ch0, q_full0, rows, rows_name, single, k, x, dt_routing, dt_runoff, rows_per_window, members_per_sweep):
@@ -921,15 +800,11 @@ def unit_route_batch(plan, q_ch0, q_full0, lateral, k, x, dt_routing, dt_runoff,
     c1, c2, c3 = muskingum_coefficients(k, x, float(dt_routing))
     ni = plan.n_inner
     whole = rows_per_window is None or int(rows_per_window) >= T      # a window of the rows: its own contiguous copy
-    if gauges is not None:
-        on_device = _upload_gauges(plan, gauges, host_gauges)
-        return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,))),
-                           lambda t0, t1, q_ch, q_full: UnitRouteGauges.apply(
-                               plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(),
-                               c1, c2, c3), axis=1)
+    on_device = None if gauges is None else _upload_gauges(plan, gauges, host_gauges)
     return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,))),
                        lambda t0, t1, q_ch, q_full: UnitRouteBatch.apply(
-                           plan, nsub, members_per_sweep, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(), c1, c2, c3), axis=1)
+                           plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral if whole else lateral[:, t0:t1].contiguous(),
+                           c1, c2, c3), axis=1)
 
 
 def unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x, dt_routing, dt_runoff, rows_per_window=None,
@@ -954,9 +829,7 @@ def unit_muskingum_batch(plan, q_ch0, q_full0, depth, uh_kernel, uh_state, k, x,
 
     def route(t0, t1, q_ch, q_full, state):      # a member's rows of a window are adjacent: the convolution reads them in place
         lateral, state = UhConvolveBatch.apply(uh_kernel, state, depth[:, t0:t1])
-        if on_device is not None:
-            return (*UnitRouteGauges.apply(plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
-        return (*UnitRouteBatch.apply(plan, nsub, members_per_sweep, q_ch, q_full, lateral, c1, c2, c3), state)
+        return (*UnitRouteBatch.apply(plan, nsub, members_per_sweep, on_device, q_ch, q_full, lateral, c1, c2, c3), state)
 
     return _in_windows(T, rows_per_window, (_per_member(q_ch0, B, (ni,)), _per_member(q_full0, B, (ni,)), _per_member(uh_state, B, (n_ks, n))),
                        route, axis=1)
