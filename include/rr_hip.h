@@ -302,7 +302,9 @@ int rr_unit_route_uh_f32in_dev(rr_plan *plan, double *q_ch, double *q_full, doub
  * of it is ignored.  UnitMuskingum distinguishes headwater tributaries from the others (_numba_kernels.py:150-156): a ghost
  * that mirrors a reach WITH upstream reaches must itself have one in the local network (a dummy headwater whose lateral
  * column is zero does), so that it falls on the same side of that distinction as the reach it mirrors, and it then has an
- * entry in the q_ch / q_full arrays, whose q_full is the mirrored reach's. */
+ * entry in the q_ch / q_full arrays, whose q_full is the mirrored reach's.
+ * A call that fails after its arguments were accepted (RR_E_ALLOC, RR_E_HIP) leaves the plan between two boundaries: every route call
+ * returns RR_E_STATE until rr_plan_set_boundary has been repeated and has succeeded; the plan can be destroyed as it is. */
 int rr_plan_set_boundary(rr_plan *plan, int64_t n_ghost, const int64_t *ghost_reaches, int64_t n_export,
                          const int64_t *export_reaches);
 
@@ -643,6 +645,10 @@ int rr_runoff_adjoint_dev(int device, int64_t n_rivers, int64_t n_points, int64_
 /* ---- small device helpers so a host language needs no HIP binding of its own ---- */
 int rr_dev_malloc(int device, int64_t bytes, void **out);
 int rr_dev_free(int device, void *ptr);
+/* The engine's device allocations, process-wide: out[0] = alive now, out[1] = made since the process started (a plan's arrays, the
+ * work memory of the host-pointer entry points and what rr_dev_malloc handed out alike).  For tests: a plan that is destroyed, and a
+ * call that fails half-way, leave out[0] where it was (RR_ALLOC_FAIL_AT, read by rr_plan_create, makes the k-th allocation fail). */
+int rr_dev_alloc_stats(int64_t out[2]);
 int rr_dev_upload(int device, void *dst_dev, const void *src_host, int64_t bytes);
 int rr_dev_download(int device, void *dst_host, const void *src_dev, int64_t bytes);
 int rr_dev_synchronize(int device);

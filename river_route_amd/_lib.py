@@ -163,6 +163,7 @@ _SIGNATURES = {
                                         _vp, _vp, _i64, _vp]),
     'rr_dev_malloc': (C.c_int, [C.c_int, _i64, C.POINTER(_vp)]),
     'rr_dev_free': (C.c_int, [C.c_int, _vp]),
+    'rr_dev_alloc_stats': (C.c_int, [_vp]),
     'rr_dev_upload': (C.c_int, [C.c_int, _vp, _vp, _i64]),
     'rr_dev_download': (C.c_int, [C.c_int, _vp, _vp, _i64]),
     'rr_dev_synchronize': (C.c_int, [C.c_int]),

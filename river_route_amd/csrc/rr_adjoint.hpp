@@ -74,11 +74,9 @@ int adjoint_ready(rr_plan *P)
         std::vector<int32_t> down(H.n, -1);
         for (int64_t p = 0; p < H.n; ++p)
             for (int32_t u = H.child_ptr[p]; u < H.child_ptr[p + 1]; ++u) down[u] = (int32_t)p;
-        int32_t *d = nullptr;
-        int rc = dev_alloc(&d, H.n);
-        if (!rc) rc = dev_upload(d, down);
-        if (rc) { if (d) (void)hipFree(d); return rc; }
-        P->d_adj_down = d;
+        DevBuf<int32_t> d;
+        if (int rc = assign(d, down)) return rc;
+        P->d_adj_down = std::move(d);
     }
     return RR_OK;
 }

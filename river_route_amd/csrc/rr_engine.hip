@@ -51,16 +51,7 @@ int rr_device_count(void)
 void rr_plan_destroy(rr_plan *P)
 {
     if (!P) return;
-    if (P->device >= 0 && hipSetDevice(P->device) == hipSuccess) {
-        void *ptrs[] = {P->d_child_ptr, P->d_lag, P->d_perm, P->d_inv, P->d_inner_pos, P->d_bidx, P->d_hwc, P->d_w, P->d_c1row_h, P->d_c2,
-                        P->d_coef, P->d_coef_unit, P->d_sq, P->d_ss, P->d_si, P->d_sqch, P->d_full, P->d_chan,
-                        P->d_tmeta, P->d_pmeta,
-                        P->d_tperm, P->d_tinv, P->d_inner_idx, P->d_colmeta, P->d_ghostmeta, P->d_c4_params,
-                        P->d_c3, P->d_c4, P->d_x, P->d_isum, P->d_qch, P->d_a2, P->d_c1own, P->d_z, P->d_ring, P->d_stage, P->d_mrows,
-                        P->d_slot_a[0], P->d_slot_a[1], P->d_slot_b[0], P->d_slot_b[1], P->d_m_index[0], P->d_m_index[1],
-                        P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef, P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch,
-                        P->d_kholemeta, P->d_kghostmeta, P->d_esq, P->d_ess, P->d_esi, P->d_adj_down, P->d_pmeta_hw, P->d_coef_hw, P->d_hwcoef, P->d_hwq};
-        for (void *p : ptrs) if (p) (void)hipFree(p);
+    if (P->device >= 0 && hipSetDevice(P->device) == hipSuccess) {      // (the device arrays go with the plan: they are DevBufs)
         P->pipe.destroy();
         for (hipEvent_t e : P->ev) (void)hipEventDestroy(e);
         for (hipEvent_t e : P->aux_ev) (void)hipEventDestroy(e);
@@ -81,8 +72,10 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
     // RR_TILE_LEAN=0 the general tick; RR_UH_PAIRS=0 one record batch per fused-convolution launch; RR_REC_BATCHES=N N record batches
     // per launch of k_rec_in / k_rec_out in every call (1: one, as before multi-batch launches); RR_DIRECT=0 records also where the
     // params order would allow the direct row path; RR_HW_INPASS=0 headwaters routed and stored by k_tile, as every other reach; RR_VERBOSE=1
-    // logs the schedule.
+    // logs the schedule; RR_ALLOC_FAIL_AT=k the k-th device allocation the process makes from here on, whoever makes it, is refused once
+    // (as the device refuses one: RR_E_ALLOC, NULL; the message says "(injected)").
     if (const char *e = getenv("RR_HW_INPASS")) P->hw_inpass = atoi(e) != 0;
+    if (const char *e = getenv("RR_ALLOC_FAIL_AT")) rr::g_dev_fail_in = std::max(0, atoi(e));
     if (const char *e = getenv("RR_WAVE")) { P->wave_enabled = atoi(e) != 0; P->wave_forced = atoi(e) == 1; }
     if (const char *e = getenv("RR_REC_BATCHES")) { P->rec_batches = std::max(1, std::min(kRecMaxLaunchBatches, atoi(e))); P->rec_batches_forced = true; }
     if (const char *e = getenv("RR_WAVE_K")) P->wave_K = std::max(kRec, atoi(e) / kRec * kRec);
@@ -139,49 +132,35 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
         (void)hipGetLastError();
         const rr::HostPlan &H = P->h;
         const int64_t ni = (int64_t)H.inner_pos.size();
-        rc = dev_alloc(&P->d_child_ptr, n + 1);
-        if (!rc) rc = dev_alloc(&P->d_lag, n);
-        if (!rc) rc = dev_alloc(&P->d_perm, n);
-        if (!rc) rc = dev_alloc(&P->d_inv, n);
-        if (!rc) rc = dev_alloc(&P->d_inner_pos, ni);
-        if (!rc) rc = dev_alloc(&P->d_hwc, n);
-        if (!rc) rc = dev_alloc(&P->d_bidx, n);
-        if (!rc) rc = dev_alloc(&P->d_c4_params, n);
+        rc = P->d_child_ptr.alloc(n + 1);      // (their uploads come last, as they always did: the order of a plan's allocations and uploads is kept)
+        for (DevBuf<int32_t> *col : {&P->d_lag, &P->d_perm, &P->d_inv}) if (!rc) rc = col->alloc(n);
+        if (!rc) rc = P->d_inner_pos.alloc(ni);
+        if (!rc) rc = P->d_hwc.alloc(n);
+        if (!rc) rc = P->d_bidx.alloc(n);
+        if (!rc) rc = P->d_c4_params.alloc(n);
         if (!rc && P->tp.ok) {      // tile layout of the time-tiled kernel
             const rr::TilePlan &TP = P->tp;
             const int64_t np = TP.np;
             std::vector<int32_t> inner_idx;
             inner_idx.reserve(ni);
             for (int64_t i = 0; i < n; ++i) if (H.child_ptr[H.inv[i] + 1] > H.child_ptr[H.inv[i]]) inner_idx.push_back((int32_t)i);
-            rc = dev_alloc(&P->d_inner_idx, ni);
-            if (!rc) rc = dev_upload(P->d_inner_idx, inner_idx);
+            rc = assign(P->d_inner_idx, inner_idx);
             if (!rc) rc = upload_tile_meta(P, TP.lag, TP.xpos, TP.tile_flags);      // (and the column metadata of the record passes)
             for (int32_t f : TP.tile_flags) P->n_wide_tiles += (f & kTileWide) ? 1 : 0;
-            if (!rc) rc = dev_alloc(&P->d_tperm, np);
-            if (!rc) rc = dev_upload(P->d_tperm, TP.perm);
-            if (!rc) rc = dev_alloc(&P->d_tinv, n);
-            if (!rc) rc = dev_upload(P->d_tinv, TP.inv);
-            if (!rc) rc = dev_alloc(&P->d_coef, 3 * np);
-            if (!rc) rc = dev_alloc(&P->d_coef_unit, 3 * np);
-            if (!rc) rc = dev_alloc(&P->d_coef_hw, 3 * np);
-            if (!rc) rc = dev_alloc(&P->d_hwcoef, 3 * n);
-            if (!rc) rc = dev_alloc(&P->d_hwq, n);
-            if (!rc) rc = dev_alloc(&P->d_sq, np);
-            if (!rc) rc = dev_alloc(&P->d_ss, np);
-            if (!rc) rc = dev_alloc(&P->d_si, np);
-            if (!rc) rc = dev_alloc(&P->d_sqch, np);
-            if (!rc) rc = dev_alloc(&P->d_full, n);
-            if (!rc) rc = dev_alloc(&P->d_chan, n);
+            if (!rc) rc = assign(P->d_tperm, TP.perm);
+            if (!rc) rc = assign(P->d_tinv, TP.inv);
+            for (DevBuf<double> *coef : {&P->d_coef, &P->d_coef_unit, &P->d_coef_hw}) if (!rc) rc = coef->alloc(3 * np);
+            if (!rc) rc = P->d_hwcoef.alloc(3 * n);
+            if (!rc) rc = P->d_hwq.alloc(n);
+            for (DevBuf<double> *state : {&P->d_sq, &P->d_ss, &P->d_si, &P->d_sqch}) if (!rc) rc = state->alloc(np);
+            if (!rc) rc = P->d_full.alloc(n);
+            if (!rc) rc = P->d_chan.alloc(n);
         }
         if (!rc) rc = upload_direct_plan(P);      // direct row path: per-column constants, the skeleton's tile arrays, the holes' out-pass
-        if (!rc) rc = dev_alloc(&P->d_w, n);
-        if (!rc) rc = dev_alloc(&P->d_c1row_h, n);
-        if (!rc) rc = dev_alloc(&P->d_c2, n);
-        if (!rc) rc = dev_alloc(&P->d_c3, n);
-        if (!rc) rc = dev_alloc(&P->d_c4, n);
-        if (!rc) rc = dev_alloc(&P->d_x, 3 * n);
-        if (!rc) rc = dev_alloc(&P->d_isum, n);
-        if (!rc) rc = dev_alloc(&P->d_qch, n);
+        for (DevBuf<double> *row : {&P->d_w, &P->d_c1row_h, &P->d_c2, &P->d_c3, &P->d_c4}) if (!rc) rc = row->alloc(n);
+        if (!rc) rc = P->d_x.alloc(3 * n);
+        if (!rc) rc = P->d_isum.alloc(n);
+        if (!rc) rc = P->d_qch.alloc(n);
         if (!rc) rc = dev_upload(P->d_child_ptr, H.child_ptr);
         if (!rc) rc = dev_upload(P->d_lag, H.lag);
         if (!rc) rc = dev_upload(P->d_perm, H.perm);
@@ -364,11 +343,9 @@ int rr_plan_set_unit_weights(rr_plan *P, const double *c1, const double *a_data)
         a2[p] = e >= 0 ? a_data[e] : 0.0;
         own[p] = c1[i];
     }
-    if (!P->d_a2) rc = dev_alloc(&P->d_a2, n);
-    if (!rc && !P->d_c1own) rc = dev_alloc(&P->d_c1own, n);
-    if (!rc && !P->d_z) rc = dev_alloc(&P->d_z, 3 * n);
-    if (!rc) rc = dev_upload(P->d_a2, a2);
-    if (!rc) rc = dev_upload(P->d_c1own, own);
+    rc = assign(P->d_a2, a2);
+    if (!rc) rc = assign(P->d_c1own, own);
+    if (!rc) rc = P->d_z.reserve(std::max<int64_t>(1, 3 * n));
     if (rc) return rc;
     P->unit_general = true;
     return RR_OK;
@@ -395,8 +372,8 @@ int rr_plan_reserve(rr_plan *P, int mode, int64_t T, int64_t nsub, int host_rows
         const bool piped = shape.host && sch.kernel == Kernel::Tile;
         const int64_t levels = sch.kernel == Kernel::Direct ? P->dp.skel.n_levels : (sch.kernel == Kernel::Tile ? P->tp.n_levels : 0);
         info[0] = (int)sch.kernel; info[1] = sch.kernel != Kernel::Tick ? sch.KC * kRec : 1; info[2] = sch.chunks;
-        info[3] = (P->ring_cap + P->mrows_cap + P->stage_cap) * (int64_t)sizeof(double);
-        info[4] = piped ? 2 * P->pipe.dev_cap * (int64_t)sizeof(double) : 0;
+        info[3] = (P->d_ring.count() + P->d_mrows.count() + P->d_stage.count()) * (int64_t)sizeof(double);
+        info[4] = piped ? 2 * P->pipe.dev_in.count() * (int64_t)sizeof(double) : 0;
         info[5] = piped ? 2 * HostPipe::kPinned * P->pipe.pin_cap * (int64_t)sizeof(double) : 0;
         info[6] = P->h.depth - 1 + levels * sch.KC * kRec;      // pipeline depth in ticks
         info[7] = sch.ring * (int64_t)sizeof(double);
@@ -457,18 +434,18 @@ int rr_plan_reserve_ensemble(rr_plan *P, int64_t members, int64_t T, int64_t nsu
     rc = reserve_core(P, shape, &sch);
     if (rc) return rc;
     if (P->ens_cap < members) {      // the members' carried state, np apart
-        for (double **p : {&P->d_esq, &P->d_ess, &P->d_esi}) { if (*p) (void)hipFree(*p); *p = nullptr; }
+        reset_all(P->d_esq, P->d_ess, P->d_esi);      // all three before any of the larger ones
         P->ens_cap = 0;
         const int64_t count = members * P->tp.np;
-        rc = dev_alloc(&P->d_esq, count);
-        if (!rc) rc = dev_alloc(&P->d_ess, count);
-        if (!rc) rc = dev_alloc(&P->d_esi, count);
+        rc = P->d_esq.alloc(count);
+        if (!rc) rc = P->d_ess.alloc(count);
+        if (!rc) rc = P->d_esi.alloc(count);
         if (rc) return rc;
         P->ens_cap = members;
     }
     if (info) {
         info[0] = (int)sch.kernel; info[1] = sch.KC * kRec; info[2] = sch.chunks;
-        info[3] = (P->ring_cap + P->mrows_cap + P->stage_cap) * (int64_t)sizeof(double);
+        info[3] = (P->d_ring.count() + P->d_mrows.count() + P->d_stage.count()) * (int64_t)sizeof(double);
         info[6] = P->h.depth - 1 + P->tp.n_levels * sch.KC * kRec;
         info[7] = sch.ring * (int64_t)sizeof(double);
         info[8] = cap;
@@ -555,6 +532,7 @@ int rr_plan_set_boundary(rr_plan *P, int64_t n_ghost, const int64_t *ghost_reach
         bidx[p] = (int32_t)e;
         emax = std::max<int64_t>(emax, H.lag[p]);
     }
+    P->boundary_whole = false;      // until everything below has succeeded
     if (!host_only) {
         rc = dev_upload(P->d_lag, lag);
         if (!rc) rc = dev_upload(P->d_bidx, bidx);
@@ -579,8 +557,7 @@ int rr_plan_set_boundary(rr_plan *P, int64_t n_ghost, const int64_t *ghost_reach
         if (!rc) rc = upload_direct_coef(P);
         if (rc) return rc;
     }
-    if (host_only) return RR_OK;
-    if (P->tp.ok) {      // the same flags and slots in the tile layout
+    if (!host_only && P->tp.ok) {      // the same flags and slots in the tile layout
         const rr::TilePlan &TP = P->tp;
         // flags in the tile layout; an export reach's slot in the export series travels in xpos[], the word a reach mirrored
         // by another tile's ghost uses for that ghost's position -- an export is normally an outlet of its part and has no
@@ -597,13 +574,15 @@ int rr_plan_set_boundary(rr_plan *P, int64_t n_ghost, const int64_t *ghost_reach
         for (int64_t e = 0; e < n_export; ++e) tflags[TP.tile_of[TP.inv[export_reaches[e]]]] |= kTileExports;
         rc = upload_tile_meta(P, tlag, P->export_inside ? TP.xpos : txpos, tflags);
         if (!rc) rc = upload_tile_coef(P);      // zeros at the boundary ghosts
-        if (P->d_ghostmeta) { (void)hipFree(P->d_ghostmeta); P->d_ghostmeta = nullptr; }
         std::vector<int2> gm((size_t)n_ghost);
         for (int64_t g = 0; g < n_ghost; ++g) { const int32_t p = TP.inv[ghost_reaches[g]]; gm[g] = make_int2(p, TP.lag[p] & kLagMask); }
-        if (!rc) rc = dev_alloc(&P->d_ghostmeta, n_ghost);
-        if (!rc) rc = dev_upload(P->d_ghostmeta, gm);
+        DevBuf<int2> ghostmeta;      // the plan keeps the table it has until this one is whole
+        if (!rc) rc = ghostmeta.alloc(n_ghost);
+        if (!rc) rc = dev_upload(ghostmeta, gm);
         if (rc) return rc;
+        P->d_ghostmeta = std::move(ghostmeta);
     }
+    P->boundary_whole = true;
     return RR_OK;
 }
 
@@ -940,11 +919,11 @@ int rr_uh_convolve(int device, const double *kernel, double *state, const double
     if (T < 1 || n_ks < 1 || n < 0) return fail(RR_E_INVALID, "rr_uh_convolve: need T >= 1, n_ks >= 1, n >= 0");
     if (n == 0) return RR_OK;
     if (!kernel || !state || !lateral || !out) return fail(RR_E_INVALID, "rr_uh_convolve: null array");
-    double *d_k = nullptr, *d_s = nullptr, *d_l = nullptr, *d_o = nullptr;
-    int rc = dev_alloc(&d_k, n_ks * n);
-    if (!rc) rc = dev_alloc(&d_s, n_ks * n);
-    if (!rc) rc = dev_alloc(&d_l, T * n);
-    if (!rc) rc = dev_alloc(&d_o, T * n);
+    DevBuf<double> d_k, d_s, d_l, d_o;
+    int rc = d_k.alloc(n_ks * n);
+    if (!rc) rc = d_s.alloc(n_ks * n);
+    if (!rc) rc = d_l.alloc(T * n);
+    if (!rc) rc = d_o.alloc(T * n);
     hipError_t e = hipSuccess;
     if (!rc) {
         e = hipMemcpy(d_k, kernel, (size_t)n_ks * n * sizeof(double), hipMemcpyHostToDevice);
@@ -952,13 +931,12 @@ int rr_uh_convolve(int device, const double *kernel, double *state, const double
         if (e == hipSuccess) e = hipMemcpy(d_l, lateral, (size_t)T * n * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
     }
-    if (!rc) rc = uh_convolve_core<double>(d_k, d_s, d_l, d_o, T, n_ks, n, nullptr, kSelNative);
+    if (!rc) rc = uh_convolve_core<double>(d_k.get(), d_s.get(), d_l.get(), d_o.get(), T, n_ks, n, nullptr, kSelNative);
     if (!rc) {
         e = hipMemcpy(out, d_o, (size_t)T * n * sizeof(double), hipMemcpyDeviceToHost);
         if (e == hipSuccess) e = hipMemcpy(state, d_s, (size_t)n_ks * n * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
     }
-    for (double *p : {d_k, d_s, d_l, d_o}) if (p) (void)hipFree(p);
     return rc;
 }
 
@@ -1028,32 +1006,28 @@ int rr_runoff_to_qlateral(int device, int64_t n_rivers, int64_t n_points, int64_
     const int64_t elems = stride_t == 1 && stride_p >= T ? std::max<int64_t>(1, n_points) * stride_p
                                                         : (T - 1) * stride_t + (n_points > 0 ? (n_points - 1) * stride_p : 0) + 1;
     const size_t esz = runoff_is_f32 ? sizeof(float) : sizeof(double);
-    int32_t *d_indptr = nullptr, *d_indices = nullptr;
-    double *d_w = nullptr, *d_area = nullptr, *d_out = nullptr;
-    void *d_runoff = nullptr;
-    int rc = dev_alloc(&d_indptr, n_rivers + 1);
-    if (!rc) rc = dev_alloc(&d_indices, std::max<int64_t>(1, nnz));
-    if (!rc) rc = dev_alloc(&d_w, std::max<int64_t>(1, nnz));
-    if (!rc && area) rc = dev_alloc(&d_area, n_rivers);
-    if (!rc) rc = dev_alloc(&d_out, T * n_rivers);
-    if (!rc && hipMalloc(&d_runoff, (size_t)elems * esz) != hipSuccess) rc = fail(RR_E_ALLOC, "rr_runoff_to_qlateral: device allocation failed");
-    auto release = [&]() {
-        (void)hipFree(d_indptr); (void)hipFree(d_indices); (void)hipFree(d_w); (void)hipFree(d_area); (void)hipFree(d_out); (void)hipFree(d_runoff);
-    };
-    if (rc) { release(); return rc; }
+    DevBuf<int32_t> d_indptr, d_indices;
+    DevBuf<double> d_w, d_area, d_out;
+    DevBuf<char> d_runoff;      // float32 or float64 values
+    int rc = d_indptr.alloc(n_rivers + 1);
+    if (!rc) rc = d_indices.alloc(nnz);
+    if (!rc) rc = d_w.alloc(nnz);
+    if (!rc && area) rc = d_area.alloc(n_rivers);
+    if (!rc) rc = d_out.alloc(T * n_rivers);
+    if (!rc && d_runoff.alloc(elems * (int64_t)esz) != RR_OK) rc = fail(RR_E_ALLOC, "rr_runoff_to_qlateral: device allocation failed");
+    if (rc) return rc;
     hipError_t e = hipMemcpy(d_indptr, indptr, (size_t)(n_rivers + 1) * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz > 0) e = hipMemcpy(d_indices, indices, (size_t)nnz * sizeof(int32_t), hipMemcpyHostToDevice);
     if (e == hipSuccess && nnz > 0) e = hipMemcpy(d_w, weights, (size_t)nnz * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess && area) e = hipMemcpy(d_area, area, (size_t)n_rivers * sizeof(double), hipMemcpyHostToDevice);
     if (e == hipSuccess) e = hipMemcpy(d_runoff, runoff, (size_t)elems * esz, hipMemcpyHostToDevice);
-    if (e != hipSuccess) { release(); return fail(RR_E_HIP, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(RR_E_HIP, hipGetErrorString(e));
     rc = rr_runoff_to_qlateral_dev(device, n_rivers, n_points, T, d_indptr, d_indices, d_w, d_runoff, runoff_is_f32, stride_t,
                                    stride_p, d_area, flags, d_out, nullptr);
     if (!rc) {
         e = hipMemcpy(qlateral, d_out, (size_t)(T * n_rivers) * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
     }
-    release();
     return rc;
 }
 
@@ -1345,24 +1319,20 @@ int rr_grid_overlap_area(int device, int64_t n_rows, int64_t n_rings, int64_t n_
     for (int64_t j = 0; j < ny; ++j)
         if (!(y_bounds[j] < y_bounds[j + 1])) return fail(RR_E_INVALID, "rr_grid_overlap_area: y_bounds not strictly ascending");
 
-    int64_t *d_rr = nullptr, *d_ro = nullptr, *d_po = nullptr;
-    double *d_w = nullptr, *d_lon = nullptr, *d_lat = nullptr, *d_xb = nullptr, *d_yb = nullptr, *d_out = nullptr;
-    int32_t *d_rc = nullptr;
-    int rc = dev_alloc(&d_rr, n_rows + 1);
-    if (!rc) rc = dev_alloc(&d_ro, n_rings + 1);
-    if (!rc) rc = dev_alloc(&d_po, n_rows + 1);
-    if (!rc) rc = dev_alloc(&d_w, n_rings);
-    if (!rc) rc = dev_alloc(&d_lon, n_vertices);
-    if (!rc) rc = dev_alloc(&d_lat, n_vertices);
-    if (!rc) rc = dev_alloc(&d_xb, nx + 1);
-    if (!rc) rc = dev_alloc(&d_yb, ny + 1);
-    if (!rc) rc = dev_alloc(&d_rc, 3 * n_rows);
-    if (!rc) rc = dev_alloc(&d_out, n_pairs);
-    auto release = [&]() {
-        (void)hipFree(d_rr); (void)hipFree(d_ro); (void)hipFree(d_po); (void)hipFree(d_w); (void)hipFree(d_lon);
-        (void)hipFree(d_lat); (void)hipFree(d_xb); (void)hipFree(d_yb); (void)hipFree(d_rc); (void)hipFree(d_out);
-    };
-    if (rc) { release(); return rc; }
+    DevBuf<int64_t> d_rr, d_ro, d_po;
+    DevBuf<double> d_w, d_lon, d_lat, d_xb, d_yb, d_out;
+    DevBuf<int32_t> d_rc;
+    int rc = d_rr.alloc(n_rows + 1);
+    if (!rc) rc = d_ro.alloc(n_rings + 1);
+    if (!rc) rc = d_po.alloc(n_rows + 1);
+    if (!rc) rc = d_w.alloc(n_rings);
+    if (!rc) rc = d_lon.alloc(n_vertices);
+    if (!rc) rc = d_lat.alloc(n_vertices);
+    if (!rc) rc = d_xb.alloc(nx + 1);
+    if (!rc) rc = d_yb.alloc(ny + 1);
+    if (!rc) rc = d_rc.alloc(3 * n_rows);
+    if (!rc) rc = d_out.alloc(n_pairs);
+    if (rc) return rc;
     auto up = [](void *dst, const void *src, int64_t bytes) {
         return bytes > 0 ? hipMemcpy(dst, src, (size_t)bytes, hipMemcpyHostToDevice) : hipSuccess;
     };
@@ -1375,14 +1345,13 @@ int rr_grid_overlap_area(int device, int64_t n_rows, int64_t n_rings, int64_t n_
     if (e == hipSuccess) e = up(d_xb, x_bounds, (nx + 1) * 8);
     if (e == hipSuccess) e = up(d_yb, y_bounds, (ny + 1) * 8);
     if (e == hipSuccess) e = up(d_rc, row_cells, 3 * n_rows * 4);
-    if (e != hipSuccess) { release(); return fail(RR_E_HIP, hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(RR_E_HIP, hipGetErrorString(e));
     rc = rr_grid_overlap_area_dev(device, n_rows, n_rings, n_vertices, nx, ny, n_pairs, d_rr, d_ro, d_w, d_lon, d_lat, d_xb, d_yb,
                                   d_rc, d_po, d_out, nullptr);
     if (!rc) {
         e = hipMemcpy(area, d_out, (size_t)n_pairs * sizeof(double), hipMemcpyDeviceToHost);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
     }
-    release();
     return rc;
 }
 
@@ -1393,8 +1362,7 @@ int rr_dev_malloc(int device, int64_t bytes, void **out)
     if (!out || bytes < 0) return fail(RR_E_INVALID, "rr_dev_malloc: bad argument");
     if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_dev_malloc: no such HIP device");
     HIPCHK(hipSetDevice(device));
-    hipError_t e = hipMalloc(out, (size_t)std::max<int64_t>(bytes, 1));
-    if (e != hipSuccess) return fail(RR_E_ALLOC, std::string("hipMalloc: ") + hipGetErrorString(e));
+    if (rr::dev_mem_alloc(out, (size_t)std::max<int64_t>(bytes, 1)) != RR_OK) return fail(RR_E_ALLOC, "hipMalloc: " + rr::g_dev_refusal);
     return RR_OK;
 }
 
@@ -1403,7 +1371,17 @@ int rr_dev_free(int device, void *ptr)
     if (!ptr) return RR_OK;
     if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_dev_free: no such HIP device");
     HIPCHK(hipSetDevice(device));
-    HIPCHK(hipFree(ptr));
+    (void)hipGetLastError();
+    rr::dev_mem_free(ptr);
+    const hipError_t e = hipGetLastError();      // of the release in there; the message is the one this entry point always had
+    if (e != hipSuccess) return fail(RR_E_HIP, std::string("hipFree" "(ptr): ") + hipGetErrorString(e));
+    return RR_OK;
+}
+
+int rr_dev_alloc_stats(int64_t out[2])
+{
+    if (!out) return fail(RR_E_INVALID, "rr_dev_alloc_stats: null out");
+    out[0] = rr::g_dev_live; out[1] = rr::g_dev_made;
     return RR_OK;
 }
 
@@ -1429,9 +1407,9 @@ int rr_copy_bandwidth(int device, int64_t bytes, int reps, double *gbps)
     if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_copy_bandwidth: no such HIP device");
     HIPCHK(hipSetDevice(device));
     const int64_t count = bytes / 16;
-    double2 *a = nullptr, *b = nullptr;
-    int rc = dev_alloc(&a, count);
-    if (!rc) rc = dev_alloc(&b, count);
+    DevBuf<double2> a, b;
+    int rc = a.alloc(count);
+    if (!rc) rc = b.alloc(count);
     hipEvent_t e0 = nullptr, e1 = nullptr;
     float ms = 0.f;
     if (!rc) {
@@ -1440,9 +1418,9 @@ int rr_copy_bandwidth(int device, int64_t bytes, int reps, double *gbps)
         if (e == hipSuccess) e = hipEventCreate(&e1);
         const dim3 g((unsigned)((count + kBlock - 1) / kBlock));      // one element per thread (count <= 2^31 x 256 elements)
         if (e == hipSuccess) {
-            hipLaunchKernelGGL(k_copy16, g, dim3(kBlock), 0, nullptr, (const double2 *)a, b, count);      // warm-up
+            hipLaunchKernelGGL(k_copy16, g, dim3(kBlock), 0, nullptr, (const double2 *)a, b.get(), count);      // warm-up
             e = hipEventRecord(e0, nullptr);
-            for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_copy16, g, dim3(kBlock), 0, nullptr, (const double2 *)a, b, count);
+            for (int r = 0; r < reps; ++r) hipLaunchKernelGGL(k_copy16, g, dim3(kBlock), 0, nullptr, (const double2 *)a, b.get(), count);
             if (e == hipSuccess) e = hipEventRecord(e1, nullptr);
             if (e == hipSuccess) e = hipEventSynchronize(e1);
             if (e == hipSuccess) e = hipEventElapsedTime(&ms, e0, e1);
@@ -1460,8 +1438,6 @@ int rr_copy_bandwidth(int device, int64_t bytes, int reps, double *gbps)
     }
     if (e0) (void)hipEventDestroy(e0);
     if (e1) (void)hipEventDestroy(e1);
-    if (a) (void)hipFree(a);
-    if (b) (void)hipFree(b);
     if (rc) return rc;
     *gbps = 2.0 * (double)count * 16.0 * reps / ((double)ms * 1e-3) / 1e9;      // bytes read + bytes written
     return RR_OK;

@@ -2,6 +2,12 @@
 // the route cores behind the C ABI.  Part of the one translation unit rr_engine.hip builds.
 #pragma once
 
+#include <atomic>
+
+#include "rr_devbuf.hpp"
+
+using rr::DevBuf;
+
 // ------------------------------------------------------------------------------------------------
 // plan object
 // ------------------------------------------------------------------------------------------------
@@ -115,16 +121,14 @@ struct HostPipe {
     int64_t chunk_mib = 512;              // staging chunk: long enough for the DMA engines to reach their rate, short enough to pipeline
     int64_t chunk_rows = 64, ring_chunks = 8;
     double *pin_in[kPinned] = {nullptr, nullptr, nullptr}, *pin_out[kPinned] = {nullptr, nullptr, nullptr};
-    double *dev_in = nullptr, *dev_out = nullptr;
-    int64_t pin_cap = 0, dev_cap = 0;      // doubles per pinned buffer / per device ring
+    DevBuf<double> dev_in, dev_out;       // the device rings (count(): doubles per ring)
+    int64_t pin_cap = 0;                  // doubles per pinned buffer
     hipStream_t s_h2d = nullptr, s_d2h = nullptr;
     std::vector<hipEvent_t> ev_h2d, ev_d2h, ev_adv;
     void destroy()
     {
         for (int k = 0; k < kPinned; ++k) { if (pin_in[k]) (void)hipHostFree(pin_in[k]); if (pin_out[k]) (void)hipHostFree(pin_out[k]); pin_in[k] = pin_out[k] = nullptr; }
-        if (dev_in) (void)hipFree(dev_in);
-        if (dev_out) (void)hipFree(dev_out);
-        dev_in = dev_out = nullptr; pin_cap = dev_cap = 0;
+        dev_in.reset(); dev_out.reset(); pin_cap = 0;
         for (auto *v : {&ev_h2d, &ev_d2h, &ev_adv}) { for (hipEvent_t e : *v) (void)hipEventDestroy(e); v->clear(); }
         if (s_h2d) (void)hipStreamDestroy(s_h2d);
         if (s_d2h) (void)hipStreamDestroy(s_d2h);
@@ -139,22 +143,19 @@ struct rr_plan {
     int64_t chunk_rows = 16, sample_every = 0;
 
     // streaming kernel (k_tick): lag-ordered layout of rr::HostPlan
-    int32_t *d_child_ptr = nullptr, *d_lag = nullptr, *d_perm = nullptr, *d_inv = nullptr, *d_inner_pos = nullptr;
-    int32_t *d_bidx = nullptr;   // ghost / export slot of flagged positions
-    uint16_t *d_hwc = nullptr;
-    double *d_w = nullptr, *d_c1row_h = nullptr, *d_c2 = nullptr, *d_c3 = nullptr, *d_c4 = nullptr;
-    double *d_x = nullptr, *d_isum = nullptr, *d_qch = nullptr;
-    double *d_a2 = nullptr, *d_c1own = nullptr, *d_z = nullptr;   // UnitMuskingum with general edge data (rr_plan_set_unit_weights): streaming kernel only
+    DevBuf<int32_t> d_child_ptr, d_lag, d_perm, d_inv, d_inner_pos;
+    DevBuf<int32_t> d_bidx;   // ghost / export slot of flagged positions
+    DevBuf<uint16_t> d_hwc;
+    DevBuf<double> d_w, d_c1row_h, d_c2, d_c3, d_c4;
+    DevBuf<double> d_x, d_isum, d_qch;
+    DevBuf<double> d_a2, d_c1own, d_z;   // UnitMuskingum with general edge data (rr_plan_set_unit_weights): streaming kernel only
     bool unit_general = false;
-    double *d_ring = nullptr;
-    int64_t ring_cap = 0;  // doubles
-    double *d_stage = nullptr;
-    int64_t stage_cap = 0;
-    double *d_mrows = nullptr;   // intermediate rows of the tiled permutation
-    int64_t mrows_cap = 0;
+    DevBuf<double> d_ring;
+    DevBuf<double> d_stage;
+    DevBuf<double> d_mrows;   // intermediate rows of the tiled permutation
     // tiled permutations: [0] params order -> engine order (pi = perm), [1] engine -> params (pi = inv)
-    uint16_t *d_slot_a[2] = {nullptr, nullptr}, *d_slot_b[2] = {nullptr, nullptr};
-    int32_t *d_m_index[2] = {nullptr, nullptr};
+    DevBuf<uint16_t> d_slot_a[2], d_slot_b[2];
+    DevBuf<int32_t> d_m_index[2];
     int64_t perm_rows_per_block = 2;
 
     // time-tiled routing (k_tile): subtree tiles of rr::TilePlan
@@ -165,13 +166,13 @@ struct rr_plan {
     int64_t wave_K = 0;          // ticks per task (multiple of 16); 0 = chosen per call
     Schedule sch;                // prepare_call: the schedule of the call about to start (or running, or just ended)
     int64_t kc_cap = int64_t{1} << 20;      // longest task (record chunks) the device had room for; 0: no record ring fits, the plan streams
-    TileMeta *d_tmeta = nullptr;     // per tile (rr_kernels_tile.hpp)
-    int4 *d_pmeta = nullptr;         // per position {lag | flags, first upstream position, xpos, upstream counts}
-    int32_t *d_tperm = nullptr, *d_tinv = nullptr;
-    int32_t *d_inner_idx = nullptr;
+    DevBuf<TileMeta> d_tmeta;     // per tile (rr_kernels_tile.hpp)
+    DevBuf<int4> d_pmeta;         // per position {lag | flags, first upstream position, xpos, upstream counts}
+    DevBuf<int32_t> d_tperm, d_tinv;
+    DevBuf<int32_t> d_inner_idx;
     bool export_inside = false;      // an export reach that another tile mirrors (it has a downstream reach in this plan): streaming kernel only
-    double *d_coef = nullptr;        // per position {c1row, c2, c3}
-    double *d_coef_unit = nullptr;   // the same with zeros at the positions without upstream positions (UnitMuskingum's short tick)
+    DevBuf<double> d_coef;        // per position {c1row, c2, c3}
+    DevBuf<double> d_coef_unit;   // the same with zeros at the positions without upstream positions (UnitMuskingum's short tick)
     // Headwaters routed by the in-pass (rr_plan.hpp: mark_inpass_headwaters; RR_HW_INPASS=0: off).  The short tick of a call with one
     // sub-step per row, single member, reads d_pmeta_hw instead of d_pmeta -- the eligible positions carry a ghost's flag there: published,
     // never stored -- and RapidMuskingum d_coef_hw instead of d_coef: zeros at those positions, whose records k_rec_in has already routed.
@@ -179,24 +180,25 @@ struct rr_plan {
     std::vector<uint8_t> hw_elig;    // [np] eligible positions, with the plan's boundary reaches
     int64_t hw_counts[4] = {0, 0, 0, 0};
     std::vector<int32_t> meta_lag, meta_xpos, meta_flags;      // what upload_tile_meta last got (the boundary reaches' flags among them)
-    int4 *d_pmeta_hw = nullptr;
-    double *d_coef_hw = nullptr;
-    double *d_hwcoef = nullptr;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
-    double *d_hwq = nullptr;         // [n] k_rec_in's carry: a column's discharge after the last batch turned into records; launch_state_in: the call's initial state
+    DevBuf<int4> d_pmeta_hw;
+    DevBuf<double> d_coef_hw;
+    DevBuf<double> d_hwcoef;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
+    DevBuf<double> d_hwq;         // [n] k_rec_in's carry: a column's discharge after the last batch turned into records; launch_state_in: the call's initial state
     std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
     int32_t n_wide_tiles = 0;        // tiles with a reach of more than three upstream reaches: general kernel beside the LEAN one
-    double *d_sq = nullptr, *d_ss = nullptr, *d_si = nullptr, *d_sqch = nullptr;
-    double *d_esq = nullptr, *d_ess = nullptr, *d_esi = nullptr;      // the carried state of an ensemble's members, np apart
+    DevBuf<double> d_sq, d_ss, d_si, d_sqch;
+    DevBuf<double> d_esq, d_ess, d_esi;      // the carried state of an ensemble's members, np apart
     int64_t ens_cap = 0;             // members they have room for (rr_plan_reserve_ensemble)
-    double *d_full = nullptr, *d_chan = nullptr;   // UnitMuskingum state scattered to params order
-    int2 *d_colmeta = nullptr;   // per params column {position, lag}
-    int2 *d_ghostmeta = nullptr; // the same per boundary ghost (column of the ghost series)
-    double *d_c4_params = nullptr;   // c4dt in params order (scale of the record permutation)
+    DevBuf<double> d_full, d_chan;   // UnitMuskingum state scattered to params order
+    DevBuf<int2> d_colmeta;   // per params column {position, lag}
+    DevBuf<int2> d_ghostmeta; // the same per boundary ghost (column of the ghost series)
+    DevBuf<double> d_c4_params;   // c4dt in params order (scale of the record permutation)
     size_t dev_total_bytes = 0;
     int cu_count = 256;
 
     // boundary reaches of a partitioned network
     int64_t n_ghost = 0, n_export = 0;
+    bool boundary_whole = true;      // false from a failed rr_plan_set_boundary (counts and tables may disagree) to the next that succeeds: no route call until then
     int64_t ghost_min_lag = 0, export_max_lag = 0;
     std::vector<int32_t> ghost_reach, export_reach;   // params indices, in the caller's order
 
@@ -207,16 +209,16 @@ struct rr_plan {
     bool direct_enabled = true;          // RR_DIRECT=0 (tests): records for every call
     bool uh_rows_ok = true;      // false once the device refused the convolved rows of rr_unit_route_uh*_dev on the direct row path: records from then on
     int direct_window = 1;               // rows of the LDS window: largest span + 1 of the plan's tiles
-    DirectTile *d_dtiles = nullptr;
-    int4 *d_dlane = nullptr;
-    int32_t *d_dsend_ptr = nullptr, *d_dsend_lane = nullptr;
-    double *d_dcoef = nullptr, *d_dq = nullptr;
-    TileMeta *d_ktmeta = nullptr;        // the skeleton's tiles (TileArgs of its k_tile launches)
-    int4 *d_kpmeta = nullptr;
-    int32_t *d_kperm = nullptr, *d_kholecol = nullptr;
-    double *d_kcoef = nullptr, *d_ksq = nullptr, *d_kss = nullptr, *d_ksi = nullptr, *d_ksqch = nullptr;
-    int2 *d_kholemeta = nullptr;         // per hole {position in the skeleton, lag}: the out-pass that patches the holes
-    int2 *d_kghostmeta = nullptr;        // per boundary ghost {position of the skeleton's ghost that mirrors it, lag}: the in-pass of the ghost series
+    DevBuf<DirectTile> d_dtiles;
+    DevBuf<int4> d_dlane;
+    DevBuf<int32_t> d_dsend_ptr, d_dsend_lane;
+    DevBuf<double> d_dcoef, d_dq;
+    DevBuf<TileMeta> d_ktmeta;        // the skeleton's tiles (TileArgs of its k_tile launches)
+    DevBuf<int4> d_kpmeta;
+    DevBuf<int32_t> d_kperm, d_kholecol;
+    DevBuf<double> d_kcoef, d_ksq, d_kss, d_ksi, d_ksqch;
+    DevBuf<int2> d_kholemeta;         // per hole {position in the skeleton, lag}: the out-pass that patches the holes
+    DevBuf<int2> d_kghostmeta;        // per boundary ghost {position of the skeleton's ghost that mirrors it, lag}: the in-pass of the ghost series
     std::vector<double> h_dcoef;         // {c1row, c2, c3, c4dt} per column as rr_plan_set_coeffs got them
     int32_t direct_block = 0;            // tile capacity the plan was built with (rr_plan_set_boundary lays the direct plan out again)
     int64_t n_kholes = 0;
@@ -227,7 +229,7 @@ struct rr_plan {
     int32_t rec_batches = kRecLaunchBatches;   // record batches per launch of k_rec_in / k_rec_out in long calls (RR_REC_BATCHES: tests, A/B)
     bool rec_batches_forced = false;    // RR_REC_BATCHES was given: rec_batches in every call the time-tiled kernel takes
     bool perm_ready = false;            // the streaming kernel's tiled permutations are on the device
-    int32_t *d_adj_down = nullptr;      // adjoint (rr_rapid_adjoint_dev): downstream engine position of each position, -1 at outlets
+    DevBuf<int32_t> d_adj_down;      // adjoint (rr_rapid_adjoint_dev): downstream engine position of each position, -1 at outlets
 
     // profile of the last route call: the routing kernel (ev, rr_plan_profile) and, sampled the same way, the kernels around it
     // (aux: 0 in-pass, 1 out-pass, 2 the skeleton's k_tile launches of the direct row path, 3 its out-pass over the holes)
@@ -242,19 +244,34 @@ struct rr_plan {
     hipStream_t last_stream = nullptr;
 };
 
-namespace {
+// The engine's device memory: every allocation and release goes through these two (rr_devbuf.hpp declares them; DevBuf and
+// rr_dev_malloc / rr_dev_free are their callers).  They count, for the whole process, the allocations alive and the allocations
+// made (rr_dev_alloc_stats), and -- a test switch, RR_ALLOC_FAIL_AT=k read by rr_plan_create -- refuse the k-th one from then on, once.
+namespace rr {
+std::atomic<int64_t> g_dev_live{0}, g_dev_made{0}, g_dev_fail_in{0};      // g_dev_fail_in: allocations until the injected refusal (0: none)
+thread_local std::string g_dev_refusal;      // the runtime's words for the last refused allocation (rr_dev_malloc has a message of its own around them)
 
-template <typename T>
-int dev_alloc(T **p, int64_t count)
+int dev_mem_alloc(void **p, size_t bytes)
 {
     *p = nullptr;
-    if (count <= 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(T));
-    if (e != hipSuccess)
-        return fail(RR_E_ALLOC, std::string("hipMalloc of ") + std::to_string((size_t)count * sizeof(T)) +
-                                    " bytes failed: " + hipGetErrorString(e));
+    const bool injected = g_dev_fail_in > 0 && --g_dev_fail_in == 0;
+    const hipError_t e = injected ? hipErrorOutOfMemory : hipMalloc(p, bytes);
+    if (e != hipSuccess) {
+        *p = nullptr;
+        g_dev_refusal = std::string(hipGetErrorString(e)) + (injected ? " (injected)" : "");
+        return fail(RR_E_ALLOC, "hipMalloc of " + std::to_string(bytes) + " bytes failed: " + g_dev_refusal);
+    }
+    ++g_dev_live; ++g_dev_made;
     return RR_OK;
 }
+
+void dev_mem_free(void *p)
+{
+    if (p && hipFree(p) == hipSuccess) --g_dev_live;      // (a block the runtime would not free stays counted; rr_dev_free reports it)
+}
+}  // namespace rr
+
+namespace {
 
 template <typename T>
 int dev_upload(T *dst, const std::vector<T> &src)
@@ -264,23 +281,26 @@ int dev_upload(T *dst, const std::vector<T> &src)
     return RR_OK;
 }
 
+template <typename T>
+int dev_upload(const DevBuf<T> &dst, const std::vector<T> &src) { return dev_upload(dst.get(), src); }
+
+template <typename... B>
+void reset_all(B &...buf) { (buf.reset(), ...); }
+
+// Room for `src` (kept where the buffer already has it), then the upload.
+template <typename T>
+int assign(DevBuf<T> &buf, const std::vector<T> &src)
+{
+    if (int rc = buf.reserve(std::max<int64_t>(1, (int64_t)src.size()))) return rc;
+    return dev_upload(buf, src);
+}
+
 int need_device(const rr_plan *plan)
 {
     if (!plan) return fail(RR_E_INVALID, "null plan");
     if (plan->device < 0)
         return fail(RR_E_NO_DEVICE, "this plan is host-only (RR_DEVICE_NONE): the HIP engine has no CPU fallback");
     HIPCHK(hipSetDevice(plan->device));
-    return RR_OK;
-}
-
-template <typename T>
-int ensure_cap(T **buf, int64_t *cap, int64_t count)
-{
-    if (*cap >= count) return RR_OK;
-    if (*buf) { (void)hipFree(*buf); *buf = nullptr; *cap = 0; }
-    int rc = dev_alloc(buf, count);
-    if (rc) return rc;
-    *cap = count;
     return RR_OK;
 }
 
@@ -294,9 +314,8 @@ int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vec
         tm[t] = TileMeta{TP.tile_ptr[t], TP.tile_ptr[t + 1], TP.tile_level[t], TP.tile_lag_lo[t], TP.tile_lag_hi[t], flags[t], 0, 0};
     std::vector<int4> pm((size_t)TP.np);
     for (int64_t p = 0; p < TP.np; ++p) pm[p] = make_int4(lag[p], TP.cfirst[p], xpos[p], (int32_t)TP.ccnt[p]);
-    int rc = RR_OK;
-    if (!P->d_tmeta) rc = dev_alloc(&P->d_tmeta, TP.n_tiles);
-    if (!rc && !P->d_pmeta) rc = dev_alloc(&P->d_pmeta, TP.np);
+    int rc = P->d_tmeta.reserve(std::max<int64_t>(1, TP.n_tiles));
+    if (!rc) rc = P->d_pmeta.reserve(std::max<int64_t>(1, TP.np));
     if (!rc) rc = dev_upload(P->d_tmeta, tm);
     if (!rc) rc = dev_upload(P->d_pmeta, pm);
     // the in-pass headwaters: a ghost's flag in the short tick's own position table, a flag in the column metadata for k_rec_in
@@ -310,10 +329,8 @@ int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vec
     for (int64_t i = 0; i < H.n; ++i)      // a headwater column is flagged: UnitMuskingum's out-pass leaves it unclamped
         cm[i] = make_int2(TP.inv[i], (TP.lag[TP.inv[i]] & kLagMask) | (H.child_ptr[H.inv[i] + 1] == H.child_ptr[H.inv[i]] ? kColHeadwater : 0) |
                                          (P->hw_elig[TP.inv[i]] ? kColInpass : 0));
-    if (!rc && !P->d_pmeta_hw) rc = dev_alloc(&P->d_pmeta_hw, TP.np);
-    if (!rc) rc = dev_upload(P->d_pmeta_hw, pm);
-    if (!rc && !P->d_colmeta) rc = dev_alloc(&P->d_colmeta, H.n);
-    if (!rc) rc = dev_upload(P->d_colmeta, cm);
+    if (!rc) rc = assign(P->d_pmeta_hw, pm);
+    if (!rc) rc = assign(P->d_colmeta, cm);
     return rc;
 }
 
@@ -359,11 +376,8 @@ direct_kernel_t direct_kernel(bool in32, bool out32, bool sub = false, int unit 
 // Called by rr_plan_create and again by rr_plan_set_boundary, which lays the plan out anew around the boundary reaches.
 int upload_direct_plan(rr_plan *P)
 {
-    void *old[] = {P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef,
-                   P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch, P->d_kholemeta, P->d_kghostmeta};
-    for (void *p : old) if (p) (void)hipFree(p);
-    P->d_dtiles = nullptr; P->d_dlane = nullptr; P->d_dsend_ptr = P->d_dsend_lane = nullptr; P->d_dcoef = P->d_dq = nullptr; P->d_ktmeta = nullptr; P->d_kpmeta = nullptr;
-    P->d_kperm = P->d_kholecol = nullptr; P->d_kcoef = P->d_ksq = P->d_kss = P->d_ksi = P->d_ksqch = nullptr; P->d_kholemeta = P->d_kghostmeta = nullptr;
+    reset_all(P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef,
+              P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch, P->d_kholemeta, P->d_kghostmeta);      // the old layout goes before the new one is allocated (one left out here would only go later, at its alloc)
     P->n_kholes = 0; P->n_kwide = 0;
     P->direct_window = 3;
     for (int32_t sp : P->dp.tile_span) P->direct_window = std::max(P->direct_window, sp + 3);
@@ -381,16 +395,12 @@ int upload_direct_plan(rr_plan *P)
     for (int32_t t = 0; t < D.n_tiles; ++t) dt[t] = DirectTile{D.tile_c0[t], D.tile_nc[t], D.tile_lag_lo[t], D.tile_span[t]};
     std::vector<int4> dl((size_t)n);
     for (int64_t i = 0; i < n; ++i) dl[i] = make_int4(D.delay[i], D.up3[i], D.xinfo[i], H.lag[H.inv[i]]);
-    int rc = dev_alloc(&P->d_dtiles, D.n_tiles);
-    if (!rc) rc = dev_upload(P->d_dtiles, dt);
-    if (!rc) rc = dev_alloc(&P->d_dlane, n);
-    if (!rc) rc = dev_upload(P->d_dlane, dl);
-    if (!rc) rc = dev_alloc(&P->d_dsend_ptr, D.n_tiles + 1);
-    if (!rc) rc = dev_upload(P->d_dsend_ptr, D.send_ptr);
-    if (!rc) rc = dev_alloc(&P->d_dsend_lane, (int64_t)D.send_lane.size());
-    if (!rc) rc = dev_upload(P->d_dsend_lane, D.send_lane);
-    if (!rc) rc = dev_alloc(&P->d_dcoef, 4 * n);
-    if (!rc) rc = dev_alloc(&P->d_dq, n);
+    int rc = assign(P->d_dtiles, dt);
+    if (!rc) rc = assign(P->d_dlane, dl);
+    if (!rc) rc = assign(P->d_dsend_ptr, D.send_ptr);
+    if (!rc) rc = assign(P->d_dsend_lane, D.send_lane);
+    if (!rc) rc = P->d_dcoef.alloc(4 * n);
+    if (!rc) rc = P->d_dq.alloc(n);
     std::vector<TileMeta> tm((size_t)K.n_tiles);
     std::vector<int32_t> klag(K.lag), kxpos(K.xpos), kflags(K.tile_flags);
     // boundary exports among the skeleton's reaches: flagged as in the plan's own tiles (rr_plan_set_boundary); the slot in the export
@@ -413,23 +423,14 @@ int upload_direct_plan(rr_plan *P)
         if (D.big[i]) { hm.push_back(make_int2(K.inv[i], K.lag[K.inv[i]] & kLagMask)); hc.push_back((int32_t)i); }
     for (int32_t i : P->ghost_reach) { const int32_t g = K.ext_ghost[i]; gm.push_back(make_int2(g, K.lag[g] & kLagMask)); }
     P->n_kholes = (int64_t)hm.size();
-    if (!rc) rc = dev_alloc(&P->d_ktmeta, K.n_tiles);
-    if (!rc) rc = dev_upload(P->d_ktmeta, tm);
-    if (!rc) rc = dev_alloc(&P->d_kpmeta, K.np);
-    if (!rc) rc = dev_upload(P->d_kpmeta, pm);
-    if (!rc) rc = dev_alloc(&P->d_kperm, K.np);
-    if (!rc) rc = dev_upload(P->d_kperm, K.perm);
-    if (!rc) rc = dev_alloc(&P->d_kcoef, 3 * K.np);
-    if (!rc) rc = dev_alloc(&P->d_ksq, K.np);
-    if (!rc) rc = dev_alloc(&P->d_kss, K.np);
-    if (!rc) rc = dev_alloc(&P->d_ksi, K.np);
-    if (!rc) rc = dev_alloc(&P->d_ksqch, K.np);
-    if (!rc) rc = dev_alloc(&P->d_kholemeta, P->n_kholes);
-    if (!rc) rc = dev_upload(P->d_kholemeta, hm);
-    if (!rc) rc = dev_alloc(&P->d_kholecol, P->n_kholes);
-    if (!rc) rc = dev_upload(P->d_kholecol, hc);
-    if (!rc) rc = dev_alloc(&P->d_kghostmeta, (int64_t)gm.size());
-    if (!rc) rc = dev_upload(P->d_kghostmeta, gm);
+    if (!rc) rc = assign(P->d_ktmeta, tm);
+    if (!rc) rc = assign(P->d_kpmeta, pm);
+    if (!rc) rc = assign(P->d_kperm, K.perm);
+    if (!rc) rc = P->d_kcoef.alloc(3 * K.np);
+    for (DevBuf<double> *state : {&P->d_ksq, &P->d_kss, &P->d_ksi, &P->d_ksqch}) if (!rc) rc = state->alloc(K.np);
+    if (!rc) rc = assign(P->d_kholemeta, hm);
+    if (!rc) rc = assign(P->d_kholecol, hc);
+    if (!rc) rc = assign(P->d_kghostmeta, gm);
     return rc;
 }
 
@@ -461,20 +462,12 @@ int upload_tiled_permutations(rr_plan *P)
     for (int w = 0; w < 2 && !rc; ++w) {
         rr::TiledPermutation tp;
         rr::build_tiled_permutation(pis[w], n, kPermE * kPermThreads, tp);
-        rc = dev_alloc(&P->d_slot_a[w], n);
-        if (!rc) rc = dev_alloc(&P->d_slot_b[w], n);
-        if (!rc) rc = dev_alloc(&P->d_m_index[w], n);
-        if (!rc) rc = dev_upload(P->d_slot_a[w], tp.slot_a);
-        if (!rc) rc = dev_upload(P->d_slot_b[w], tp.slot_b);
-        if (!rc) rc = dev_upload(P->d_m_index[w], tp.m_index);
+        rc = assign(P->d_slot_a[w], tp.slot_a);
+        if (!rc) rc = assign(P->d_slot_b[w], tp.slot_b);
+        if (!rc) rc = assign(P->d_m_index[w], tp.m_index);
     }
     if (rc) {      // all or nothing: a later call must not find half of the tables
-        for (int w = 0; w < 2; ++w) {
-            if (P->d_slot_a[w]) (void)hipFree(P->d_slot_a[w]);
-            if (P->d_slot_b[w]) (void)hipFree(P->d_slot_b[w]);
-            if (P->d_m_index[w]) (void)hipFree(P->d_m_index[w]);
-            P->d_slot_a[w] = P->d_slot_b[w] = nullptr; P->d_m_index[w] = nullptr;
-        }
+        for (int w = 0; w < 2; ++w) reset_all(P->d_slot_a[w], P->d_slot_b[w], P->d_m_index[w]);
         return rc;
     }
     P->perm_ready = true;
@@ -660,20 +653,20 @@ int reserve_core(rr_plan *P, const CallShape &s, Schedule *out)
     Schedule sch;
     for (;;) {
         sch = choose_schedule(P, s);
-        if (sch.kernel == Kernel::Direct && s.uh && ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows) != RR_OK) {      // no room for the convolved rows: the fused form on records
+        if (sch.kernel == Kernel::Direct && s.uh && P->d_mrows.reserve(sch.mrows) != RR_OK) {      // no room for the convolved rows: the fused form on records
             (void)hipGetLastError();
             P->uh_rows_ok = false;
             continue;
         }
-        if (ensure_cap(&P->d_ring, &P->ring_cap, sch.ring) == RR_OK) break;
+        if (P->d_ring.reserve(sch.ring) == RR_OK) break;
         (void)hipGetLastError();
         if (sch.kernel == Kernel::Direct) return fail(RR_E_ALLOC, "route: the skeleton's record ring does not fit on the device");
         if (sch.kernel == Kernel::Tick) return fail(RR_E_ALLOC, "route: the work rows of the streaming kernel do not fit on the device");
         if (s.members > 0) return fail(RR_E_ALLOC, "route: the record rings of " + std::to_string(s.members) + " ensemble members do not fit on the device");      // (kc_cap is the plan's: a smaller group is the remedy)
         P->kc_cap = sch.KC / 2;      // shorter tasks, a smaller ring; 0: this plan streams
     }
-    int rc = ensure_cap(&P->d_mrows, &P->mrows_cap, sch.mrows);
-    if (!rc) rc = ensure_cap(&P->d_stage, &P->stage_cap, sch.stage);
+    int rc = P->d_mrows.reserve(sch.mrows);
+    if (!rc) rc = P->d_stage.reserve(sch.stage);
     if (!rc && sch.kernel == Kernel::Tick && !P->perm_ready) rc = upload_tiled_permutations(P);
     if (!rc && sch.kernel == Kernel::Tile && s.host) rc = host_pipe_prepare(P);
     if (rc) return rc;
@@ -704,10 +697,10 @@ int prepare_call(rr_plan *P, const CallShape &s, const char *who)
     if ((s.in32 || s.out32 || s.uh || s.runoff) && sch.kernel == Kernel::Tick)
         return fail(RR_E_UNSUPPORTED, std::string(who) + " needs the time-tiled kernel or the direct row path, which this call does not get");
     const size_t samples = P->sample_every >= kSampleGroup ? 1 : 0;
-    if (P->h.n > 0 && s.T > 0 && (sch.ring > P->ring_cap || sch.mrows > P->mrows_cap || sch.stage > P->stage_cap || !P->ev_first || P->ev.size() < 2 * samples ||
+    if (P->h.n > 0 && s.T > 0 && (sch.ring > P->d_ring.count() || sch.mrows > P->d_mrows.count() || sch.stage > P->d_stage.count() || !P->ev_first || P->ev.size() < 2 * samples ||
                                   (sch.kernel == Kernel::Tick && !P->perm_ready && sch.mrows > 0)))
         return fail(RR_E_STATE, "this call needs " + std::to_string((sch.ring + sch.mrows + sch.stage) * 8) + " bytes of work memory on the device (" +
-                                    std::to_string((P->ring_cap + P->mrows_cap + P->stage_cap) * 8) + " reserved): call " +
+                                    std::to_string((P->d_ring.count() + P->d_mrows.count() + P->d_stage.count()) * 8) + " reserved): call " +
                                     (s.members > 0 ? "rr_plan_reserve_ensemble(plan, " + std::to_string(s.members) + ", " : std::string("rr_plan_reserve(plan, mode, ")) +
                                     std::to_string(s.T) + ", " + std::to_string(s.nsub) + ", ...) first; the *_dev entry points only enqueue work");
     P->sch = sch;
@@ -812,7 +805,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         S.hw = P->hw_inpass && P->lean_enabled && nsub == 1 && S.members == 0 &&
                (mode == Mode::Unit || (mode == Mode::Rapid && !io.runoff && !io.uh_kernel));
         if (S.members > 0) {      // an ensemble: one ring per member, the members' carried state np apart (k_tile<..., ENS>)
-            if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->ring_cap) { S.open = false; return fail(RR_E_STATE, "route: the ensemble was not reserved"); }
+            if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->d_ring.count()) { S.open = false; return fail(RR_E_STATE, "route: the ensemble was not reserved"); }
             S.ring_stride = S.rec_chunks * kRec * TP.np;
             w.sq = P->d_esq; w.ss = P->d_ess; w.si = P->d_esi; w.sqch = nullptr;
         }
@@ -839,7 +832,7 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         const int64_t lag_rows = (dmax + nsub - 1) / nsub;
         S.ring_rows = S.in_place ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2);
         if (S.ring_rows > 0xFFFFFFFFLL || T > 0x7FFFFFFFLL) { S.open = false; return fail(RR_E_INVALID, "route: too many time rows"); }
-        if (S.ring_rows * n > P->ring_cap || (!S.in_place && C * n > P->mrows_cap) || (host_io && C * n > P->stage_cap)) {      // prepare_call sized them
+        if (S.ring_rows * n > P->d_ring.count() || (!S.in_place && C * n > P->d_mrows.count()) || (host_io && C * n > P->d_stage.count())) {      // prepare_call sized them
             S.open = false;
             return fail(RR_E_STATE, "route: work rows of the streaming kernel were not reserved");
         }
@@ -1503,6 +1496,7 @@ int check_route_args(rr_plan *P, bool need_c4, int64_t T, int64_t nsub)
     int rc = need_device(P);
     if (rc) return rc;
     if (!P->coeffs_set) return fail(RR_E_STATE, "route called before rr_plan_set_coeffs");
+    if (!P->boundary_whole) return fail(RR_E_STATE, "route called after a failed rr_plan_set_boundary: repeat that call first");
     if (need_c4 && !P->has_c4) return fail(RR_E_STATE, "rr_rapid_route needs c4_dt (rr_plan_set_coeffs got NULL)");
     if (T < 0 || nsub < 1) return fail(RR_E_INVALID, "route: need num steps >= 0 and sub-steps >= 1");
     if (nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "route: too many sub-steps");
@@ -1564,7 +1558,7 @@ int host_pipe_prepare(rr_plan *P)
     if (n * 8 * 64 <= (int64_t{1} << 30)) H.chunk_rows = std::max<int64_t>(H.chunk_rows, 64);
     H.ring_chunks = std::max<int64_t>(8, (2 * kRecRows + 15) / H.chunk_rows + 6);      // a batch of rows + its 15-row overlap stays readable
     const int64_t pin_need = H.chunk_rows * n, dev_need = H.ring_chunks * H.chunk_rows * n;
-    if (H.pin_cap < pin_need || H.dev_cap < dev_need) {
+    if (H.pin_cap < pin_need || H.dev_in.count() < dev_need) {
         H.destroy();
         for (int k = 0; k < HostPipe::kPinned; ++k) {
             if (hipHostMalloc((void **)&H.pin_in[k], (size_t)pin_need * 8, hipHostMallocDefault) != hipSuccess ||
@@ -1573,11 +1567,11 @@ int host_pipe_prepare(rr_plan *P)
                 return fail(RR_E_ALLOC, "host pipeline: pinned staging buffers could not be allocated");
             }
         }
-        if (hipMalloc((void **)&H.dev_in, (size_t)dev_need * 8) != hipSuccess || hipMalloc((void **)&H.dev_out, (size_t)dev_need * 8) != hipSuccess) {
+        if (H.dev_in.alloc(dev_need) != RR_OK || H.dev_out.alloc(dev_need) != RR_OK) {
             (void)hipGetLastError(); H.destroy();
             return fail(RR_E_ALLOC, "host pipeline: device staging rings could not be allocated");
         }
-        H.pin_cap = pin_need; H.dev_cap = dev_need;
+        H.pin_cap = pin_need;
     }
     if (!H.s_h2d) { HIPCHK(hipStreamCreateWithFlags(&H.s_h2d, hipStreamNonBlocking)); HIPCHK(hipStreamCreateWithFlags(&H.s_d2h, hipStreamNonBlocking)); }
     return RR_OK;
@@ -1708,7 +1702,7 @@ int route_rows(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io, h
 // for the call, `count` doubles each; out() copies them back.
 struct CallState {
     std::vector<double *> host, dev;
-    double *tmp = nullptr;
+    DevBuf<double> tmp;
     int64_t count = 0;
     hipStream_t stream = nullptr;
     int in(bool on_host, std::vector<double *> arrays, int64_t count_, hipStream_t stream_)
@@ -1716,7 +1710,7 @@ struct CallState {
         host = dev = arrays; count = count_; stream = stream_;
         const int64_t each = std::max<int64_t>(count, 1);
         if (!on_host) return RR_OK;
-        if (int rc = dev_alloc(&tmp, (int64_t)host.size() * each)) return rc;
+        if (int rc = tmp.alloc((int64_t)host.size() * each)) return rc;
         hipError_t e = hipSuccess;
         for (size_t i = 0; i < host.size() && e == hipSuccess; ++i)
             e = hipMemcpyAsync(dev[i] = tmp + i * each, host[i], count * sizeof(double), hipMemcpyHostToDevice, stream);
@@ -1729,7 +1723,7 @@ struct CallState {
         if (tmp && e == hipSuccess) e = hipStreamSynchronize(stream);
         return e == hipSuccess ? RR_OK : fail(RR_E_HIP, hipGetErrorString(e));
     }
-    ~CallState() { if (tmp) { (void)hipStreamSynchronize(stream); (void)hipFree(tmp); } }
+    ~CallState() { if (tmp) (void)hipStreamSynchronize(stream); }      // (before tmp goes)
 };
 
 // RapidMuskingum / channel-only Muskingum.  `who` names the entry point in the errors of prepare_call.
@@ -1825,7 +1819,7 @@ int unit_like(rr_plan *P, double *q_ch, double *q_full, const Rows &io_in, int64
     if (!rc && kernel == Kernel::Direct && io.uh_kernel) {
         // the direct row path: the convolution first, into the work rows (choose_schedule: uh), carry-over state updated in place;
         // the lanes then route those rows
-        if (T * n > P->mrows_cap) rc = fail(RR_E_STATE, "route: the convolved rows of the direct row path were not reserved");
+        if (T * n > P->d_mrows.count()) rc = fail(RR_E_STATE, "route: the convolved rows of the direct row path were not reserved");
         else if (io.dev_in32) rc = uh_convolve_core<float>(io.uh_kernel, uh_state_inout, io.dev_in32, P->d_mrows, T, io.uh_nks, n, stream, sel32);
         else rc = uh_convolve_core<double>(io.uh_kernel, uh_state_inout, io.dev_in, P->d_mrows, T, io.uh_nks, n, stream, kSelNative);
         io.dev_in = P->d_mrows; io.dev_in32 = nullptr; io.rows_in = T; io.uh_kernel = nullptr; io.uh_state = nullptr;

@@ -711,6 +711,13 @@ class DeviceBuffer:
             pass
 
 
+def dev_alloc_stats() -> dict:
+    """rr_dev_alloc_stats: the engine's device allocations alive now and made since the process started (plans, calls and DeviceBuffers alike)."""
+    out = np.zeros(2, dtype=np.int64)
+    check(_lib.lib().rr_dev_alloc_stats(ptr(out)))
+    return dict(live=int(out[0]), made=int(out[1]))
+
+
 def rows_upload(dst, dst_pitch: int, path, file_offset: int, file_pitch: int, row_bytes: int, n_rows: int, device: int = 0, stream=None) -> None:
     """rr_rows_upload: rows of a file straight into a device array (pinned staging, reader threads beside the copy engine)."""
     check(_lib.lib().rr_rows_upload(int(device), ptr(dst), int(dst_pitch), str(path).encode(), int(file_offset), int(file_pitch), int(row_bytes), int(n_rows), stream))
