@@ -146,13 +146,12 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
             for (int64_t i = 0; i < n; ++i) if (H.child_ptr[H.inv[i] + 1] > H.child_ptr[H.inv[i]]) inner_idx.push_back((int32_t)i);
             rc = assign(P->d_inner_idx, inner_idx);
             if (!rc) rc = upload_tile_meta(P, TP.lag, TP.xpos, TP.tile_flags);      // (and the column metadata of the record passes)
-            for (int32_t f : TP.tile_flags) P->n_wide_tiles += (f & kTileWide) ? 1 : 0;
-            if (!rc) rc = assign(P->d_tperm, TP.perm);
+            if (!rc) rc = assign(P->ts.perm, TP.perm);
             if (!rc) rc = assign(P->d_tinv, TP.inv);
-            for (DevBuf<double> *coef : {&P->d_coef, &P->d_coef_unit, &P->d_coef_hw}) if (!rc) rc = coef->alloc(3 * np);
+            for (DevBuf<double> *coef : {&P->ts.coef, &P->d_coef_unit, &P->d_coef_hw}) if (!rc) rc = coef->alloc(3 * np);
             if (!rc) rc = P->d_hwcoef.alloc(3 * n);
             if (!rc) rc = P->d_hwq.alloc(n);
-            for (DevBuf<double> *state : {&P->d_sq, &P->d_ss, &P->d_si, &P->d_sqch}) if (!rc) rc = state->alloc(np);
+            for (DevBuf<double> *state : {&P->ts.sq, &P->ts.ss, &P->ts.si, &P->ts.sqch}) if (!rc) rc = state->alloc(np);
             if (!rc) rc = P->d_full.alloc(n);
             if (!rc) rc = P->d_chan.alloc(n);
         }
@@ -790,7 +789,7 @@ int rr_rapid_route_ensemble_dev(rr_plan *P, int64_t members, double *q_t, int64_
     const hipStream_t st = (hipStream_t)stream;
     const int64_t np = P->tp.np;
     hipLaunchKernelGGL(k_tile_state_in_ens, dim3((unsigned)((np + kBlock - 1) / kBlock), (unsigned)members), dim3(kBlock), 0, st, P->d_esq, P->d_ess, P->d_esi,
-                       (const double *)q_t, q_pitch, (const int32_t *)P->d_tperm, (const int4 *)P->d_pmeta, (int32_t)np);
+                       (const double *)q_t, q_pitch, (const int32_t *)P->ts.perm, (const int4 *)P->ts.pmeta, (int32_t)np);
     rc = route_core(P, Mode::Rapid, T, nsub, io, st);
     if (rc) return rc;
     hipLaunchKernelGGL(k_tile_state_out_ens, dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)members), dim3(kBlock), 0, st, q_t, q_pitch,

@@ -136,6 +136,17 @@ struct HostPipe {
     }
 };
 
+// The device side of one rr::TilePlan, as k_tile's launches and the state kernels read it.  A plan has two: over its own tiles
+// (rr_plan::ts) and over the skeleton of the direct row path (rr_plan::ks); tiles_of() picks the one a call's kernel runs on.
+struct TileSet {
+    const rr::TilePlan *tp;
+    DevBuf<TileMeta> tmeta;       // per tile (rr_kernels_tile.hpp)
+    DevBuf<int4> pmeta;           // per position {lag | flags, first upstream position, xpos, upstream counts}
+    DevBuf<int32_t> perm;
+    DevBuf<double> coef, sq, ss, si, sqch;      // per position: {c1row, c2, c3}; the carried state
+    int32_t n_wide = 0;           // tiles with a reach of more than three upstream reaches: general kernel beside the LEAN one
+};
+
 struct rr_plan {
     rr::HostPlan h;
     int device = RR_DEVICE_NONE;
@@ -166,16 +177,14 @@ struct rr_plan {
     int64_t wave_K = 0;          // ticks per task (multiple of 16); 0 = chosen per call
     Schedule sch;                // prepare_call: the schedule of the call about to start (or running, or just ended)
     int64_t kc_cap = int64_t{1} << 20;      // longest task (record chunks) the device had room for; 0: no record ring fits, the plan streams
-    DevBuf<TileMeta> d_tmeta;     // per tile (rr_kernels_tile.hpp)
-    DevBuf<int4> d_pmeta;         // per position {lag | flags, first upstream position, xpos, upstream counts}
-    DevBuf<int32_t> d_tperm, d_tinv;
+    TileSet ts{&tp};              // the tiles' device side: tmeta, pmeta, perm, coef {c1row, c2, c3}, the carried state
+    DevBuf<int32_t> d_tinv;
     DevBuf<int32_t> d_inner_idx;
     bool export_inside = false;      // an export reach that another tile mirrors (it has a downstream reach in this plan): streaming kernel only
-    DevBuf<double> d_coef;        // per position {c1row, c2, c3}
-    DevBuf<double> d_coef_unit;   // the same with zeros at the positions without upstream positions (UnitMuskingum's short tick)
+    DevBuf<double> d_coef_unit;   // ts.coef with zeros at the positions without upstream positions (UnitMuskingum's short tick)
     // Headwaters routed by the in-pass (rr_plan.hpp: mark_inpass_headwaters; RR_HW_INPASS=0: off).  The short tick of a call with one
-    // sub-step per row, single member, reads d_pmeta_hw instead of d_pmeta -- the eligible positions carry a ghost's flag there: published,
-    // never stored -- and RapidMuskingum d_coef_hw instead of d_coef: zeros at those positions, whose records k_rec_in has already routed.
+    // sub-step per row, single member, reads d_pmeta_hw instead of ts.pmeta -- the eligible positions carry a ghost's flag there: published,
+    // never stored -- and RapidMuskingum d_coef_hw instead of ts.coef: zeros at those positions, whose records k_rec_in has already routed.
     bool hw_inpass = true;
     std::vector<uint8_t> hw_elig;    // [np] eligible positions, with the plan's boundary reaches
     int64_t hw_counts[4] = {0, 0, 0, 0};
@@ -185,8 +194,6 @@ struct rr_plan {
     DevBuf<double> d_hwcoef;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
     DevBuf<double> d_hwq;         // [n] k_rec_in's carry: a column's discharge after the last batch turned into records; launch_state_in: the call's initial state
     std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
-    int32_t n_wide_tiles = 0;        // tiles with a reach of more than three upstream reaches: general kernel beside the LEAN one
-    DevBuf<double> d_sq, d_ss, d_si, d_sqch;
     DevBuf<double> d_esq, d_ess, d_esi;      // the carried state of an ensemble's members, np apart
     int64_t ens_cap = 0;             // members they have room for (rr_plan_reserve_ensemble)
     DevBuf<double> d_full, d_chan;   // UnitMuskingum state scattered to params order
@@ -213,16 +220,13 @@ struct rr_plan {
     DevBuf<int4> d_dlane;
     DevBuf<int32_t> d_dsend_ptr, d_dsend_lane;
     DevBuf<double> d_dcoef, d_dq;
-    DevBuf<TileMeta> d_ktmeta;        // the skeleton's tiles (TileArgs of its k_tile launches)
-    DevBuf<int4> d_kpmeta;
-    DevBuf<int32_t> d_kperm, d_kholecol;
-    DevBuf<double> d_kcoef, d_ksq, d_kss, d_ksi, d_ksqch;
+    TileSet ks{&dp.skel};             // the skeleton's tiles (TileArgs of its k_tile launches)
+    DevBuf<int32_t> d_kholecol;
     DevBuf<int2> d_kholemeta;         // per hole {position in the skeleton, lag}: the out-pass that patches the holes
     DevBuf<int2> d_kghostmeta;        // per boundary ghost {position of the skeleton's ghost that mirrors it, lag}: the in-pass of the ghost series
     std::vector<double> h_dcoef;         // {c1row, c2, c3, c4dt} per column as rr_plan_set_coeffs got them
     int32_t direct_block = 0;            // tile capacity the plan was built with (rr_plan_set_boundary lays the direct plan out again)
     int64_t n_kholes = 0;
-    int32_t n_kwide = 0;
     bool in32_big_endian = false, out32_big_endian = false;      // rr_plan_set_row_format: float32 rows as a big-endian file stores them
     bool lean_enabled = true;           // RR_TILE_LEAN=0 (tests): the general tick for every call
     bool uh_pairs = true;               // the fused convolution takes two record batches per launch where it can (RR_UH_PAIRS=0: tests)
@@ -304,20 +308,27 @@ int need_device(const rr_plan *plan)
     return RR_OK;
 }
 
-// Tile and position constants of the time-tiled kernel, packed (TileArgs); boundary reaches of a partitioned network change
-// the lag flags, the xpos word and the tile flags (rr_plan_set_boundary).
+// Tile and position constants of a tile plan as k_tile reads them (TileArgs::tiles, ::pos), packed from the plan and the lag words, xpos
+// words and tile flags to go with it (the boundary reaches of a partitioned network change all three).  Returns the number of wide tiles.
+int32_t pack_tile_meta(const rr::TilePlan &TP, const std::vector<int32_t> &lag, const std::vector<int32_t> &xpos, const std::vector<int32_t> &flags, std::vector<TileMeta> &tm, std::vector<int4> &pm)
+{
+    tm.resize((size_t)TP.n_tiles); pm.resize((size_t)TP.np);
+    for (int32_t t = 0; t < TP.n_tiles; ++t)
+        tm[t] = TileMeta{TP.tile_ptr[t], TP.tile_ptr[t + 1], TP.tile_level[t], TP.tile_lag_lo[t], TP.tile_lag_hi[t], flags[t], 0, 0};
+    for (int64_t p = 0; p < TP.np; ++p) pm[p] = make_int4(lag[p], TP.cfirst[p], xpos[p], (int32_t)TP.ccnt[p]);
+    return (int32_t)std::count_if(flags.begin(), flags.end(), [](int32_t f) { return (f & kTileWide) != 0; });
+}
+
+// The plan's own tiles on the device (rr_plan_create; rr_plan_set_boundary and rr_plan_set_coeffs again), with the tables of the in-pass headwaters.
 int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vector<int32_t> &xpos, const std::vector<int32_t> &flags)
 {
     const rr::TilePlan &TP = P->tp;
-    std::vector<TileMeta> tm((size_t)TP.n_tiles);
-    for (int32_t t = 0; t < TP.n_tiles; ++t)
-        tm[t] = TileMeta{TP.tile_ptr[t], TP.tile_ptr[t + 1], TP.tile_level[t], TP.tile_lag_lo[t], TP.tile_lag_hi[t], flags[t], 0, 0};
-    std::vector<int4> pm((size_t)TP.np);
-    for (int64_t p = 0; p < TP.np; ++p) pm[p] = make_int4(lag[p], TP.cfirst[p], xpos[p], (int32_t)TP.ccnt[p]);
-    int rc = P->d_tmeta.reserve(std::max<int64_t>(1, TP.n_tiles));
-    if (!rc) rc = P->d_pmeta.reserve(std::max<int64_t>(1, TP.np));
-    if (!rc) rc = dev_upload(P->d_tmeta, tm);
-    if (!rc) rc = dev_upload(P->d_pmeta, pm);
+    std::vector<TileMeta> tm; std::vector<int4> pm;
+    P->ts.n_wide = pack_tile_meta(TP, lag, xpos, flags, tm, pm);
+    int rc = P->ts.tmeta.reserve(std::max<int64_t>(1, TP.n_tiles));
+    if (!rc) rc = P->ts.pmeta.reserve(std::max<int64_t>(1, TP.np));
+    if (!rc) rc = dev_upload(P->ts.tmeta, tm);
+    if (!rc) rc = dev_upload(P->ts.pmeta, pm);
     // the in-pass headwaters: a ghost's flag in the short tick's own position table, a flag in the column metadata for k_rec_in
     // (with the plan's coefficients once it has them: rr_plan_set_coeffs comes here again, mark_inpass_headwaters looks at c1row and c2)
     rr::mark_inpass_headwaters(TP, lag, kGhostBit, P->hw_elig, P->hw_counts, P->h_coef.empty() ? nullptr : P->h_coef.data());
@@ -342,7 +353,7 @@ int upload_tile_coef(rr_plan *P)
     if (P->h_coef.empty()) return RR_OK;
     std::vector<double> coef(P->h_coef);
     for (int32_t i : P->ghost_reach) { const int64_t p = P->tp.inv[i]; coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0; }
-    int rc = dev_upload(P->d_coef, coef);
+    int rc = dev_upload(P->ts.coef, coef);
     if (rc) return rc;
     {   // RapidMuskingum's short tick where the in-pass routes headwaters: those publish their record, as a ghost does
         std::vector<double> hw(coef);
@@ -361,24 +372,28 @@ int upload_tile_coef(rr_plan *P)
     return dev_upload(P->d_coef_unit, coef);
 }
 
+// ---- kernel pickers: the instantiation a call gets, one function per kernel family.  They name every form the engine has and no other. ----
+
 typedef void (*direct_kernel_t)(const DirectArgs);
-direct_kernel_t direct_kernel(bool in32, bool out32, bool sub = false, int unit = 0)
+struct DirectForm { bool in32, out32, sub, unit; direct_kernel_t kernel; };
+#define RR_DF(I_, O_, S_, U_) DirectForm{I_, O_, S_, U_ != 0, k_direct<kDirectAhead, I_, O_, S_, U_>}
+const DirectForm kDirectForms[] = {      // k_direct's twelve forms (upload_direct_plan walks them): UnitMuskingum reads float64 rows only
+    RR_DF(false, true, true, 1), RR_DF(false, false, true, 1), RR_DF(false, true, false, 1), RR_DF(false, false, false, 1), RR_DF(true, true, true, 0),   RR_DF(true, true, false, 0),
+    RR_DF(true, false, true, 0), RR_DF(true, false, false, 0), RR_DF(false, true, true, 0),  RR_DF(false, true, false, 0),  RR_DF(false, false, true, 0), RR_DF(false, false, false, 0)};
+#undef RR_DF
+direct_kernel_t direct_kernel(bool in32, bool out32, bool sub, bool unit)
 {
-    if (unit == 1)      // UnitMuskingum: float64 rows
-        return sub ? (out32 ? (direct_kernel_t)k_direct<kDirectAhead, false, true, true, 1> : (direct_kernel_t)k_direct<kDirectAhead, false, false, true, 1>)
-                   : (out32 ? (direct_kernel_t)k_direct<kDirectAhead, false, true, false, 1> : (direct_kernel_t)k_direct<kDirectAhead, false, false, false, 1>);
-#define RR_DK(I_, O_) (sub ? (direct_kernel_t)k_direct<kDirectAhead, I_, O_, true> : (direct_kernel_t)k_direct<kDirectAhead, I_, O_, false>)
-    return in32 ? (out32 ? RR_DK(true, true) : RR_DK(true, false)) : (out32 ? RR_DK(false, true) : RR_DK(false, false));
-#undef RR_DK
+    for (const DirectForm &f : kDirectForms) if (f.in32 == (in32 && !unit) && f.out32 == out32 && f.sub == sub && f.unit == unit) return f.kernel;
+    return nullptr;      // (every combination is in the table)
 }
 
 // The direct row path's device arrays (rr::DirectPlan): per-column constants, the skeleton's tile arrays, the columns of the holes' out-pass.
 // Called by rr_plan_create and again by rr_plan_set_boundary, which lays the plan out anew around the boundary reaches.
 int upload_direct_plan(rr_plan *P)
 {
-    reset_all(P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->d_ktmeta, P->d_kpmeta, P->d_kperm, P->d_kholecol, P->d_kcoef,
-              P->d_ksq, P->d_kss, P->d_ksi, P->d_ksqch, P->d_kholemeta, P->d_kghostmeta);      // the old layout goes before the new one is allocated (one left out here would only go later, at its alloc)
-    P->n_kholes = 0; P->n_kwide = 0;
+    reset_all(P->d_dtiles, P->d_dlane, P->d_dsend_ptr, P->d_dsend_lane, P->d_dcoef, P->d_dq, P->ks.tmeta, P->ks.pmeta, P->ks.perm, P->d_kholecol, P->ks.coef,
+              P->ks.sq, P->ks.ss, P->ks.si, P->ks.sqch, P->d_kholemeta, P->d_kghostmeta);      // the old layout goes before the new one is allocated (one left out here would only go later, at its alloc)
+    P->n_kholes = 0; P->ks.n_wide = 0;
     P->direct_window = 3;
     for (int32_t sp : P->dp.tile_span) P->direct_window = std::max(P->direct_window, sp + 3);
     if (!P->dp.ok || P->device < 0) return RR_OK;
@@ -386,8 +401,8 @@ int upload_direct_plan(rr_plan *P)
     const rr::DirectPlan &D = P->dp;
     const rr::TilePlan &K = D.skel;
     const int64_t n = H.n;
-    for (int v = 0; v < 12; ++v)      // > 64 KiB of dynamic LDS needs an explicit opt-in per kernel (v = 8 ... 11: UnitMuskingum, float64 rows in)
-        if (hipFuncSetAttribute((const void *)direct_kernel(v < 8 && (v & 1) != 0, (v & 2) != 0, v < 8 ? (v & 4) != 0 : (v & 1) != 0, v >= 8 ? 1 : 0), hipFuncAttributeMaxDynamicSharedMemorySize, (int)direct_lds_bytes(kDirectMaxWindow)) != hipSuccess) {
+    for (const DirectForm &f : kDirectForms)      // > 64 KiB of dynamic LDS needs an explicit opt-in per kernel
+        if (hipFuncSetAttribute((const void *)f.kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)direct_lds_bytes(kDirectMaxWindow)) != hipSuccess) {
             (void)hipGetLastError();
             P->direct_enabled = false;
         }
@@ -401,7 +416,6 @@ int upload_direct_plan(rr_plan *P)
     if (!rc) rc = assign(P->d_dsend_lane, D.send_lane);
     if (!rc) rc = P->d_dcoef.alloc(4 * n);
     if (!rc) rc = P->d_dq.alloc(n);
-    std::vector<TileMeta> tm((size_t)K.n_tiles);
     std::vector<int32_t> klag(K.lag), kxpos(K.xpos), kflags(K.tile_flags);
     // boundary exports among the skeleton's reaches: flagged as in the plan's own tiles (rr_plan_set_boundary); the slot in the export
     // series travels in xpos[] (an export is an outlet of its part: no ghost of another tile mirrors it -- checked by build_direct_plan)
@@ -411,23 +425,19 @@ int upload_direct_plan(rr_plan *P)
         const int32_t p = K.inv[i];
         klag[p] |= kExportBit; kxpos[p] = (int32_t)e; kflags[K.tile_of[p]] |= kTileExports;
     }
-    for (int32_t t = 0; t < K.n_tiles; ++t) {
-        tm[t] = TileMeta{K.tile_ptr[t], K.tile_ptr[t + 1], K.tile_level[t], K.tile_lag_lo[t], K.tile_lag_hi[t], kflags[t], 0, 0};
-        P->n_kwide += (kflags[t] & kTileWide) ? 1 : 0;
-    }
-    std::vector<int4> pm((size_t)K.np);
-    for (int64_t p = 0; p < K.np; ++p) pm[p] = make_int4(klag[p], K.cfirst[p], kxpos[p], (int32_t)K.ccnt[p]);
+    std::vector<TileMeta> tm; std::vector<int4> pm;
+    P->ks.n_wide = pack_tile_meta(K, klag, kxpos, kflags, tm, pm);
     std::vector<int2> hm, gm;
     std::vector<int32_t> hc;
     for (int64_t i = 0; i < n; ++i)
         if (D.big[i]) { hm.push_back(make_int2(K.inv[i], K.lag[K.inv[i]] & kLagMask)); hc.push_back((int32_t)i); }
     for (int32_t i : P->ghost_reach) { const int32_t g = K.ext_ghost[i]; gm.push_back(make_int2(g, K.lag[g] & kLagMask)); }
     P->n_kholes = (int64_t)hm.size();
-    if (!rc) rc = assign(P->d_ktmeta, tm);
-    if (!rc) rc = assign(P->d_kpmeta, pm);
-    if (!rc) rc = assign(P->d_kperm, K.perm);
-    if (!rc) rc = P->d_kcoef.alloc(3 * K.np);
-    for (DevBuf<double> *state : {&P->d_ksq, &P->d_kss, &P->d_ksi, &P->d_ksqch}) if (!rc) rc = state->alloc(K.np);
+    if (!rc) rc = assign(P->ks.tmeta, tm);
+    if (!rc) rc = assign(P->ks.pmeta, pm);
+    if (!rc) rc = assign(P->ks.perm, K.perm);
+    if (!rc) rc = P->ks.coef.alloc(3 * K.np);
+    for (DevBuf<double> *state : {&P->ks.sq, &P->ks.ss, &P->ks.si, &P->ks.sqch}) if (!rc) rc = state->alloc(K.np);
     if (!rc) rc = assign(P->d_kholemeta, hm);
     if (!rc) rc = assign(P->d_kholecol, hc);
     if (!rc) rc = assign(P->d_kghostmeta, gm);
@@ -447,7 +457,7 @@ int upload_direct_coef(rr_plan *P)
         const int64_t i = K.perm[p];
         kc[3 * p] = P->h_dcoef[4 * i]; kc[3 * p + 1] = P->h_dcoef[4 * i + 1]; kc[3 * p + 2] = P->h_dcoef[4 * i + 2];
     }
-    if (!rc) rc = dev_upload(P->d_kcoef, kc);
+    if (!rc) rc = dev_upload(P->ks.coef, kc);
     return rc;
 }
 
@@ -712,13 +722,15 @@ int prepare_call(rr_plan *P, const CallShape &s, const char *who)
 // profiles/r03_nt_and_rec_stream_ab.txt, r03_rec_stream_small_networks.txt.)
 hipStream_t rec_stream(const rr_plan *P) { return P->ses.stream; }
 
-int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io, hipStream_t stream,
+// The tiles a kernel's k_tile launches, record passes and state kernels work on: the skeleton's on the direct row path, else the plan's own.
+const TileSet &tiles_of(const rr_plan *P, Kernel kernel) { return kernel == Kernel::Direct ? P->ks : P->ts; }
+
+int session_setup(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io, hipStream_t stream,
                   const double *ghost_series, double *export_series)
 {
     const rr::HostPlan &H = P->h;
     const int64_t n = H.n;
     Session &S = P->ses;
-    if (S.open) return fail(RR_E_STATE, "a routing call is already open on this plan (rr_stream_end it first)");
     S = Session();
     S.mode = mode; S.T = T; S.nsub = nsub; S.total = T * nsub; S.io = io; S.stream = stream;
     S.members = io.members;
@@ -740,27 +752,34 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     P->prof_reach_steps = n * S.total * std::max<int64_t>(1, S.members);
     P->ev_reaches.clear();
     P->last_stream = stream;
-    S.open = true;
-    if (n == 0 || S.total == 0) return RR_OK;
-    if (P->n_ghost > 0 && !ghost_series) { S.open = false; return fail(RR_E_INVALID, "plan has ghost reaches but no ghost series was given"); }
-    if (P->n_export > 0 && !export_series) { S.open = false; return fail(RR_E_INVALID, "plan has export reaches but no export series was given"); }
+    if (n == 0 || S.total == 0) return RR_OK;      // (an empty call is open too: session_end closes it)
+    if (P->n_ghost > 0 && !ghost_series) return fail(RR_E_INVALID, "plan has ghost reaches but no ghost series was given");
+    if (P->n_export > 0 && !export_series) return fail(RR_E_INVALID, "plan has export reaches but no export series was given");
 
     S.KC = P->sch.KC; S.KS = P->sch.KS; S.rec_chunks = P->sch.chunks;     // ring sized by choose_schedule, allocated by rr_plan_reserve
     S.rec_nb = S.kernel == Kernel::Tile ? std::max<int64_t>(1, P->sch.rec_nb) : 1;
+    if (S.kernel != Kernel::Tick) {      // the k_tile launches' arguments, over the plan's tiles or the skeleton's (whose tasks are KS chunks)
+        const TileSet &ts = tiles_of(P, S.kernel);
+        TileArgs &w = S.ta;
+        w.tiles = ts.tmeta; w.pos = ts.pmeta; w.coef = ts.coef;
+        w.sq = ts.sq; w.ss = ts.ss; w.si = ts.si; w.sqch = ts.sqch;
+        w.np = (int32_t)ts.tp->np; w.KC = (int32_t)(S.kernel == Kernel::Direct ? S.KS : S.KC);
+        S.n_macro = (S.total_ticks + w.KC * kRec - 1) / (w.KC * kRec);
+        w.exports = export_series; w.n_export = (int32_t)P->n_export;
+        w.rec = P->d_ring; w.rec_chunks = Div32((uint32_t)S.rec_chunks);
+        w.n_macro = (int32_t)S.n_macro; w.total = (int32_t)S.total;
+        w.has_lat = S.has_in ? 1 : 0; w.nsub = Div32((uint32_t)nsub); w.inv_nsub = 1.0 / (double)nsub;
+    }
     if (S.kernel == Kernel::Direct) {
         if (io.uh_kernel || io.runoff || (!io.dev_out && !io.dev_out32) || (mode == Mode::Unit && (io.dev_in32 || P->n_ghost > 0 || P->n_export > 0)) || nsub > kDirectMaxSub ||
-            (io.dev_out32 && (io.out_factor < 1 || (S.KC * kRec) % io.out_factor != 0 || T % io.out_factor != 0))) {
-            S.open = false;
+            (io.dev_out32 && (io.out_factor < 1 || (S.KC * kRec) % io.out_factor != 0 || T % io.out_factor != 0)))
             return fail(RR_E_STATE, "route: the direct row path was chosen for a call it does not take");      // (choose_schedule: dev_rows / out32)
-        }
         const rr::TilePlan &TP = P->dp.skel;
         const int64_t K = S.KC * kRec;
         S.n_tasks = (S.T + K - 1) / K;
-        S.n_macro = (S.total_ticks + S.KS * kRec - 1) / (S.KS * kRec);      // of the skeleton's launches
         S.n_diags = TP.n_tiles > 0 ? S.n_macro + TP.n_levels - 1 : 0;
         S.n_in_batches = (S.total + 14) / kRecRows + 1;      // of the boundary series (if any)
         S.n_out_batches = TP.np > 0 ? (S.total + kRecRows - 1) / kRecRows : 0;
-        S.export_skew = 0; S.export_lanes = S.export_skel = false;
         for (int32_t i : P->export_reach) {
             if (!P->dp.big[i]) { S.export_lanes = true; continue; }
             S.export_skel = true;
@@ -778,44 +797,27 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         da.rec = P->d_ring; da.rec_chunks = (uint32_t)std::max<int64_t>(1, S.rec_chunks); da.np = (int32_t)TP.np;
         da.K = (int32_t)K; da.total = (int32_t)S.T;
         da.exports = export_series; da.n_export = (int32_t)P->n_export;
-        TileArgs &w = S.ta;      // the skeleton's k_tile launches
-        w.tiles = P->d_ktmeta; w.pos = P->d_kpmeta; w.coef = P->d_kcoef;
-        w.sq = P->d_ksq; w.ss = P->d_kss; w.si = P->d_ksi; w.sqch = P->d_ksqch;
-        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KS;
     }
     if (S.kernel == Kernel::Tile) {
         const rr::TilePlan &TP = P->tp;
         const int64_t K = S.KC * kRec;
-        S.n_macro = (S.total_ticks + K - 1) / K;
         S.n_diags = S.n_macro + TP.n_levels - 1;
         S.n_in_batches = (S.total + 14) / kRecRows + 1;      // of the lateral rows (if any) and of the boundary series (if any)
         S.n_out_batches = (S.total + kRecRows - 1) / kRecRows;
         // external boundary reaches: a ghost in a tile of level l at lag L is read for sub-steps below (diag - l + 1) K - L,
         // an export reach there has produced the sub-steps below (diag - l) K - L
-        S.export_skew = 0;
         S.ghost_slack = P->ghost_reach.empty() ? 0 : S.total_ticks + (int64_t)TP.n_levels * K;
         for (int32_t i : P->ghost_reach) { const int32_t p = TP.inv[i]; S.ghost_slack = std::min<int64_t>(S.ghost_slack, (int64_t)TP.tile_level[TP.tile_of[p]] * K + (TP.lag[p] & kLagMask)); }
         for (int32_t i : P->export_reach) { const int32_t p = TP.inv[i]; S.export_skew = std::max<int64_t>(S.export_skew, (int64_t)TP.tile_level[TP.tile_of[p]] * K + (TP.lag[p] & kLagMask)); }
-        TileArgs &w = S.ta;
-        w.tiles = P->d_tmeta; w.pos = P->d_pmeta; w.coef = P->d_coef;
-        w.sq = P->d_sq; w.ss = P->d_ss; w.si = P->d_si; w.sqch = P->d_sqch;
-        w.np = (int32_t)TP.np; w.KC = (int32_t)S.KC;
         // headwaters routed by the in-pass: the short tick of a single-member call (launch_tile_diag); RapidMuskingum fed by lateral rows
         // has k_rec_in route them, UnitMuskingum's are final as any in-pass writes them (discharge = lateral inflow)
         S.hw = P->hw_inpass && P->lean_enabled && nsub == 1 && S.members == 0 &&
                (mode == Mode::Unit || (mode == Mode::Rapid && !io.runoff && !io.uh_kernel));
         if (S.members > 0) {      // an ensemble: one ring per member, the members' carried state np apart (k_tile<..., ENS>)
-            if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->d_ring.count()) { S.open = false; return fail(RR_E_STATE, "route: the ensemble was not reserved"); }
+            if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->d_ring.count()) return fail(RR_E_STATE, "route: the ensemble was not reserved");
             S.ring_stride = S.rec_chunks * kRec * TP.np;
-            w.sq = P->d_esq; w.ss = P->d_ess; w.si = P->d_esi; w.sqch = nullptr;
+            S.ta.sq = P->d_esq; S.ta.ss = P->d_ess; S.ta.si = P->d_esi; S.ta.sqch = nullptr;
         }
-    }
-    if (S.kernel != Kernel::Tick) {      // the rest of the k_tile launches' arguments, the plan's tiles' or the skeleton's
-        TileArgs &w = S.ta;
-        w.exports = export_series; w.n_export = (int32_t)P->n_export;
-        w.rec = P->d_ring; w.rec_chunks = Div32((uint32_t)S.rec_chunks);
-        w.n_macro = (int32_t)S.n_macro; w.total = (int32_t)S.total;
-        w.has_lat = S.has_in ? 1 : 0; w.nsub = Div32((uint32_t)nsub); w.inv_nsub = 1.0 / (double)nsub;
     }
     if (getenv("RR_VERBOSE") && S.kernel == Kernel::Direct)
         fprintf(stderr, "rr: n=%lld T=%lld direct rows: K=%lld tiles=%d window=%d holes=%lld outlets=%lld; skeleton: positions=%lld tiles=%d levels=%d ring_chunks=%lld (%.1f GB)\n",
@@ -831,11 +833,9 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
         // outlet-most reaches have passed them
         const int64_t lag_rows = (dmax + nsub - 1) / nsub;
         S.ring_rows = S.in_place ? 0 : std::min<int64_t>(T, lag_rows + 2 * C + 2);
-        if (S.ring_rows > 0xFFFFFFFFLL || T > 0x7FFFFFFFLL) { S.open = false; return fail(RR_E_INVALID, "route: too many time rows"); }
-        if (S.ring_rows * n > P->d_ring.count() || (!S.in_place && C * n > P->d_mrows.count()) || (host_io && C * n > P->d_stage.count())) {      // prepare_call sized them
-            S.open = false;
+        if (S.ring_rows > 0xFFFFFFFFLL || T > 0x7FFFFFFFLL) return fail(RR_E_INVALID, "route: too many time rows");
+        if (S.ring_rows * n > P->d_ring.count() || (!S.in_place && C * n > P->d_mrows.count()) || (host_io && C * n > P->d_stage.count()))      // prepare_call sized them
             return fail(RR_E_STATE, "route: work rows of the streaming kernel were not reserved");
-        }
         TickArgs &a = S.a;
         a.child_ptr = P->d_child_ptr; a.lag = P->d_lag; a.w = P->d_w; a.c2 = P->d_c2; a.c3 = P->d_c3; a.c4 = P->d_c4;
         a.c1row = P->weights_uniform ? P->d_c1row_h : nullptr;
@@ -854,9 +854,25 @@ int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
     if (S.kernel == Kernel::Tile && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_diags / 4 + 1);     // every fourth launch
     if (S.kernel == Kernel::Direct && S.max_samples > 0) S.max_samples = (size_t)std::min<int64_t>(4096, S.n_tasks);            // every direct launch
     S.max_samples = std::min(S.max_samples, P->ev.size() / 2);      // events are made by rr_plan_reserve, never here
-    if (!P->ev_first) { S.open = false; return fail(RR_E_STATE, "route: the plan's events were not reserved"); }
+    if (!P->ev_first) return fail(RR_E_STATE, "route: the plan's events were not reserved");
     HIPCHK(hipEventRecord(P->ev_first, stream));
     return RR_OK;
+}
+
+// Opens a routing call on the plan: open exactly when session_setup set all of it up.
+int session_begin(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io, hipStream_t stream,
+                  const double *ghost_series, double *export_series)
+{
+    if (P->ses.open) return fail(RR_E_STATE, "a routing call is already open on this plan (rr_stream_end it first)");
+    const int rc = session_setup(P, mode, T, nsub, io, stream, ghost_series, export_series);
+    P->ses.open = rc == RR_OK;
+    return rc;
+}
+
+// A skeleton position's carried value `state` (TileSet::sq or ::sqch) back into the params-order array the lanes kept.
+void launch_skel_state_out(const TileSet &ks, double *dst, const DevBuf<double> &state, hipStream_t stream)
+{
+    if (ks.tp->np > 0) hipLaunchKernelGGL(k_skel_state_out, grid1(ks.tp->np), dim3(kBlock), 0, stream, dst, (const double *)state, ks.perm.get(), ks.pmeta.get(), (int32_t)ks.tp->np);
 }
 
 // params order <-> engine order through the two-phase tiled permutation (k_perm_a / k_perm_b); mrows holds nrows x n intermediate values
@@ -927,6 +943,14 @@ inline bool tick_window(const rr::HostPlan &H, int64_t tau, int64_t total, int64
     return p_hi > p_lo;
 }
 
+typedef void (*tick_unit_kernel_t)(const UnitTickArgs);
+typedef void (*tick_kernel_t)(const TickArgs);
+tick_unit_kernel_t tick_unit_kernel(bool one) { return one ? (tick_unit_kernel_t)k_tick_unit<true> : (tick_unit_kernel_t)k_tick_unit<false>; }
+tick_kernel_t tick_kernel(bool lat, bool one)      // lat: RapidMuskingum's lateral term; one: one sub-step per row
+{
+    return lat ? (one ? (tick_kernel_t)k_tick<true, true> : (tick_kernel_t)k_tick<true, false>) : (one ? (tick_kernel_t)k_tick<false, true> : (tick_kernel_t)k_tick<false, false>);
+}
+
 int session_launch_tick(rr_plan *P, int64_t tau)
 {
     Session &S = P->ses;
@@ -952,14 +976,9 @@ int session_launch_tick(rr_plan *P, int64_t tau)
         ua.t = a; ua.hw_children = P->d_hwc; ua.qch = P->d_qch;
         ua.a2 = P->unit_general ? P->d_a2 : nullptr; ua.c1own = P->d_c1own;
         if (P->unit_general) { ua.t.c1row = nullptr; ua.zc = P->d_z + (tau % 3) * n; ua.za = P->d_z + ((tau + 2) % 3) * n; }
-        if (one) hipLaunchKernelGGL(k_tick_unit<true>, g, dim3(kBlock), 0, S.stream, ua);
-        else hipLaunchKernelGGL(k_tick_unit<false>, g, dim3(kBlock), 0, S.stream, ua);
-    } else if (S.mode == Mode::Rapid) {
-        if (one) hipLaunchKernelGGL((k_tick<true, true>), g, dim3(kBlock), 0, S.stream, a);
-        else hipLaunchKernelGGL((k_tick<true, false>), g, dim3(kBlock), 0, S.stream, a);
+        hipLaunchKernelGGL(tick_unit_kernel(one), g, dim3(kBlock), 0, S.stream, ua);
     } else {
-        if (one) hipLaunchKernelGGL((k_tick<false, true>), g, dim3(kBlock), 0, S.stream, a);
-        else hipLaunchKernelGGL((k_tick<false, false>), g, dim3(kBlock), 0, S.stream, a);
+        hipLaunchKernelGGL(tick_kernel(S.mode == Mode::Rapid, one), g, dim3(kBlock), 0, S.stream, a);
     }
     if (S.bracket_open) {
         S.bracket_reaches += p_hi - p_lo;
@@ -1000,26 +1019,13 @@ tile_kernel_t tile_ens_kernel(bool sub)
     return sub ? (tile_kernel_t)k_tile<T, false, true, false, false, true> : (tile_kernel_t)k_tile<T, false, false, false, false, true>;
 }
 
-// An ensemble's launch (k_tile<..., ENS>): the tasks of every member, member on the grid's second dimension.  The workgroups of one member
-// walk its tiles as k_tile's do; together the members' take the slots one member's would (fewer tiles each: the card fills with
-// (tile, member) tasks however few tiles the network has).
-void launch_tile_diag_ens(rr_plan *P, const TileArgs &w, int64_t tiles)
-{
-    Session &S = P->ses;
-    const int64_t slots = (int64_t)P->cu_count * (1024 / kTileThreads);
-    const dim3 g((unsigned)std::min<int64_t>(tiles, std::max<int64_t>(1, (slots + S.members - 1) / S.members)), (unsigned)S.members);
-    const size_t lds_bytes = tile_lds_bytes(kTileThreads);
-    TileArgs e = w;      // (member m's ring: chunks [m C, (m + 1) C); its state: positions [m np, (m + 1) np))
-    e.tile_filter = 0; e.coef = P->d_coef;
-    hipLaunchKernelGGL(tile_ens_kernel(S.nsub > 1), g, dim3((unsigned)kTileThreads), lds_bytes, S.stream, e);
-}
-
 // Launch d of the time-tiled schedule: the tasks (tile, macro-chunk d - level) of every tile whose macro-chunk exists.
 // Tiles are stored by level, so they are one contiguous range; a tile with no active position returns at once.
-// TP / w / wide tiles: the plan's own tiles, or the skeleton of the direct row path (its levels start at 1).
-int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_wide, const double *coef, const double *coef_unit, int64_t d, bool sampled)
+// ts: the plan's own tiles, or the skeleton of the direct row path (its levels start at 1); coef_unit: the coefficients of UnitMuskingum's short tick.
+int launch_tile_diag(rr_plan *P, const TileSet &ts, TileArgs &w, const double *coef_unit, int64_t d, bool sampled)
 {
     Session &S = P->ses;
+    const rr::TilePlan &TP = *ts.tp;
     const int64_t l_lo = std::max<int64_t>(0, d - (S.n_macro - 1)), l_hi = std::min<int64_t>(TP.n_levels - 1, d);
     if (l_hi < l_lo) return RR_OK;
     int64_t t_lo = TP.level_start[l_lo], t_hi = TP.level_start[l_hi + 1];
@@ -1047,10 +1053,14 @@ int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_
     const bool unit = S.mode == Mode::Unit;
     const bool lean = S.nsub == 1 && P->lean_enabled;      // every router's default (dt_routing = dt_runoff); sub-steps keep the general tick
     if (S.members > 0) {
-        launch_tile_diag_ens(P, w, t_hi - t_lo);
+        // An ensemble (k_tile<..., ENS>): the tasks of every member, member on the grid's second dimension.  The workgroups of one member walk its tiles as k_tile's do;
+        // together the members' take the slots one member's would (fewer tiles each: the card fills with (tile, member) tasks however few tiles the network has).
+        const dim3 ge((unsigned)std::min<int64_t>(t_hi - t_lo, std::max<int64_t>(1, ((int64_t)P->cu_count * (1024 / kTileThreads) + S.members - 1) / S.members)), (unsigned)S.members);
+        w.tile_filter = 0; w.coef = ts.coef;      // (member m's ring: chunks [m C, (m + 1) C); its state: positions [m np, (m + 1) np))
+        hipLaunchKernelGGL(tile_ens_kernel(S.nsub > 1), ge, dim3((unsigned)kTileThreads), tile_lds_bytes(kTileThreads), S.stream, w);
     } else {
         w.tile_filter = lean ? 1 : 0;
-        w.coef = (lean && unit) ? coef_unit : coef;
+        w.coef = (lean && unit) ? coef_unit : ts.coef.get();
         const int4 *const pos = w.pos;
         if (lean && S.hw) {      // (S.hw: the plan's own tiles) the in-pass headwaters are published, not stored: their flag and, RapidMuskingum, zero coefficients
             w.pos = P->d_pmeta_hw;
@@ -1058,8 +1068,8 @@ int launch_tile_diag(rr_plan *P, const rr::TilePlan &TP, TileArgs &w, int32_t n_
         }
         hipLaunchKernelGGL(tile_kernel(unit, S.nsub > 1, lean, S.mode == Mode::Muskingum), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
         w.pos = pos;      // (no in-pass headwater in a tile the general kernel takes)
-        if (lean && n_wide > 0) {
-            w.tile_filter = 2; w.coef = coef;
+        if (lean && ts.n_wide > 0) {
+            w.tile_filter = 2; w.coef = ts.coef;
             hipLaunchKernelGGL(tile_kernel(unit, false, false), g, dim3((unsigned)P->wave_threads), lds_bytes, S.stream, w);
         }
     }
@@ -1088,11 +1098,17 @@ bool tile_diag_launches(const rr_plan *P, const rr::TilePlan &TP, int64_t d)
     return l_hi >= l_lo && TP.level_start[l_hi + 1] > TP.level_start[l_lo];
 }
 
-int session_launch_diag(rr_plan *P, int64_t d)
+// What every record pass of the open call hands its kernel, whichever columns it is over: the ring and its positions, the call's length,
+// the float32 rows' format.  The passes add their columns (n, colmeta, cols), their rows and what only they have.
+RecPermArgs rec_args(const rr_plan *P, int64_t batch)
 {
-    int rc = launch_tile_diag(P, P->tp, P->ses.ta, P->n_wide_tiles, P->d_coef, P->d_coef_unit, d, true);
-    ++P->prof_launches;
-    return rc;
+    const Session &S = P->ses;
+    RecPermArgs ra{};
+    ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
+    ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.np = tiles_of(P, S.kernel).tp->np;
+    ra.T = S.T; ra.total = S.total; ra.batch = batch; ra.nsub = Div32((uint32_t)S.nsub);
+    ra.factor = Div32((uint32_t)std::max<int64_t>(1, S.io.out_factor));
+    return ra;
 }
 
 // Boundary inflow of a partitioned network: the ghost series (total sub-steps x ghosts, row = sub-step) is a matrix of
@@ -1100,13 +1116,11 @@ int session_launch_diag(rr_plan *P, int64_t d)
 void launch_ghost_permute(rr_plan *P, int64_t batch)
 {
     Session &S = P->ses;
-    RecPermArgs ra{};
-    ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
+    RecPermArgs ra = rec_args(P, batch);
+    ra.T = S.total; ra.nsub = Div32(1u);      // a row is a sub-step
     // (direct row path: the ghosts' records are those of the skeleton's positions that mirror them)
-    ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = P->n_ghost; ra.np = S.kernel == Kernel::Direct ? P->dp.skel.np : P->tp.np; ra.T = S.total; ra.total = S.total;
-    ra.batch = batch; ra.nsub = Div32(1u); ra.colmeta = S.kernel == Kernel::Direct ? P->d_kghostmeta : P->d_ghostmeta; ra.scale = nullptr;
+    ra.n = P->n_ghost; ra.colmeta = S.kernel == Kernel::Direct ? P->d_kghostmeta : P->d_ghostmeta;
     ra.rows = RowView{const_cast<double *>(S.ghost_series), P->n_ghost, 0, (uint32_t)S.total};
-    ra.factor = Div32(1u);
     hipLaunchKernelGGL(k_rec_in<false>, dim3((unsigned)((P->n_ghost + kRecInCols - 1) / kRecInCols)), dim3(kRecInThreads), 0, rec_stream(P), ra);
 }
 
@@ -1125,17 +1139,33 @@ rec_in_uh_t rec_in_uh_kernel(bool sub, int64_t n_ks, int batches, bool in32 = fa
 #undef RR_UHIN_IN
 }
 
-// The out-pass k_rec_out<SUB, F32> over `cols` columns (the plan's, or the holes' of the direct row path).
-void launch_rec_out(const RecPermArgs &ra, bool sub, int64_t cols, hipStream_t st)
+// The record passes' forms.  (The casts settle each form where it stands: kernels lie in the code object in the order they are first named.)
+typedef void (*rec_kernel_t)(const RecPermArgs);
+typedef void (*rec_ens_kernel_t)(const RecEnsArgs);
+typedef void (*rec_in_runoff_t)(const RecPermArgs, const RunoffArgs);
+rec_kernel_t rec_out_kernel(bool sub, bool f32)
 {
-    const dim3 g((unsigned)((cols + kRecOutCols - 1) / kRecOutCols));
-    if (ra.rows32) {
-        if (sub) hipLaunchKernelGGL((k_rec_out<true, true>), g, dim3(kRecOutThreads), 0, st, ra);
-        else hipLaunchKernelGGL((k_rec_out<false, true>), g, dim3(kRecOutThreads), 0, st, ra);
-    } else {
-        if (sub) hipLaunchKernelGGL((k_rec_out<true, false>), g, dim3(kRecOutThreads), 0, st, ra);
-        else hipLaunchKernelGGL((k_rec_out<false, false>), g, dim3(kRecOutThreads), 0, st, ra);
-    }
+    return f32 ? (sub ? (rec_kernel_t)k_rec_out<true, true> : (rec_kernel_t)k_rec_out<false, true>) : (sub ? (rec_kernel_t)k_rec_out<true, false> : (rec_kernel_t)k_rec_out<false, false>);
+}
+rec_ens_kernel_t rec_in_ens_kernel(bool sub, bool in32)      // member-batched
+{
+    return in32 ? (sub ? (rec_ens_kernel_t)k_rec_in<true, true, true> : (rec_ens_kernel_t)k_rec_in<false, true, true>) : (sub ? (rec_ens_kernel_t)k_rec_in<true, false, true> : (rec_ens_kernel_t)k_rec_in<false, false, true>);
+}
+rec_ens_kernel_t rec_out_ens_kernel(bool sub, bool f32)
+{
+    return f32 ? (sub ? (rec_ens_kernel_t)k_rec_out<true, true, true> : (rec_ens_kernel_t)k_rec_out<false, true, true>) : (sub ? (rec_ens_kernel_t)k_rec_out<true, false, true> : (rec_ens_kernel_t)k_rec_out<false, false, true>);
+}
+rec_in_runoff_t rec_in_runoff_kernel(bool f32) { return f32 ? (rec_in_runoff_t)k_rec_in_runoff<float> : (rec_in_runoff_t)k_rec_in_runoff<double>; }
+rec_kernel_t rec_in_kernel(bool sub, bool in32, bool hw)      // hw (the in-pass routes the flagged headwaters): only with one sub-step per row
+{
+    if (in32) return sub ? (rec_kernel_t)k_rec_in<true, true> : (hw ? (rec_kernel_t)k_rec_in<false, true, false, true> : (rec_kernel_t)k_rec_in<false, true>);
+    return sub ? (rec_kernel_t)k_rec_in<true> : (hw ? (rec_kernel_t)k_rec_in<false, false, false, true> : (rec_kernel_t)k_rec_in<false>);
+}
+
+// The out-pass over ra.n columns (the plan's, or the holes' of the direct row path).
+void launch_rec_out(const RecPermArgs &ra, bool sub, hipStream_t st)
+{
+    hipLaunchKernelGGL(rec_out_kernel(sub, ra.rows32 != nullptr), dim3((unsigned)((ra.n + kRecOutCols - 1) / kRecOutCols)), dim3(kRecOutThreads), 0, st, ra);
 }
 
 // `count` batches from `batch` on (session_advance_tile): up to Session::rec_nb for k_rec_in / k_rec_out, up to 2 for the fused
@@ -1144,18 +1174,12 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
 {
     Session &S = P->ses;
     const int64_t n = P->h.n;
-    RecPermArgs ra{};
+    RecPermArgs ra = rec_args(P, batch);
     ra.batches = count;
-    ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
-    ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = n; ra.np = P->tp.np; ra.T = S.T; ra.total = S.total; ra.batch = batch;
-    ra.nsub = Div32((uint32_t)S.nsub);
-    ra.colmeta = P->d_colmeta;
+    ra.n = n; ra.colmeta = P->d_colmeta;
     ra.scale = (in && S.mode == Mode::Rapid) ? P->d_c4_params : nullptr;
-    ra.rows = in ? RowView{const_cast<double *>(S.io.dev_in), n, 0, (uint32_t)S.io.rows_in}
-                 : RowView{S.io.dev_out, n, 0, (uint32_t)std::max<int64_t>(1, S.io.rows_out)};
-    ra.rows32 = in ? nullptr : S.io.dev_out32;
-    ra.rows_in32 = in ? S.io.dev_in32 : nullptr;
-    ra.factor = Div32((uint32_t)std::max<int64_t>(1, S.io.out_factor));
+    if (in) { ra.rows = RowView{const_cast<double *>(S.io.dev_in), n, 0, (uint32_t)S.io.rows_in}; ra.rows_in32 = S.io.dev_in32; }
+    else { ra.rows = RowView{S.io.dev_out, n, 0, (uint32_t)std::max<int64_t>(1, S.io.rows_out)}; ra.rows32 = S.io.dev_out32; }
     ra.clamp = S.nsub > 1 ? 0 : (S.mode == Mode::Unit ? 2 : 1);
     // The out-pass walks its column tiles in XCD-contiguous order (xcd_swizzle): where the row pitch is not a whole number
     // of 128-byte lines neighbouring tiles write parts of the same lines, and on one XCD those meet in its L2 (1.25M-reach
@@ -1164,51 +1188,38 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     ra.swizzle = in ? 0 : 1;
     // one column tile per workgroup, dispatched in address order: a persistent grid with the next tile's loads in flight was no
     // faster (427 / 469 us per 128 rows against 419 / 434-448 at 1M reaches; a plain copy shows the same, profiles/r03_hbm_probe_*.txt)
-    const dim3 gp((unsigned)((n + kRecInCols - 1) / kRecInCols));      // (the in-pass's; launch_rec_out has its own)
-    const bool sub = S.nsub > 1;
+    static_assert(kRecInCols == kRecOutCols && kRecInThreads == kRecOutThreads, "one grid for the member-batched in- and out-pass");
+    const unsigned tiles = (unsigned)((n + kRecInCols - 1) / kRecInCols);
+    const bool sub = S.nsub > 1, in32 = ra.rows_in32 != nullptr;
     const bool hw = in && S.hw && S.mode == Mode::Rapid;      // k_rec_in<..., HW>: the flagged columns leave as discharge
     if (hw) { ra.hw_coef = P->d_hwcoef; ra.hw_carry = P->d_hwq; }
     hipStream_t st = rec_stream(P);
     const int aux = aux_begin(P, in ? 0 : 1, st);
     if (S.members > 0) {      // an ensemble: every member's rows in one launch, member on the grid's second dimension
         const RecEnsArgs e{ra, S.ring_stride, in ? S.io.in_pitch : S.io.out_pitch};      // (in32 / out32 rows: the pitch counts float32 elements)
-        const dim3 ge((unsigned)((n + kRecInCols - 1) / kRecInCols), (unsigned)S.members);
-        if (in && ra.rows_in32) {
-            if (sub) hipLaunchKernelGGL((k_rec_in<true, true, true>), ge, dim3(kRecInThreads), 0, st, e);
-            else hipLaunchKernelGGL((k_rec_in<false, true, true>), ge, dim3(kRecInThreads), 0, st, e);
-        } else if (in) {
-            if (sub) hipLaunchKernelGGL((k_rec_in<true, false, true>), ge, dim3(kRecInThreads), 0, st, e);
-            else hipLaunchKernelGGL((k_rec_in<false, false, true>), ge, dim3(kRecInThreads), 0, st, e);
-        } else {
-            const dim3 go((unsigned)((n + kRecOutCols - 1) / kRecOutCols), (unsigned)S.members);
-            if (ra.rows32) {
-                if (sub) hipLaunchKernelGGL((k_rec_out<true, true, true>), go, dim3(kRecOutThreads), 0, st, e);
-                else hipLaunchKernelGGL((k_rec_out<false, true, true>), go, dim3(kRecOutThreads), 0, st, e);
-            } else {
-                if (sub) hipLaunchKernelGGL((k_rec_out<true, false, true>), go, dim3(kRecOutThreads), 0, st, e);
-                else hipLaunchKernelGGL((k_rec_out<false, false, true>), go, dim3(kRecOutThreads), 0, st, e);
-            }
-        }
-    } else if (in && S.io.runoff) {
+        hipLaunchKernelGGL(in ? rec_in_ens_kernel(sub, in32) : rec_out_ens_kernel(sub, ra.rows32 != nullptr), dim3(tiles, (unsigned)S.members), dim3(kRecInThreads), 0, st, e);
+    } else if (!in) {
+        launch_rec_out(ra, sub, st);
+    } else if (S.io.runoff) {
         const dim3 gr((unsigned)((n + kRunoffInThreads - 1) / kRunoffInThreads), (unsigned)kRecBatch);
-        if (S.io.runoff->is_f32) hipLaunchKernelGGL(k_rec_in_runoff<float>, gr, dim3(kRunoffInThreads), 0, st, ra, *S.io.runoff);
-        else hipLaunchKernelGGL(k_rec_in_runoff<double>, gr, dim3(kRunoffInThreads), 0, st, ra, *S.io.runoff);
-    } else if (in && S.io.uh_kernel) {
+        hipLaunchKernelGGL(rec_in_runoff_kernel(S.io.runoff->is_f32), gr, dim3(kRunoffInThreads), 0, st, ra, *S.io.runoff);
+    } else if (S.io.uh_kernel) {
         UhArgs ua{S.io.uh_kernel, S.io.uh_state, (int32_t)S.io.uh_nks};
-        hipLaunchKernelGGL(rec_in_uh_kernel(sub, S.io.uh_nks, count, ra.rows_in32 != nullptr), dim3((unsigned)((n + kUhCols - 1) / kUhCols)), dim3(uh_threads(count)),
+        hipLaunchKernelGGL(rec_in_uh_kernel(sub, S.io.uh_nks, count, in32), dim3((unsigned)((n + kUhCols - 1) / kUhCols)), dim3(uh_threads(count)),
                            rec_in_uh_lds_bytes(uh_padded_taps(S.io.uh_nks), count), st, ra, ua);
-    } else if (in && ra.rows_in32) {
-        if (sub) hipLaunchKernelGGL((k_rec_in<true, true>), gp, dim3(kRecInThreads), 0, st, ra);
-        else if (hw) hipLaunchKernelGGL((k_rec_in<false, true, false, true>), gp, dim3(kRecInThreads), 0, st, ra);
-        else hipLaunchKernelGGL((k_rec_in<false, true>), gp, dim3(kRecInThreads), 0, st, ra);
-    } else if (in) {
-        if (sub) hipLaunchKernelGGL(k_rec_in<true>, gp, dim3(kRecInThreads), 0, st, ra);
-        else if (hw) hipLaunchKernelGGL((k_rec_in<false, false, false, true>), gp, dim3(kRecInThreads), 0, st, ra);
-        else hipLaunchKernelGGL(k_rec_in<false>, gp, dim3(kRecInThreads), 0, st, ra);
     } else {
-        launch_rec_out(ra, sub, n, st);
+        hipLaunchKernelGGL(rec_in_kernel(sub, in32, hw), dim3(tiles), dim3(kRecInThreads), 0, st, ra);
     }
     aux_end(P, aux, st);
+}
+
+// Whether the ring slots batch j of an in-pass writes are free: a slot is recycled only after every tick-row it can hold has left.  Batch j writes, for a position of lag L,
+// the records whose last tick-row lies in the batch -- chunks up to (R (j + 1) + L) / 16, R = kRecRows (the boundary in-pass: whole records, zeros past the call's end).
+// One ring revolution earlier that slot held the same position's tick-rows up to R (j + 1) - 16 rec_chunks + 15, whatever L is: those must have left.
+bool slot_free(const Session &S, int64_t j)
+{
+    const int64_t must_have_left = kRecRows * (j + 1) + kRec - kRec * S.rec_chunks;
+    return must_have_left <= 0 || S.ticks_stored >= std::min(S.total, must_have_left);
 }
 
 // Time-tiled schedule: batches of kRecRows (128) tick-rows become records as soon as their rows are there and their ring slots
@@ -1223,26 +1234,19 @@ int session_advance_tile(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, in
         // one batch of tick-rows -> records; a record slot is recycled only after every tick-row it can hold has left.
         // Lateral rows and boundary sub-steps (the ghost series of a partitioned network) advance separately: a ghost in a
         // tile of level l at lag L is first read (l K + L) ticks into the schedule, so the boundary may trail the rows.
-        // Batch j writes, for a position of lag L, the records whose last tick-row lies in the batch: chunks up to
-        // (R (j + 1) + L) / 16, R = kRecRows.  One ring revolution earlier that slot held the same position's tick-rows up to
-        // R (j + 1) - 16 rec_chunks + 15, whatever L is: those must have left.
-        auto slot_free = [&](int64_t j) {
-            const int64_t must_have_left = kRecRows * (j + 1) + kRec - kRec * S.rec_chunks;
-            return must_have_left <= 0 || S.ticks_stored >= std::min(S.total, must_have_left);
-        };
-        if (S.has_in && S.in_batches < S.n_in_batches && ticks_ready >= std::min(kRecRows * (S.in_batches + 1), S.total) && slot_free(S.in_batches)) {
+        if (S.has_in && S.in_batches < S.n_in_batches && ticks_ready >= std::min(kRecRows * (S.in_batches + 1), S.total) && slot_free(S, S.in_batches)) {
             // the next batches along while their rows and ring slots are there too (less to read per value): up to rec_nb for k_rec_in,
             // two for the fused convolution, one batch a launch for gridded runoff
             const int max_count = S.io.runoff ? 1 : (S.io.uh_kernel ? (P->uh_pairs ? 2 : 1) : (int)S.rec_nb);
             int count = 1;
             while (count < max_count && S.in_batches + count < S.n_in_batches &&
-                   ticks_ready >= std::min(kRecRows * (S.in_batches + count + 1), S.total) && slot_free(S.in_batches + count)) ++count;
+                   ticks_ready >= std::min(kRecRows * (S.in_batches + count + 1), S.total) && slot_free(S, S.in_batches + count)) ++count;
             launch_rec_permute(P, true, S.in_batches, count);
             S.in_batches += count;
             progressed = true;
         }
         if (P->n_ghost > 0 && S.ghost_batches < S.n_in_batches && (!S.has_in || S.ghost_batches < S.in_batches) &&      // after the lateral batch: that one writes zeros into the ghosts' records
-            ghost_ready >= std::min(kRecRows * (S.ghost_batches + 1), S.total) && slot_free(S.ghost_batches)) {
+            ghost_ready >= std::min(kRecRows * (S.ghost_batches + 1), S.total) && slot_free(S, S.ghost_batches)) {
             launch_ghost_permute(P, S.ghost_batches);
             ++S.ghost_batches;
             progressed = true;
@@ -1262,7 +1266,8 @@ int session_advance_tile(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, in
             // one ring revolution earlier (their chunks are at most (d + 1) KC - 1)
             const int64_t top = std::min(std::min(S.diag + 1, S.n_macro) * S.KC - 1, (S.total_ticks - 1) / kRec);      // (a task longer than what is left of the call -- RR_WAVE_K -- ends with the call's last chunk)
             if (top >= S.rec_chunks && S.ticks_stored < std::min(S.total, kRec * (top - S.rec_chunks + 1))) break;
-            int rc = session_launch_diag(P, S.diag);
+            int rc = launch_tile_diag(P, P->ts, S.ta, P->d_coef_unit, S.diag, true);
+            ++P->prof_launches;
             if (rc) return rc;
             ++S.diag; ++launched;
             progressed = true;
@@ -1314,11 +1319,6 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
     const int64_t dmax = P->h.depth - 1, levels = TP.n_levels, K = S.KC * kRec, Kt = K * S.nsub, KS = S.KS * kRec, per = Kt / KS, n = P->h.n;      // K rows = Kt ticks per direct task
     rows_ready = std::min(rows_ready, S.T);
     const bool skel = TP.n_tiles > 0, ghosts = skel && P->n_ghost > 0;
-    // a record slot is recycled only after every tick-row it can hold has left (the same rule as session_advance_tile's)
-    auto slot_free = [&](int64_t j) {      // (a batch of the boundary in-pass writes whole records up to tick-row 128 (j + 1) + lag, zeros past the call's end)
-        const int64_t must_have_left = kRecRows * (j + 1) + kRec - kRec * S.rec_chunks;
-        return must_have_left <= 0 || S.ticks_stored >= std::min(S.total, must_have_left);
-    };
     for (;;) {
         bool progressed = false;
         while (S.d_done < S.n_tasks) {
@@ -1332,7 +1332,7 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
             if (sample) HIPCHK(hipEventRecord(P->ev[2 * P->prof_brackets], S.stream));
             S.da.m = (int32_t)d;
             const dim3 g((unsigned)std::min<int64_t>(P->dp.n_tiles, (int64_t)P->cu_count));
-            hipLaunchKernelGGL(direct_kernel(S.io.dev_in32 != nullptr && S.has_in, S.da.out32 != nullptr, S.nsub > 1, S.mode == Mode::Unit ? 1 : 0), g, dim3(kDirectThreads), direct_lds_bytes(P->direct_window), S.stream, S.da);
+            hipLaunchKernelGGL(direct_kernel(S.io.dev_in32 != nullptr && S.has_in, S.da.out32 != nullptr, S.nsub > 1, S.mode == Mode::Unit), g, dim3(kDirectThreads), direct_lds_bytes(P->direct_window), S.stream, S.da);
             if (sample) {
                 HIPCHK(hipEventRecord(P->ev[2 * P->prof_brackets + 1], S.stream));
                 P->ev_reaches.push_back(n * (std::min((d + 1) * K, S.T) - d * K));
@@ -1350,7 +1350,7 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
         // 128 tick-rows at a time (k_rec_in's batches), never ahead of the rows the lanes have routed: the ring's slots up to there are free.
         while (ghosts && S.ghost_batches < S.n_in_batches) {
             const int64_t need = std::min(kRecRows * (S.ghost_batches + 1), S.total);
-            if (ghost_ready < need || need > ticks_routed || !slot_free(S.ghost_batches)) break;
+            if (ghost_ready < need || need > ticks_routed || !slot_free(S, S.ghost_batches)) break;
             launch_ghost_permute(P, S.ghost_batches);
             ++S.ghost_batches;
             progressed = true;
@@ -1364,7 +1364,7 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
             if (ghost_loaded < std::min(S.total, j * KS)) break;
             if (tile_diag_launches(P, TP, j)) {      // (an empty bracket would be counted as a launch of the skeleton)
                 const int aux = aux_begin(P, 2, S.stream);
-                int rc = launch_tile_diag(P, TP, S.ta, P->n_kwide, P->d_kcoef, P->d_kcoef, j, false);
+                int rc = launch_tile_diag(P, P->ks, S.ta, P->ks.coef, j, false);
                 aux_end(P, aux, S.stream);      // before rc is looked at: rr_plan_profile_aux reads both events of every sample
                 if (rc) return rc;
             }
@@ -1378,15 +1378,12 @@ int session_advance_direct(rr_plan *P, int64_t rows_ready, int64_t ghost_ready, 
             int64_t sk = S.diag >= S.n_diags ? S.total : (m_done >= 0 ? std::max<int64_t>(0, (m_done + 1) * KS - dmax) : 0);
             done = std::min(done, std::min(sk, S.total));
             while (S.out_batches < S.n_out_batches && done >= std::min(kRecRows * (S.out_batches + 1), S.total)) {
-                RecPermArgs ra{};
-                ra.in32_sel = P->in32_big_endian ? kSelSwap : kSelNative; ra.out32_sel = P->out32_big_endian ? kSelSwap : kSelNative;
-                ra.rec = P->d_ring; ra.rec_chunks = Div32((uint32_t)S.rec_chunks); ra.n = P->n_kholes; ra.np = TP.np; ra.T = S.T; ra.total = S.total;
-                ra.batch = S.out_batches; ra.nsub = Div32((uint32_t)S.nsub); ra.colmeta = P->d_kholemeta; ra.cols = P->d_kholecol; ra.scale = nullptr;
-                ra.rows = RowView{S.io.dev_out, n, 0, (uint32_t)std::max<int64_t>(1, S.io.rows_out)};
-                ra.rows32 = S.io.dev_out32;
-                ra.factor = Div32((uint32_t)std::max<int64_t>(1, S.io.out_factor)); ra.clamp = S.nsub > 1 ? 0 : 1; ra.swizzle = 0;
+                RecPermArgs ra = rec_args(P, S.out_batches);
+                ra.n = P->n_kholes; ra.colmeta = P->d_kholemeta; ra.cols = P->d_kholecol;
+                ra.rows = RowView{S.io.dev_out, n, 0, (uint32_t)std::max<int64_t>(1, S.io.rows_out)}; ra.rows32 = S.io.dev_out32;
+                ra.clamp = S.nsub > 1 ? 0 : 1;
                 const int aux = aux_begin(P, 3, S.stream);
-                if (P->n_kholes > 0) launch_rec_out(ra, S.nsub > 1, P->n_kholes, S.stream);
+                if (P->n_kholes > 0) launch_rec_out(ra, S.nsub > 1, S.stream);
                 aux_end(P, aux, S.stream);
                 ++S.out_batches;
                 S.ticks_stored = std::min(S.total, kRecRows * S.out_batches);
@@ -1508,12 +1505,12 @@ int launch_state_in(rr_plan *P, const double *d_q, hipStream_t stream)
     const int64_t n = P->h.n;
     if (P->sch.kernel != Kernel::Tick) {      // positions and ghosts as k_tile wants them (direct row path: the skeleton's; the lanes carry their discharge in params order)
         const bool d = P->sch.kernel == Kernel::Direct;
-        const int64_t np = d ? P->dp.skel.np : P->tp.np;
+        const TileSet &ts = tiles_of(P, P->sch.kernel);
+        const int64_t np = ts.tp->np;
         if (d) HIPCHK(hipMemcpyAsync(P->d_dq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));
         if (!d && P->hw_inpass) HIPCHK(hipMemcpyAsync(P->d_hwq, d_q, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream));      // k_rec_in's carry starts from the call's state
         if (np > 0)
-            hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, d ? P->d_ksq : P->d_sq, d ? P->d_kss : P->d_ss, d ? P->d_ksi : P->d_si, d_q,
-                               d ? P->d_kperm : P->d_tperm, d ? P->d_kpmeta : P->d_pmeta, (int32_t)np);
+            hipLaunchKernelGGL(k_tile_state_in, grid1(np), dim3(kBlock), 0, stream, ts.sq.get(), ts.ss.get(), ts.si.get(), d_q, ts.perm.get(), ts.pmeta.get(), (int32_t)np);
         return RR_OK;
     }
     hipLaunchKernelGGL(k_state_in, grid1(n), dim3(kBlock), 0, stream, P->d_x, P->d_x + n, P->d_x + 2 * n, d_q,
@@ -1526,12 +1523,11 @@ void launch_state_out(rr_plan *P, double *d_q, int64_t total, hipStream_t stream
     const int64_t n = P->h.n;
     if (P->sch.kernel == Kernel::Direct) {
         (void)hipMemcpyAsync(d_q, P->d_dq, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream);
-        const int64_t np = P->dp.skel.np;
-        if (np > 0) hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, d_q, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
+        launch_skel_state_out(P->ks, d_q, P->ks.sq, stream);
         return;
     }
     if (P->sch.kernel == Kernel::Tile) {
-        hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q, (const double *)P->d_sq, P->d_tinv,
+        hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q, (const double *)P->ts.sq, P->d_tinv,
                            (int32_t)n);
         return;
     }
@@ -1751,16 +1747,15 @@ int unit_state_in(rr_plan *P, const double *d_qch, const double *d_qfull, hipStr
     if (P->sch.kernel != Kernel::Tick) {
         // q_full / q_ch scattered to params order (zeros on headwaters: the direct row path's lanes carry them so), then gathered position by
         // position as k_tile<UNIT> wants them (on the direct row path: the skeleton's positions)
-        const bool d = P->sch.kernel == Kernel::Direct;
-        const int64_t np = d ? P->dp.skel.np : P->tp.np;
+        const TileSet &ts = tiles_of(P, P->sch.kernel);
+        const int64_t np = ts.tp->np;
         e0 = hipMemsetAsync(P->d_full, 0, n * sizeof(double), stream);
         if (e0 == hipSuccess) e0 = hipMemsetAsync(P->d_chan, 0, n * sizeof(double), stream);
         if (e0 == hipSuccess && ni > 0)
             hipLaunchKernelGGL(k_unit_scatter, grid1(ni), dim3(kBlock), 0, stream, P->d_full, P->d_chan, d_qfull, d_qch, P->d_inner_idx, (int32_t)ni);
         if (e0 == hipSuccess && np > 0)
-            hipLaunchKernelGGL(k_tile_unit_state_in, grid1(np), dim3(kBlock), 0, stream, d ? P->d_ksq : P->d_sq, d ? P->d_kss : P->d_ss, d ? P->d_ksi : P->d_si,
-                               d ? P->d_ksqch : P->d_sqch, (const double *)P->d_full, (const double *)P->d_chan, d ? P->d_kperm : P->d_tperm,
-                               d ? P->d_kpmeta : P->d_pmeta, (int32_t)np);
+            hipLaunchKernelGGL(k_tile_unit_state_in, grid1(np), dim3(kBlock), 0, stream, ts.sq.get(), ts.ss.get(), ts.si.get(), ts.sqch.get(),
+                               (const double *)P->d_full, (const double *)P->d_chan, ts.perm.get(), ts.pmeta.get(), (int32_t)np);
     } else {
         e0 = hipMemsetAsync(P->d_x, 0, 3 * n * sizeof(double), stream);
         if (e0 == hipSuccess && ni > 0)
@@ -1775,29 +1770,28 @@ void unit_state_out(rr_plan *P, double *d_qch, double *d_qfull, int64_t total, h
     const int64_t n = P->h.n, ni = (int64_t)P->h.inner_pos.size();
     if (ni == 0) return;
     if (P->sch.kernel == Kernel::Direct) {      // the skeleton's reaches back into the params-order arrays the lanes kept, then the inner reaches' pairs
-        const int64_t np = P->dp.skel.np;
-        if (np > 0) {
-            hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_full, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
-            hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_chan, (const double *)P->d_ksqch, P->d_kperm, P->d_kpmeta, (int32_t)np);
-        }
+        launch_skel_state_out(P->ks, P->d_full, P->ks.sq, stream);
+        launch_skel_state_out(P->ks, P->d_chan, P->ks.sqch, stream);
         hipLaunchKernelGGL(k_unit_gather, grid1(ni), dim3(kBlock), 0, stream, d_qch, d_qfull, (const double *)P->d_chan, (const double *)P->d_full, P->d_inner_idx, (int32_t)ni);
     } else if (P->sch.kernel == Kernel::Tile)
         hipLaunchKernelGGL(k_tile_unit_state_out, grid1(ni), dim3(kBlock), 0, stream, d_qch, d_qfull,
-                           (const double *)P->d_sq, (const double *)P->d_sqch, P->d_inner_idx, P->d_tinv, (int32_t)ni);
+                           (const double *)P->ts.sq, (const double *)P->ts.sqch, P->d_inner_idx, P->d_tinv, (int32_t)ni);
     else
         hipLaunchKernelGGL(k_unit_state_out, grid1(ni), dim3(kBlock), 0, stream, d_qch, d_qfull,
                            (const double *)P->d_x, n, (const double *)P->d_qch, P->d_lag, P->d_inner_pos, (int32_t)ni, total);
 }
 
 // Carry-over state of the unit-hydrograph convolution, in place, enqueued after every pass that reads the old one (same stream).
+template <typename TIn> using uh_tail_t = void (*)(const double *, double *, const TIn *, int64_t, int32_t, int64_t, uint32_t);
+template <typename TIn>
+uh_tail_t<TIn> uh_tail_kernel(int64_t n_ks)      // (0: any number of taps, from memory)
+{
+    return n_ks <= 16 ? (uh_tail_t<TIn>)k_uh_tail<16, TIn> : (n_ks <= 48 ? (uh_tail_t<TIn>)k_uh_tail<48, TIn> : (uh_tail_t<TIn>)k_uh_tail<0, TIn>);
+}
 template <typename TIn>
 void launch_uh_tail(const double *kernel, double *state, const TIn *rows, int64_t T, int64_t n_ks, int64_t n, hipStream_t stream, uint32_t sel)
 {
-    const dim3 gt((unsigned)((n + kUhTailThreads - 1) / kUhTailThreads));
-    const int32_t nks = (int32_t)n_ks;
-    if (nks <= 16) hipLaunchKernelGGL((k_uh_tail<16, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
-    else if (nks <= 48) hipLaunchKernelGGL((k_uh_tail<48, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
-    else hipLaunchKernelGGL((k_uh_tail<0, TIn>), gt, dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, nks, n, sel);
+    hipLaunchKernelGGL(uh_tail_kernel<TIn>(n_ks), dim3((unsigned)((n + kUhTailThreads - 1) / kUhTailThreads)), dim3(kUhTailThreads), 0, stream, kernel, state, rows, T, (int32_t)n_ks, n, sel);
 }
 
 template <typename TIn>
@@ -1826,10 +1820,9 @@ int unit_like(rr_plan *P, double *q_ch, double *q_full, const Rows &io_in, int64
     }
     if (!rc) rc = route_rows(P, Mode::Unit, T, nsub, io, stream);
     if (!rc && kernel == Kernel::Tile && d_q_final)      // every reach: a headwater's state is its last lateral inflow, an inner reach's q_full
-        hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q_final, (const double *)P->d_sq, P->d_tinv, (int32_t)n);
+        hipLaunchKernelGGL(k_tile_state_out, grid1(n), dim3(kBlock), 0, stream, d_q_final, (const double *)P->ts.sq, P->d_tinv, (int32_t)n);
     if (!rc && kernel == Kernel::Direct && d_q_final) {      // the lanes' columns hold exactly that; the skeleton's reaches join them
-        const int64_t np = P->dp.skel.np;
-        if (np > 0) hipLaunchKernelGGL(k_skel_state_out, grid1(np), dim3(kBlock), 0, stream, P->d_full, (const double *)P->d_ksq, P->d_kperm, P->d_kpmeta, (int32_t)np);
+        launch_skel_state_out(P->ks, P->d_full, P->ks.sq, stream);
         (void)hipMemcpyAsync(d_q_final, P->d_full, (size_t)n * sizeof(double), hipMemcpyDeviceToDevice, stream);
     }
     if (!rc && io.uh_kernel && uh_state_inout) {      // carry-over state of the fused convolution, after every batch has read the old one

@@ -421,3 +421,67 @@ def test_rows_between_a_file_and_the_device(tmp_path):
         engine.rows_upload(dev, cols * 4 - 4, path, head, cols * 4 + pad, cols * 4, rows)      # device pitch shorter than a row
     np.testing.assert_array_equal(dev.download(np.float32, (rows, cols))[:rows - 5], data[:rows - 5])      # (the failed calls left the device usable)
     dev.free()
+
+
+@pytest.mark.parametrize('name,env,kernel', [('forest', {'RR_WAVE': '0'}, 'tick'), ('forest', {'RR_WAVE': '1'}, 'tile'), ('direct', {}, 'direct')])
+def test_a_refused_stream_begin_leaves_no_call_open(monkeypatch, name, env, kernel):
+    """Every refusal session_begin gives a caller of a plan with boundary reaches -- no ghost series, no export series, a second begin
+    while a call is open -- leaves the plan as it was: the correct begin / advance / end that follows gives, bit for bit, the discharge,
+    export series and state a freshly made plan gives for the same call.  The 70-reach forest in tiles of 8 on the streaming and the
+    time-tiled kernel, the 300-reach post-order network on the direct row path (the networks and boundaries of test_gpu_devbuf)."""
+    from river_route_amd import _lib
+    from test_gpu_devbuf import network
+    for k in KNOBS + ('RR_DIRECT',):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setenv('RR_TILE_BLOCK', '8')      # (network() sets or clears it in os.environ: put back after the test)
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    indptr, indices, cf, ghosts, exports, _ = network(name)
+    n, T = indptr.size - 1, 40
+    q0, ql = 2.0 * synth.u01(3, np.arange(n)), synth.synth_qlateral(n, 0, T)
+    ghost = 1.0 + synth.u01(5, np.arange(T * len(ghosts[0]))).reshape(T, len(ghosts[0]))
+    d_ql, d_ghost = DeviceBuffer(ql.nbytes).upload(ql), DeviceBuffer(ghost.nbytes).upload(ghost)
+    d_q, d_out, d_exp = DeviceBuffer(n * 8), DeviceBuffer(ql.nbytes), DeviceBuffer(T * len(exports[0]) * 8)
+
+    def begin(plan, ghost_series=d_ghost, export_series=d_exp):
+        d_q.upload(q0)
+        d_out.upload(np.full((T, n), -1.0))
+        d_exp.upload(np.full((T, len(exports[0])), -1.0))
+        plan.stream_begin(d_q, d_ql, T, d_out, T, T, 1, ghost_series, export_series)
+
+    def finish(plan):
+        assert plan.stream_advance(T, T) == T
+        plan.stream_end(d_q)
+        assert plan.last_kernel() == kernel, plan.last_kernel()
+        return d_out.download(np.float64, (T, n)), d_exp.download(np.float64, (T, len(exports[0]))), d_q.download(np.float64, (n,))
+
+    def refused(call, code, words):
+        with pytest.raises(_lib.RRError) as e:
+            call()
+        assert e.value.code == code and words in e.value.message, (e.value.code, e.value.message)
+
+    def make():
+        plan = Plan(indptr, indices)
+        plan.set_coeffs(*cf)
+        plan.set_boundary(ghosts[0], exports[0])
+        return plan
+
+    with make() as fresh:
+        begin(fresh)
+        want = finish(fresh)
+    assert np.isfinite(want[0]).all() and (want[1] != -1.0).all()
+    with make() as plan:
+        def second_begin():      # the C entry point itself: Plan.stream_begin reserves first, and rr_plan_reserve has a refusal of its own
+            _lib.check(_lib.lib().rr_stream_begin(plan._h, 1, _lib.ptr(d_q), _lib.ptr(d_ql), T, _lib.ptr(d_out), T, T, 1, _lib.ptr(d_ghost), _lib.ptr(d_exp), None))
+        for what in ('ghost', 'export', 'open'):
+            if what == 'ghost':
+                refused(lambda: begin(plan, ghost_series=None), _lib.RR_E_INVALID, 'no ghost series')
+            if what == 'export':
+                refused(lambda: begin(plan, export_series=None), _lib.RR_E_INVALID, 'no export series')
+            begin(plan)
+            if what == 'open':
+                refused(second_begin, _lib.RR_E_STATE, 'already open')
+            for got, ref, label in zip(finish(plan), want, ('discharge', 'export series', 'q_t')):
+                np.testing.assert_array_equal(got.view(np.int64), ref.view(np.int64), err_msg=f'after the refusal "{what}": {label}')
+    for b in (d_ql, d_ghost, d_q, d_out, d_exp):
+        b.free()
