@@ -259,6 +259,27 @@ int rr_plan_reserve_ensemble(rr_plan *plan, int64_t members, int64_t T, int64_t 
 int rr_rapid_route_ensemble_dev(rr_plan *plan, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
                                 int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
                                 int64_t factor, int64_t T, int64_t nsub, void *stream);
+/* Parameter ensembles: the members of an ensemble call with a coefficient set each -- one basin, one forcing, `members` (k, x) sets: a
+ * generation of a population-based calibration, the samples of a sensitivity analysis.
+ * rr_plan_set_member_coeffs takes host arrays, as rr_plan_set_coeffs does: member m's lhs_off_data (n_edges values) at + m * lhs_pitch,
+ * its c2, c3 and c4_dt (n values each, params order) at + m * pitch.  It builds per member what rr_plan_set_coeffs builds for the
+ * time-tiled general tick -- {c1row, c2, c3} per position in tile order (zeros at tile ghosts) and c4dt in params order -- and keeps them
+ * on the device beside the plan's own coefficient set, which it does not touch: every other call on the plan computes what it did.  A
+ * later call replaces the tables.  RR_E_INVALID: members < 1 (or > 65535), a null array (c4_dt included), pitch < n, lhs_pitch < n_edges
+ * with more than one member; RR_E_UNSUPPORTED: a member with two tributaries of one reach at different weights (the message names the
+ * member; there is no streaming fallback here); RR_E_STATE: a routing call is open.
+ * rr_rapid_route_members_dev is rr_rapid_route_ensemble_dev, argument for argument, with member m routed by coefficient set m.
+ * lateral_member_pitch == 0: one forcing (T rows) shared by all members.  RR_E_STATE if fewer sets than `members` were set (the message
+ * names the rr_plan_set_member_coeffs call to make).  Work memory: rr_plan_reserve_ensemble's, which either setter allows; the plan needs
+ * no rr_plan_set_coeffs for this call.  Every member runs the general tick: member m's results are bit for bit those of
+ * rr_plan_set_coeffs(member m's arrays) + a one-member rr_rapid_route_ensemble_dev.  rr_plan_last_kernel: RR_KERNEL_TILE_ENSEMBLE. */
+int rr_plan_set_member_coeffs(rr_plan *plan, int64_t members,
+                              const double *lhs_off_data, int64_t lhs_pitch,   /* member m: n_edges values at + m * lhs_pitch */
+                              const double *c2, const double *c3, const double *c4_dt, int64_t pitch);   /* member m: n values at + m * pitch */
+int rr_rapid_route_members_dev(rr_plan *plan, int64_t members, double *q_t, int64_t q_pitch,
+                               const void *lateral, int lateral_is_f32, int64_t lateral_member_pitch,
+                               void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                               int64_t factor, int64_t T, int64_t nsub, void *stream);
 int rr_muskingum_route_f32_dev(rr_plan *plan, double *q_t, float *discharge32, int64_t num_output_steps,
                                int64_t num_routing_per_output, void *stream);
 int rr_unit_route_f32_dev(rr_plan *plan, double *q_ch, double *q_full, const double *convolved_lateral, int64_t conv_rows,

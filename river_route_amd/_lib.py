@@ -118,6 +118,8 @@ _SIGNATURES = {
     'rr_rapid_route_f32in_dev': (C.c_int, [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _i64, _i64, _vp]),
     'rr_plan_reserve_ensemble': (C.c_int, [_vp, _i64, _i64, _i64, C.c_int, _vp]),
     'rr_rapid_route_ensemble_dev': (C.c_int, [_vp, _i64, _vp, _i64, _vp, C.c_int, _i64, _vp, C.c_int, _i64, _i64, _i64, _i64, _vp]),
+    'rr_plan_set_member_coeffs': (C.c_int, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _i64]),
+    'rr_rapid_route_members_dev': (C.c_int, [_vp, _i64, _vp, _i64, _vp, C.c_int, _i64, _vp, C.c_int, _i64, _i64, _i64, _i64, _vp]),
     'rr_muskingum_route_f32_dev': (C.c_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     'rr_unit_route_f32_dev': (C.c_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _i64, _vp]),
     'rr_plan_set_boundary': (C.c_int, [_vp, _i64, _vp, _i64, _vp]),

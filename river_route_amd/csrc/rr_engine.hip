@@ -121,8 +121,8 @@ int rr_plan_create(int64_t n, const int32_t *csc_indptr, const int32_t *csc_indi
                 (void)hipGetLastError();
                 P->wave_enabled = false;
             }
-        for (int v = 0; v < 2; ++v)    // the same for the member-batched forms (ensembles)
-            if (hipFuncSetAttribute((const void *)tile_ens_kernel(v == 1), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(kTileThreads)) != hipSuccess) {
+        for (int v = 0; v < 4; ++v)    // the same for the member-batched forms (ensembles; v = 2, 3: with a coefficient set per member)
+            if (hipFuncSetAttribute((const void *)tile_ens_kernel((v & 1) != 0, v >= 2), hipFuncAttributeMaxDynamicSharedMemorySize, (int)tile_lds_bytes(kTileThreads)) != hipSuccess) {
                 (void)hipGetLastError();
                 P->ens_enabled = false;
             }
@@ -383,9 +383,10 @@ int rr_plan_reserve(rr_plan *P, int mode, int64_t T, int64_t nsub, int host_rows
 // ---- ensembles (rr_rapid_route_ensemble_dev) ----
 
 // Why an ensemble call of this shape does not get the time-tiled kernel, or NULL (record rings that do not fit: ensemble_member_cap).
-static const char *ensemble_unsupported(const rr_plan *P, int64_t T, int64_t nsub)
+// member_coeffs: the call routes the members' own coefficient sets, which have one weight per reach each (rr_plan_set_member_coeffs).
+static const char *ensemble_unsupported(const rr_plan *P, int64_t T, int64_t nsub, bool member_coeffs = false)
 {
-    if (!P->weights_uniform) return "per-edge weights (the time-tiled kernel keeps one upstream weight per reach)";
+    if (!member_coeffs && !P->weights_uniform) return "per-edge weights (the time-tiled kernel keeps one upstream weight per reach)";
     if (T * nsub < 32) return "fewer than 32 routing sub-steps (T x nsub) in a call";
     if (P->n_ghost > 0 || P->n_export > 0) return "the plan has boundary reaches (a partitioned network)";
     if (!P->tp.ok || !P->wave_enabled || !P->ens_enabled || P->wave_threads != kTileThreads || P->export_inside || P->tp.np >= (int64_t{1} << 25)) return "the network does not take the time-tiled kernel";
@@ -418,12 +419,14 @@ int rr_plan_reserve_ensemble(rr_plan *P, int64_t members, int64_t T, int64_t nsu
     int rc = need_device(P);
     if (rc) return rc;
     if (members < 1 || members > 65535 || T < 0 || nsub < 1) return fail(RR_E_INVALID, "rr_plan_reserve_ensemble: need 1 <= members <= 65535, T >= 0 and sub-steps >= 1");
-    if (!P->coeffs_set) return fail(RR_E_STATE, "rr_plan_reserve_ensemble before rr_plan_set_coeffs");
+    if (!P->coeffs_set && P->mc_sets == 0) return fail(RR_E_STATE, "rr_plan_reserve_ensemble before rr_plan_set_coeffs (or rr_plan_set_member_coeffs)");
     if (P->ses.open) return fail(RR_E_STATE, "rr_plan_reserve_ensemble: a routing call is open");
     if (info) for (int k = 0; k < 9; ++k) info[k] = 0;
     if (P->h.n == 0 || T == 0) return RR_OK;
-    if (const char *why = ensemble_unsupported(P, T, nsub)) return fail(RR_E_UNSUPPORTED, std::string("rr_plan_reserve_ensemble: ") + why);
-    const CallShape shape = ensemble_shape(members, T, nsub, (flags & RR_ROWS_F32_IN) != 0, (flags & RR_ROWS_F32_OUT) != 0, 1);
+    // (the work memory of a call is the same whichever coefficients it routes with: with member sets on the plan the reservation is theirs too)
+    if (const char *why = ensemble_unsupported(P, T, nsub, P->mc_sets > 0)) return fail(RR_E_UNSUPPORTED, std::string("rr_plan_reserve_ensemble: ") + why);
+    CallShape shape = ensemble_shape(members, T, nsub, (flags & RR_ROWS_F32_IN) != 0, (flags & RR_ROWS_F32_OUT) != 0, 1);
+    shape.member_coeffs = P->mc_sets > 0;
     const int64_t cap = ensemble_member_cap(P, shape);
     if (info) info[8] = cap;
     if (members > cap)
@@ -755,37 +758,43 @@ int rr_rapid_route_f32in_dev(rr_plan *P, double *q_t, const float *qlateral32, i
     return rapid_like(P, Mode::Rapid, q_t, io, T, nsub, (hipStream_t)stream, false, "rr_rapid_route_f32in_dev");
 }
 
-int rr_rapid_route_ensemble_dev(rr_plan *P, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
-                                int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
-                                int64_t factor, int64_t T, int64_t nsub, void *stream)
+// An ensemble call on the time-tiled kernel: with the plan's coefficients for every member (rr_rapid_route_ensemble_dev), or with the
+// members' own sets (member_coeffs: rr_rapid_route_members_dev, where a lateral pitch of 0 shares one forcing).  The caller has checked the plan.
+static int ensemble_route(rr_plan *P, const char *who, bool member_coeffs, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
+                          int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                          int64_t factor, int64_t T, int64_t nsub, void *stream)
 {
-    int rc = check_route_args(P, true, T, nsub);
-    if (rc) return rc;
+    const std::string name(who);
     const int64_t n = P->h.n;
-    if (members < 1 || members > 65535) return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: need 1 <= members <= 65535");
+    if (members < 1 || members > 65535) return fail(RR_E_INVALID, name + ": need 1 <= members <= 65535");
     if (n == 0 || T == 0) return RR_OK;
-    if (!q_t || !lateral || !discharge) return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: null array");
+    if (!q_t || !lateral || !discharge) return fail(RR_E_INVALID, name + ": null array");
     if (discharge_is_f32 && (factor < 1 || T % factor != 0))
-        return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: float32 output: the number of rows must be a multiple of factor >= 1");
+        return fail(RR_E_INVALID, name + ": float32 output: the number of rows must be a multiple of factor >= 1");
     const int64_t out_rows = discharge_is_f32 ? T / factor : T;
-    if (q_pitch < n || lateral_member_pitch < T * n || discharge_member_pitch < out_rows * n)
-        return fail(RR_E_INVALID, "rr_rapid_route_ensemble_dev: a pitch is shorter than a member (q_pitch >= n, lateral pitch >= T n, discharge pitch >= rows x n)");
-    if (const char *why = ensemble_unsupported(P, T, nsub)) return fail(RR_E_UNSUPPORTED, std::string("rr_rapid_route_ensemble_dev: ") + why);
+    const bool shared_lateral = member_coeffs && lateral_member_pitch == 0;
+    if (q_pitch < n || (!shared_lateral && lateral_member_pitch < T * n) || discharge_member_pitch < out_rows * n)
+        return fail(RR_E_INVALID, name + ": a pitch is shorter than a member (q_pitch >= n, lateral pitch >= T n" + (member_coeffs ? " or 0: one forcing for all" : "") +
+                                      ", discharge pitch >= rows x n)");
+    if (member_coeffs && members > P->mc_sets)
+        return fail(RR_E_STATE, name + ": " + std::to_string(members) + " members but " + std::to_string(P->mc_sets) + " coefficient sets: call rr_plan_set_member_coeffs(plan, " +
+                                    std::to_string(members) + ", ...) first");
+    if (const char *why = ensemble_unsupported(P, T, nsub, member_coeffs)) return fail(RR_E_UNSUPPORTED, name + ": " + why);
     Rows io;
     if (lateral_is_f32) io.dev_in32 = (const float *)lateral; else io.dev_in = (const double *)lateral;
     io.rows_in = T;
     if (discharge_is_f32) { io.dev_out32 = (float *)discharge; io.out_factor = factor; } else io.dev_out = (double *)discharge;
     io.rows_out = out_rows;
-    io.members = members; io.in_pitch = lateral_member_pitch; io.out_pitch = discharge_member_pitch;
+    io.members = members; io.in_pitch = lateral_member_pitch; io.out_pitch = discharge_member_pitch; io.member_coeffs = member_coeffs;
     const CallShape shape = call_shape(Mode::Rapid, T, nsub, io);
     if (members > ensemble_member_cap(P, shape))
-        return fail(RR_E_UNSUPPORTED, "rr_rapid_route_ensemble_dev: the record rings of " + std::to_string(members) + " members do not fit the card; route fewer per call "
+        return fail(RR_E_UNSUPPORTED, name + ": the record rings of " + std::to_string(members) + " members do not fit the card; route fewer per call "
                                       "(rr_plan_reserve_ensemble's info[8])");
-    rc = prepare_call(P, shape, "rr_rapid_route_ensemble_dev");
+    int rc = prepare_call(P, shape, who);
     if (rc) return rc;
     if (P->ens_cap < members)
         return fail(RR_E_STATE, "the carried state of " + std::to_string(members) + " members was not reserved: call rr_plan_reserve_ensemble(plan, " + std::to_string(members) +
-                                ", " + std::to_string(T) + ", " + std::to_string(nsub) + ", ...) first; rr_rapid_route_ensemble_dev only enqueues work");
+                                ", " + std::to_string(T) + ", " + std::to_string(nsub) + ", ...) first; " + name + " only enqueues work");
     const hipStream_t st = (hipStream_t)stream;
     const int64_t np = P->tp.np;
     hipLaunchKernelGGL(k_tile_state_in_ens, dim3((unsigned)((np + kBlock - 1) / kBlock), (unsigned)members), dim3(kBlock), 0, st, P->d_esq, P->d_ess, P->d_esi,
@@ -796,6 +805,91 @@ int rr_rapid_route_ensemble_dev(rr_plan *P, int64_t members, double *q_t, int64_
                        (const double *)P->d_esq, np, (const int32_t *)P->d_tinv, (int32_t)n);
     HIPCHK(hipGetLastError());
     return RR_OK;
+}
+
+int rr_rapid_route_ensemble_dev(rr_plan *P, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
+                                int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                                int64_t factor, int64_t T, int64_t nsub, void *stream)
+{
+    int rc = check_route_args(P, true, T, nsub);
+    if (rc) return rc;
+    return ensemble_route(P, "rr_rapid_route_ensemble_dev", false, members, q_t, q_pitch, lateral, lateral_is_f32, lateral_member_pitch, discharge, discharge_is_f32,
+                          discharge_member_pitch, factor, T, nsub, stream);
+}
+
+// ---- parameter ensembles: a coefficient set per member (rr_plan_set_member_coeffs, rr_rapid_route_members_dev) ----
+
+int rr_plan_set_member_coeffs(rr_plan *P, int64_t members, const double *lhs_off_data, int64_t lhs_pitch, const double *c2, const double *c3, const double *c4_dt,
+                              int64_t pitch)
+{
+    int rc = need_device(P);
+    if (rc) return rc;
+    if (P->ses.open) return fail(RR_E_STATE, "rr_plan_set_member_coeffs: a routing call is open");
+    const rr::HostPlan &H = P->h;
+    const rr::TilePlan &TP = P->tp;
+    const int64_t n = H.n;
+    if (members < 1 || members > 65535) return fail(RR_E_INVALID, "rr_plan_set_member_coeffs: need 1 <= members <= 65535");
+    if (!c2 || !c3 || !c4_dt || (H.n_edges > 0 && !lhs_off_data)) return fail(RR_E_INVALID, "rr_plan_set_member_coeffs: null coefficient array (c4_dt included: the members are RapidMuskingum's)");
+    if (pitch < n || (members > 1 && lhs_pitch < H.n_edges))
+        return fail(RR_E_INVALID, "rr_plan_set_member_coeffs: a pitch is shorter than a member (pitch >= n, lhs_pitch >= the number of edges)");
+    if (!TP.ok) return fail(RR_E_UNSUPPORTED, "rr_plan_set_member_coeffs: the network does not take the time-tiled kernel");
+    // per reach: the edges leaving its upstream reaches, as rr_plan_set_coeffs walks them (the first one's weight is the reach's c1row)
+    std::vector<int32_t> up_ptr((size_t)n + 1, 0), up_edge((size_t)H.n_edges);
+    for (int64_t p = 0; p < n; ++p) {
+        const int32_t i = H.perm[p];
+        up_ptr[i + 1] = H.child_ptr[p + 1] - H.child_ptr[p];
+    }
+    for (int64_t i = 0; i < n; ++i) up_ptr[i + 1] += up_ptr[i];
+    for (int64_t p = 0; p < n; ++p) {
+        const int32_t i = H.perm[p];
+        for (int32_t u = H.child_ptr[p], k = 0; u < H.child_ptr[p + 1]; ++u, ++k) up_edge[up_ptr[i] + k] = H.edge_of[H.perm[u]];
+    }
+    const int64_t np = TP.np;
+    std::vector<double> coef, c1row((size_t)n);
+    try { coef.assign((size_t)(members * 3 * np), 0.0); }
+    catch (const std::bad_alloc &) { return fail(RR_E_ALLOC, "rr_plan_set_member_coeffs: out of host memory for the members' tables"); }
+    for (int64_t m = 0; m < members; ++m) {
+        const double *lhs = lhs_off_data ? lhs_off_data + m * lhs_pitch : nullptr, *m2 = c2 + m * pitch, *m3 = c3 + m * pitch;
+        for (int64_t i = 0; i < n; ++i) {
+            const int32_t e0 = up_ptr[i], e1 = up_ptr[i + 1];
+            const double w0 = e1 > e0 ? -lhs[up_edge[e0]] : 0.0;
+            for (int32_t e = e0 + 1; e < e1; ++e)
+                if (-lhs[up_edge[e]] != w0)
+                    return fail(RR_E_UNSUPPORTED, "rr_plan_set_member_coeffs: member " + std::to_string(m) + " has per-edge weights (two tributaries of reach " + std::to_string(i) +
+                                                      " differ): the time-tiled kernel keeps one upstream weight per reach, and a parameter ensemble has no streaming fallback");
+            c1row[i] = w0;
+        }
+        double *mc = coef.data() + m * 3 * np;
+        for (int64_t p = 0; p < np; ++p) {
+            if (TP.lag[p] & kTileGhostBit) continue;      // a ghost computes nothing: zeros
+            const int32_t i = TP.perm[p];
+            mc[3 * p] = c1row[i]; mc[3 * p + 1] = m2[i]; mc[3 * p + 2] = m3[i];
+        }
+        for (int32_t i : P->ghost_reach) { const int64_t p = TP.inv[i]; mc[3 * p] = mc[3 * p + 1] = mc[3 * p + 2] = 0.0; }      // (upload_tile_coef: a boundary ghost too)
+    }
+    P->mc_sets = 0;      // until both tables are whole
+    rc = P->d_mcoef.reserve(members * 3 * np);
+    if (!rc) rc = P->d_mc4.reserve(members * n);
+    if (!rc) rc = dev_upload(P->d_mcoef, coef);
+    if (!rc && n > 0) {
+        const hipError_t e = hipMemcpy2D(P->d_mc4, (size_t)n * sizeof(double), c4_dt, (size_t)pitch * sizeof(double), (size_t)n * sizeof(double), (size_t)members, hipMemcpyHostToDevice);
+        if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
+    }
+    if (rc) return rc;
+    P->mc_sets = members;
+    return RR_OK;
+}
+
+int rr_rapid_route_members_dev(rr_plan *P, int64_t members, double *q_t, int64_t q_pitch, const void *lateral, int lateral_is_f32,
+                               int64_t lateral_member_pitch, void *discharge, int discharge_is_f32, int64_t discharge_member_pitch,
+                               int64_t factor, int64_t T, int64_t nsub, void *stream)
+{
+    int rc = need_device(P);      // (check_route_args without the plan's own coefficients: the call needs none)
+    if (rc) return rc;
+    if (!P->boundary_whole) return fail(RR_E_STATE, "rr_rapid_route_members_dev after a failed rr_plan_set_boundary: repeat that call first");
+    if (T < 0 || nsub < 1 || nsub > 0x7FFFFFFF) return fail(RR_E_INVALID, "rr_rapid_route_members_dev: need num steps >= 0 and 1 <= sub-steps < 2^31");
+    return ensemble_route(P, "rr_rapid_route_members_dev", true, members, q_t, q_pitch, lateral, lateral_is_f32, lateral_member_pitch, discharge, discharge_is_f32,
+                          discharge_member_pitch, factor, T, nsub, stream);
 }
 
 int rr_muskingum_route_f32_dev(rr_plan *P, double *q_t, float *discharge32, int64_t n_out, int64_t n_per_out, void *stream)

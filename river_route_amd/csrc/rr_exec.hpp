@@ -34,6 +34,9 @@ struct Rows {
     // an ensemble call (rr_rapid_route_ensemble_dev): `members` sets of rows, member m's at m * in_pitch / m * out_pitch elements from
     // the first member's (0: a single-member call)
     int64_t members = 0, in_pitch = 0, out_pitch = 0;
+    // a parameter ensemble (rr_rapid_route_members_dev): member m is routed with the plan's m-th coefficient set (rr_plan::d_mcoef, d_mc4);
+    // in_pitch may be 0 there: one forcing shared by all members
+    bool member_coeffs = false;
 };
 
 // What a route call hands over, as far as the choice of its kernel is concerned.  Built in two places only -- call_shape (from the
@@ -50,6 +53,7 @@ struct CallShape {
     bool runoff = false;         // gridded runoff: no lateral rows, the in-pass makes them
     int64_t ring_in = 0, ring_out = 0;      // streaming calls (rr_stream_begin*): rows of the caller's cyclic lateral / discharge arrays
     int64_t members = 0;         // ensemble calls: members routed together on the time-tiled kernel, one record ring each (0: a single-member call)
+    bool member_coeffs = false;  // a parameter ensemble: the members' own coefficient sets (one weight per reach each: rr_plan_set_member_coeffs), not the plan's
 };
 
 // streaming k_tick over rows, time-tiled k_tile over records, the direct row path (rr_plan_last_kernel, rr_plan_reserve's info[0])
@@ -196,6 +200,11 @@ struct rr_plan {
     std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
     DevBuf<double> d_esq, d_ess, d_esi;      // the carried state of an ensemble's members, np apart
     int64_t ens_cap = 0;             // members they have room for (rr_plan_reserve_ensemble)
+    // Parameter ensembles (rr_plan_set_member_coeffs): member m's {c1row, c2, c3} per position in tile order, zeros at ghosts -- what ts.coef
+    // would hold after rr_plan_set_coeffs with that member's arrays -- 3 np doubles apart, and its c4dt in params order, n apart.  Beside
+    // the plan's own coefficient set, never instead of it.
+    DevBuf<double> d_mcoef, d_mc4;
+    int64_t mc_sets = 0;             // coefficient sets they hold
     DevBuf<double> d_full, d_chan;   // UnitMuskingum state scattered to params order
     DevBuf<int2> d_colmeta;   // per params column {position, lag}
     DevBuf<int2> d_ghostmeta; // the same per boundary ghost (column of the ghost series)
@@ -543,7 +552,7 @@ CallShape call_shape(Mode mode, int64_t T, int64_t nsub, const Rows &io, bool st
     s.out32 = io.dev_out32 != nullptr; s.factor = io.out_factor;
     s.uh = io.uh_kernel != nullptr;
     s.runoff = io.runoff != nullptr;
-    s.members = io.members;
+    s.members = io.members; s.member_coeffs = io.member_coeffs;
     if (stream) { s.ring_in = mode == Mode::Muskingum ? 0 : io.rows_in; s.ring_out = io.rows_out; }
     return s;
 }
@@ -613,7 +622,7 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
             sch = Schedule();
         }
     }
-    bool ok = P->wave_enabled && P->tp.ok && P->weights_uniform && n > 0 && P->tp.np < (int64_t{1} << 25) &&
+    bool ok = P->wave_enabled && P->tp.ok && (P->weights_uniform || s.member_coeffs) && n > 0 && P->tp.np < (int64_t{1} << 25) &&
               !P->export_inside && P->kc_cap >= 1 && !(mode == Mode::Unit && P->unit_general);
     if (ok && !P->wave_forced) ok = total >= 32;
     if (ok) {
@@ -815,6 +824,7 @@ int session_setup(rr_plan *P, Mode mode, int64_t T, int64_t nsub, const Rows &io
                (mode == Mode::Unit || (mode == Mode::Rapid && !io.runoff && !io.uh_kernel));
         if (S.members > 0) {      // an ensemble: one ring per member, the members' carried state np apart (k_tile<..., ENS>)
             if (S.members > P->ens_cap || (S.rec_chunks * kRec * TP.np) * S.members > P->d_ring.count()) return fail(RR_E_STATE, "route: the ensemble was not reserved");
+            if (io.member_coeffs && S.members > P->mc_sets) return fail(RR_E_STATE, "route: fewer coefficient sets than members");
             S.ring_stride = S.rec_chunks * kRec * TP.np;
             S.ta.sq = P->d_esq; S.ta.ss = P->d_ess; S.ta.si = P->d_esi; S.ta.sqch = nullptr;
         }
@@ -1013,9 +1023,11 @@ tile_kernel_t tile_kernel(bool unit, bool sub, bool lean = false, bool nolat = f
 // RapidMuskingum's k_tile forms, member-batched: the general tick, with or without sub-steps.  (The short tick's member-batched form needs 72
 // bytes of scratch at 128 VGPRs -- the member's chunk and position offsets tip it over -- so an ensemble with one sub-step per row runs the
 // general tick on every tile, as RR_TILE_LEAN=0 does: the same multiply-adds on the same sums, which can differ only in the sign of a zero.)
-tile_kernel_t tile_ens_kernel(bool sub)
+// mcoef: a coefficient set per member (k_tile<..., MCOEF>): the same two forms over the members' table.
+tile_kernel_t tile_ens_kernel(bool sub, bool mcoef = false)
 {
     constexpr int T = kTileThreads;
+    if (mcoef) return sub ? (tile_kernel_t)k_tile<T, false, true, false, false, true, true> : (tile_kernel_t)k_tile<T, false, false, false, false, true, true>;
     return sub ? (tile_kernel_t)k_tile<T, false, true, false, false, true> : (tile_kernel_t)k_tile<T, false, false, false, false, true>;
 }
 
@@ -1056,8 +1068,9 @@ int launch_tile_diag(rr_plan *P, const TileSet &ts, TileArgs &w, const double *c
         // An ensemble (k_tile<..., ENS>): the tasks of every member, member on the grid's second dimension.  The workgroups of one member walk its tiles as k_tile's do;
         // together the members' take the slots one member's would (fewer tiles each: the card fills with (tile, member) tasks however few tiles the network has).
         const dim3 ge((unsigned)std::min<int64_t>(t_hi - t_lo, std::max<int64_t>(1, ((int64_t)P->cu_count * (1024 / kTileThreads) + S.members - 1) / S.members)), (unsigned)S.members);
-        w.tile_filter = 0; w.coef = ts.coef;      // (member m's ring: chunks [m C, (m + 1) C); its state: positions [m np, (m + 1) np))
-        hipLaunchKernelGGL(tile_ens_kernel(S.nsub > 1), ge, dim3((unsigned)kTileThreads), tile_lds_bytes(kTileThreads), S.stream, w);
+        const bool mcoef = S.io.member_coeffs;      // a parameter ensemble: member m's coefficients at 3 m np doubles of the members' table
+        w.tile_filter = 0; w.coef = mcoef ? P->d_mcoef.get() : ts.coef.get();      // (member m's ring: chunks [m C, (m + 1) C); its state: positions [m np, (m + 1) np))
+        hipLaunchKernelGGL(tile_ens_kernel(S.nsub > 1, mcoef), ge, dim3((unsigned)kTileThreads), tile_lds_bytes(kTileThreads), S.stream, w);
     } else {
         w.tile_filter = lean ? 1 : 0;
         w.coef = (lean && unit) ? coef_unit : ts.coef.get();
@@ -1196,7 +1209,8 @@ void launch_rec_permute(rr_plan *P, bool in, int64_t batch, int count = 1)
     hipStream_t st = rec_stream(P);
     const int aux = aux_begin(P, in ? 0 : 1, st);
     if (S.members > 0) {      // an ensemble: every member's rows in one launch, member on the grid's second dimension
-        const RecEnsArgs e{ra, S.ring_stride, in ? S.io.in_pitch : S.io.out_pitch};      // (in32 / out32 rows: the pitch counts float32 elements)
+        RecEnsArgs e{ra, S.ring_stride, in ? S.io.in_pitch : S.io.out_pitch, 0};      // (in32 / out32 rows: the pitch counts float32 elements)
+        if (in && S.io.member_coeffs) { e.scale = P->d_mc4; e.scale_pitch = n; }      // a parameter ensemble: the member's own c4dt
         hipLaunchKernelGGL(in ? rec_in_ens_kernel(sub, in32) : rec_out_ens_kernel(sub, ra.rows32 != nullptr), dim3(tiles, (unsigned)S.members), dim3(kRecInThreads), 0, st, e);
     } else if (!in) {
         launch_rec_out(ra, sub, st);

@@ -49,9 +49,10 @@ struct RecPermArgs {
 };
 
 // Ensembles (rr_kernels_tile.hpp: member_chunk0): member blockIdx.y has its rows at m * row_pitch elements from the first member's and its record
-// ring at m * ring_stride doubles; the member-batched passes (ENS) are the single-member ones on those.
+// ring at m * ring_stride doubles; the member-batched passes (ENS) are the single-member ones on those.  scale_pitch: member m's scale
+// (c4dt in params order) at m * scale_pitch doubles -- a parameter ensemble's (rr_rapid_route_members_dev); 0: the plan's, shared.
 struct RecEnsArgs : RecPermArgs {
-    int64_t ring_stride, row_pitch;
+    int64_t ring_stride, row_pitch, scale_pitch;
 };
 template <bool ENS> using RecArgsOf = typename std::conditional<ENS, RecEnsArgs, RecPermArgs>::type;
 __device__ __forceinline__ const RecPermArgs &member_args(const RecPermArgs &a) { return a; }
@@ -63,6 +64,7 @@ __device__ __forceinline__ RecPermArgs member_args(const RecEnsArgs &e)      // 
     a.rows.base += m * e.row_pitch;
     if (a.rows_in32) a.rows_in32 += m * e.row_pitch;
     if (a.rows32) a.rows32 += m * e.row_pitch;
+    if (a.scale) a.scale += m * e.scale_pitch;
     return a;
 }
 

@@ -57,6 +57,10 @@ struct TileArgs {
 // 32-bit (rr_plan_reserve_ensemble caps M C below 2^32 and M np below 2^31) and uniform: they stay in scalar registers.  k_tile uses
 // them as (ENS ? index + offset : index): with a constant condition only the live arm is emitted, so the single-member kernels compile
 // to what they were before ensembles existed.
+// Parameter ensembles (rr_rapid_route_members_dev; template flag MCOEF, only with ENS): the coefficients are not shared either.  a.coef is
+// then a table of M x 3 np doubles, member m's {c1row, c2, c3} per position behind the first member's (rr_plan_set_member_coeffs), and the
+// one place that reads a position's coefficients (load_state) starts from the member's base: one more uniform offset, 64-bit (3 M np may
+// pass 2^31).
 __device__ __forceinline__ uint32_t member_chunk0(const TileArgs &a) { return blockIdx.y * a.rec_chunks.d; }
 __device__ __forceinline__ int32_t member_pos0(const TileArgs &a) { return (int32_t)blockIdx.y * a.np; }
 
@@ -140,10 +144,11 @@ constexpr size_t tile_lds_bytes(int threads)
 // one (the two do not fit one kernel: with the record buffers in 64 of 128 registers the allocator spills the records in flight).
 // NOLAT (short tick only): channel-only routing (Muskingum.py:262-290) -- no lateral rows were turned into records, so a record slot
 // holds whatever the ring held; only a ghost's slot means something (what its reach published).
-// ENS: an ensemble's member-batched form (see member_chunk0).
-template <int TH, bool UNIT, bool SUB, bool LEAN = false, bool NOLAT = false, bool ENS = false>
+// ENS: an ensemble's member-batched form (see member_chunk0).  MCOEF: its members have a coefficient set each.
+template <int TH, bool UNIT, bool SUB, bool LEAN = false, bool NOLAT = false, bool ENS = false, bool MCOEF = false>
 __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 waves per CU: 1,024 / TH workgroups of 128 VGPRs
 {
+    static_assert(!MCOEF || ENS, "a coefficient set per member: only the member-batched forms");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     const int tid = threadIdx.x;
     const int32_t total = a.total, K = a.KC * kRec;
@@ -225,7 +230,8 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
             if (UNIT) { s.uh = first_up + (int32_t)(cc >> 16); s.qch = a.sqch[p]; }
             if (SUB) s.isum = a.si[ENS ? p + member_pos0(a) : p];
             s.s_prev = a.ss[ENS ? p + member_pos0(a) : p];
-            s.q = a.sq[ENS ? p + member_pos0(a) : p]; s.c1 = a.coef[3 * (int64_t)p]; s.c2 = a.coef[3 * (int64_t)p + 1]; s.c3 = a.coef[3 * (int64_t)p + 2];
+            const double *coef = MCOEF ? a.coef + 3 * (int64_t)member_pos0(a) : a.coef;      // (uniform: scalar registers)
+            s.q = a.sq[ENS ? p + member_pos0(a) : p]; s.c1 = coef[3 * (int64_t)p]; s.c2 = coef[3 * (int64_t)p + 1]; s.c3 = coef[3 * (int64_t)p + 2];
         }
     };
     // The first tile: state and coefficients are requested BEFORE the record: memory operations retire in order, so the

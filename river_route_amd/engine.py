@@ -225,7 +225,7 @@ class Plan:
 
     def last_kernel(self) -> str:
         """'tick' (streaming), 'tile' (time-tiled over records), 'direct' (direct row path) or 'tile_ensemble' (time-tiled, members
-        batched: rapid_route_ensemble*): what the last call ran."""
+        batched: rapid_route_ensemble*, rapid_route_members*): what the last call ran."""
         return ('tick', 'tile', 'direct', 'tile_ensemble')[int(_lib.lib().rr_plan_last_kernel(self._h))]
 
     # -- device-pointer routing (enqueue only) --
@@ -428,6 +428,112 @@ class Plan:
                 d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
                 d_q.upload(q0[g0:g0 + m])
                 self.rapid_route_ensemble_dev(m, d_q, n, d_ql, f32_in, T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
+                discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
+                q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
+        finally:
+            for b in (d_ql, d_out, d_q):
+                b.free()
+        return q0
+
+    # -- parameter ensembles: the members of an ensemble call with a coefficient set each (include/rr_hip.h) --
+    def _member_arrays(self, lhs_off_data, c2, c3, c4_dt):
+        arrays = [_f64(a, nm) for a, nm in ((lhs_off_data, 'lhs_off_data'), (c2, 'c2'), (c3, 'c3'), (c4_dt, 'c4_dt'))]
+        if any(a.ndim != 2 for a in arrays):
+            raise ValueError('member coefficients are 2-D: lhs_off_data (M, n_edges), c2 / c3 / c4_dt (M, n)')
+        M = arrays[1].shape[0]
+        if M < 1 or arrays[0].shape != (M, self.n_edges) or any(a.shape != (M, self.n) for a in arrays[1:]):
+            raise ValueError(f'member coefficients must be lhs_off_data (M, {self.n_edges}) and c2, c3, c4_dt (M, {self.n}) with one M >= 1; got '
+                             + ', '.join(str(a.shape) for a in arrays))
+        return arrays
+
+    def _upload_member_coeffs(self, g0: int, m: int) -> None:
+        lhs, c2, c3, c4 = (a[g0:g0 + m] for a in self._member_sets)      # (row slices of C-contiguous arrays: contiguous)
+        self._member_on_device = None
+        check(_lib.lib().rr_plan_set_member_coeffs(self._h, m, ptr(lhs) if lhs.size else None, self.n_edges, ptr(c2), ptr(c3), ptr(c4), self.n))
+        self._member_on_device = (g0, m)
+
+    def set_member_coeffs(self, lhs_off_data, c2, c3, c4_dt) -> None:
+        """rr_plan_set_member_coeffs: M coefficient sets for rapid_route_members*, lhs_off_data (M, n_edges), c2 / c3 / c4_dt (M, n); anything
+        array-like is made C-contiguous float64.  The plan's own coefficients (set_coeffs) are not touched.  The arrays are kept on the plan
+        (before the library sees them: where it refuses them, rapid_route_members meets the same refusal): rapid_route_members sets slices
+        of them again when it has to route in groups."""
+        self._member_sets = self._member_arrays(lhs_off_data, c2, c3, c4_dt)
+        self._upload_member_coeffs(0, self._member_sets[1].shape[0])
+
+    def rapid_route_members_dev(self, members, q_t, q_pitch, lateral, lateral_is_f32, lateral_member_pitch, discharge, discharge_is_f32,
+                                discharge_member_pitch, factor, T, num_substeps, stream=None) -> None:
+        """rr_rapid_route_members_dev (enqueue only): rapid_route_ensemble_dev with member m routed by coefficient set m of the sets on the
+        device; lateral_member_pitch 0: one forcing for all members."""
+        self.reserve_ensemble(members, T, num_substeps, f32_in=bool(lateral_is_f32), f32_out=bool(discharge_is_f32))
+        check(_lib.lib().rr_rapid_route_members_dev(self._h, int(members), ptr(q_t), int(q_pitch), ptr(lateral), int(bool(lateral_is_f32)),
+                                                    int(lateral_member_pitch), ptr(discharge), int(bool(discharge_is_f32)), int(discharge_member_pitch),
+                                                    int(factor), int(T), int(num_substeps), stream))
+
+    def rapid_route_members(self, q_t, qlateral, discharge, num_substeps: int, factor: int = 1) -> np.ndarray:
+        """Host arrays, M = the number of sets last given to set_member_coeffs: qlateral (T, n) -- one forcing, uploaded once and shared by
+        all members -- or (M, T, n), float64 or float32; q_t (n,) or (M, n); discharge (M, T, n) float64, or (M, T / factor, n) float32 (each
+        row the mean of `factor` routed rows).  Returns the (M, n) final states.  Where the reservation (members_max) or the device's memory
+        does not take all members at once they are routed in groups, each group's coefficient sets set again from the arrays the plan keeps."""
+        ql = np.asarray(qlateral)
+        if ql.dtype != np.float32:
+            ql = np.asarray(ql, dtype=np.float64)
+        if ql.ndim not in (2, 3) or ql.shape[-1] != self.n:
+            raise ValueError(f'qlateral must have shape (T, {self.n}) or (M, T, {self.n})')
+        sets = getattr(self, '_member_sets', None)
+        if sets is None:
+            raise RRError(_lib.RR_E_STATE, 'rapid_route_members before set_member_coeffs')
+        M, n = sets[1].shape[0], self.n
+        shared = ql.ndim == 2
+        T = ql.shape[-2]
+        if not shared and ql.shape[0] != M:
+            raise ValueError(f'qlateral has {ql.shape[0]} members, set_member_coeffs was given {M} sets')
+        q_in = np.asarray(q_t, dtype=np.float64)
+        if q_in.shape not in ((n,), (M, n)):
+            raise ValueError(f'q_t must have shape ({n},) or ({M}, {n})')
+        q0 = np.array(np.broadcast_to(q_in, (M, n)), order='C')      # (a copy: returned as the final states)
+        f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
+        if int(factor) < 1:
+            raise ValueError('factor must be >= 1')
+        rows = T // int(factor) if f32_out else T
+        if not (isinstance(discharge, np.ndarray) and discharge.dtype in (np.float32, np.float64) and discharge.flags['C_CONTIGUOUS']
+                and discharge.flags['WRITEABLE'] and discharge.shape == (M, rows, n) and (f32_out or int(factor) == 1)):
+            raise ValueError(f'discharge must be a writeable C-contiguous float64 ({M}, {T}, {n}) array, or float32 ({M}, T / factor, {n})')
+        f32_in = ql.dtype == np.float32
+        nsub = int(num_substeps)
+        if T == 0 or n == 0:
+            return q0
+        if getattr(self, '_member_on_device', None) is None:      # (reserve_ensemble wants coefficients on the plan)
+            self._upload_member_coeffs(0, M)
+        group = min(M, self.reserve_ensemble(1, T, nsub, f32_in, f32_out)['members_max'])
+        if group < 1:
+            raise RRError(_lib.RR_E_UNSUPPORTED, 'the record ring of one member does not fit the card at this shape')
+        # members_max budgets the record rings only: the group's rows must fit beside them, so a group the device refuses is halved
+        lat_each, out_each = T * n * ql.itemsize, rows * n * discharge.itemsize
+        while True:
+            bufs = []
+            try:
+                for b in (lat_each * (1 if shared else group), out_each * group, n * 8 * group):
+                    bufs.append(DeviceBuffer(b, self.device))
+                self.reserve_ensemble(group, T, nsub, f32_in, f32_out)
+                break
+            except RRError as e:
+                for b in bufs:
+                    b.free()
+                if e.code != _lib.RR_E_ALLOC or group == 1:
+                    raise
+                group = (group + 1) // 2
+        d_ql, d_out, d_q = bufs
+        try:
+            if shared:
+                d_ql.upload(np.ascontiguousarray(ql))
+            for g0 in range(0, M, group):
+                m = min(group, M - g0)
+                if self._member_on_device != (g0, m) and not (g0 == 0 and self._member_on_device == (0, M)):
+                    self._upload_member_coeffs(g0, m)
+                if not shared:
+                    d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
+                d_q.upload(q0[g0:g0 + m])
+                self.rapid_route_members_dev(m, d_q, n, d_ql, f32_in, 0 if shared else T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
                 discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
                 q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
         finally:
