@@ -383,16 +383,16 @@ class Plan:
                                                      int(lateral_member_pitch), ptr(discharge), int(bool(discharge_is_f32)), int(discharge_member_pitch),
                                                      int(factor), int(T), int(num_substeps), stream))
 
-    def rapid_route_ensemble(self, q_t, qlateral, discharge, num_substeps: int, factor: int = 1) -> np.ndarray:
-        """Host arrays: qlateral (M, T, n) float64 or float32; q_t (n,) -- every member starts there -- or (M, n); discharge (M, T, n)
-        float64, or (M, T / factor, n) float32 (each row the mean of `factor` routed rows).  Returns the (M, n) final states.  The members
-        go to the device in groups of the size the reservation reports (members_max)."""
+    def _route_member_groups(self, q_t, qlateral, M, discharge, num_substeps, factor, route_dev, per_group=None) -> np.ndarray:
+        """The host-array driver behind rapid_route_ensemble and rapid_route_members: M members' rows (M, T, n) -- or one (T, n) forcing that
+        all members share, uploaded once and passed with member pitch 0 -- go to the device in groups of the size the reservation reports
+        (members_max), each group routed by `route_dev` (rapid_route_ensemble_dev's signature).  `per_group(g0, m)` is called before each
+        group with its range, and once before the first reservation with (0, 0): rapid_route_members puts the group's coefficient sets
+        on the plan there.  Returns the (M, n) final states."""
         ql = np.asarray(qlateral)
         if ql.dtype != np.float32:
             ql = np.asarray(ql, dtype=np.float64)
-        if ql.ndim != 3 or ql.shape[2] != self.n:
-            raise ValueError(f'qlateral must have shape (M, T, {self.n})')
-        M, T, n = ql.shape
+        shared, (T, n) = ql.ndim == 2, ql.shape[-2:]
         q0 = np.array(np.broadcast_to(np.asarray(q_t, dtype=np.float64), (M, n)), order='C')      # (a copy: returned as the final states)
         f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
         rows = T // int(factor) if f32_out else T
@@ -403,6 +403,8 @@ class Plan:
         nsub = int(num_substeps)
         if M == 0 or T == 0 or n == 0:
             return q0
+        if per_group:
+            per_group(0, 0)
         group = min(M, self.reserve_ensemble(1, T, nsub, f32_in, f32_out)['members_max'])
         if group < 1:
             raise RRError(_lib.RR_E_UNSUPPORTED, 'the record ring of one member does not fit the card at this shape')
@@ -411,8 +413,8 @@ class Plan:
         while True:
             bufs = []
             try:
-                for b in (lat_each, out_each, n * 8):
-                    bufs.append(DeviceBuffer(group * b, self.device))
+                for b in (lat_each * (1 if shared else group), out_each * group, n * 8 * group):
+                    bufs.append(DeviceBuffer(b, self.device))
                 self.reserve_ensemble(group, T, nsub, f32_in, f32_out)
                 break
             except RRError as e:
@@ -423,17 +425,31 @@ class Plan:
                 group = (group + 1) // 2
         d_ql, d_out, d_q = bufs
         try:
+            if shared:
+                d_ql.upload(np.ascontiguousarray(ql))
             for g0 in range(0, M, group):
                 m = min(group, M - g0)
-                d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
+                if per_group:
+                    per_group(g0, m)
+                if not shared:
+                    d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
                 d_q.upload(q0[g0:g0 + m])
-                self.rapid_route_ensemble_dev(m, d_q, n, d_ql, f32_in, T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
+                route_dev(m, d_q, n, d_ql, f32_in, 0 if shared else T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
                 discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
                 q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
         finally:
             for b in (d_ql, d_out, d_q):
                 b.free()
         return q0
+
+    def rapid_route_ensemble(self, q_t, qlateral, discharge, num_substeps: int, factor: int = 1) -> np.ndarray:
+        """Host arrays: qlateral (M, T, n) float64 or float32; q_t (n,) -- every member starts there -- or (M, n); discharge (M, T, n)
+        float64, or (M, T / factor, n) float32 (each row the mean of `factor` routed rows).  Returns the (M, n) final states.  The members
+        go to the device in groups of the size the reservation reports (members_max)."""
+        ql = np.asarray(qlateral)
+        if ql.ndim != 3 or ql.shape[2] != self.n:
+            raise ValueError(f'qlateral must have shape (M, T, {self.n})')
+        return self._route_member_groups(q_t, ql, ql.shape[0], discharge, num_substeps, factor, self.rapid_route_ensemble_dev)
 
     # -- parameter ensembles: the members of an ensemble call with a coefficient set each (include/rr_hip.h, DESIGN.md section 10b) --
     def _member_arrays(self, lhs_off_data, c2, c3, c4_dt):
@@ -475,71 +491,28 @@ class Plan:
         row the mean of `factor` routed rows).  Returns the (M, n) final states.  Where the reservation (members_max) or the device's memory
         does not take all members at once they are routed in groups, each group's coefficient sets set again from the arrays the plan keeps."""
         ql = np.asarray(qlateral)
-        if ql.dtype != np.float32:
-            ql = np.asarray(ql, dtype=np.float64)
         if ql.ndim not in (2, 3) or ql.shape[-1] != self.n:
             raise ValueError(f'qlateral must have shape (T, {self.n}) or (M, T, {self.n})')
         sets = getattr(self, '_member_sets', None)
         if sets is None:
             raise RRError(_lib.RR_E_STATE, 'rapid_route_members before set_member_coeffs')
         M, n = sets[1].shape[0], self.n
-        shared = ql.ndim == 2
-        T = ql.shape[-2]
-        if not shared and ql.shape[0] != M:
+        if ql.ndim == 3 and ql.shape[0] != M:
             raise ValueError(f'qlateral has {ql.shape[0]} members, set_member_coeffs was given {M} sets')
         q_in = np.asarray(q_t, dtype=np.float64)
         if q_in.shape not in ((n,), (M, n)):
             raise ValueError(f'q_t must have shape ({n},) or ({M}, {n})')
-        q0 = np.array(np.broadcast_to(q_in, (M, n)), order='C')      # (a copy: returned as the final states)
-        f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
         if int(factor) < 1:
             raise ValueError('factor must be >= 1')
-        rows = T // int(factor) if f32_out else T
-        if not (isinstance(discharge, np.ndarray) and discharge.dtype in (np.float32, np.float64) and discharge.flags['C_CONTIGUOUS']
-                and discharge.flags['WRITEABLE'] and discharge.shape == (M, rows, n) and (f32_out or int(factor) == 1)):
-            raise ValueError(f'discharge must be a writeable C-contiguous float64 ({M}, {T}, {n}) array, or float32 ({M}, T / factor, {n})')
-        f32_in = ql.dtype == np.float32
-        nsub = int(num_substeps)
-        if T == 0 or n == 0:
-            return q0
-        if getattr(self, '_member_on_device', None) is None:      # (reserve_ensemble wants coefficients on the plan)
-            self._upload_member_coeffs(0, M)
-        group = min(M, self.reserve_ensemble(1, T, nsub, f32_in, f32_out)['members_max'])
-        if group < 1:
-            raise RRError(_lib.RR_E_UNSUPPORTED, 'the record ring of one member does not fit the card at this shape')
-        # members_max budgets the record rings only: the group's rows must fit beside them, so a group the device refuses is halved
-        lat_each, out_each = T * n * ql.itemsize, rows * n * discharge.itemsize
-        while True:
-            bufs = []
-            try:
-                for b in (lat_each * (1 if shared else group), out_each * group, n * 8 * group):
-                    bufs.append(DeviceBuffer(b, self.device))
-                self.reserve_ensemble(group, T, nsub, f32_in, f32_out)
-                break
-            except RRError as e:
-                for b in bufs:
-                    b.free()
-                if e.code != _lib.RR_E_ALLOC or group == 1:
-                    raise
-                group = (group + 1) // 2
-        d_ql, d_out, d_q = bufs
-        try:
-            if shared:
-                d_ql.upload(np.ascontiguousarray(ql))
-            for g0 in range(0, M, group):
-                m = min(group, M - g0)
-                if self._member_on_device != (g0, m) and not (g0 == 0 and self._member_on_device == (0, M)):
-                    self._upload_member_coeffs(g0, m)
-                if not shared:
-                    d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
-                d_q.upload(q0[g0:g0 + m])
-                self.rapid_route_members_dev(m, d_q, n, d_ql, f32_in, 0 if shared else T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
-                discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
-                q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
-        finally:
-            for b in (d_ql, d_out, d_q):
-                b.free()
-        return q0
+
+        def sets_on_plan(g0, m):
+            on = getattr(self, '_member_on_device', None)
+            if m == 0:      # no group yet: reserve_ensemble wants coefficients on the plan, whichever
+                if on is None:
+                    self._upload_member_coeffs(0, M)
+            elif on != (g0, m) and not (g0 == 0 and on == (0, M)):
+                self._upload_member_coeffs(g0, m)
+        return self._route_member_groups(q_in, ql, M, discharge, num_substeps, factor, self.rapid_route_members_dev, sets_on_plan)
 
     def muskingum_route_f32_dev(self, q_t, discharge32, num_output_steps, num_routing_per_output, stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output, f32_out=True)

@@ -30,14 +30,12 @@ class TransformMuskingum(Muskingum, ABC):
                     yield rows[0], rows[1], lateral_file, discharge_file
                     continue
                 # a router that converts on the device takes a float32 file as float32 (RapidMuskingum: rr_rapid_route_f32in_dev)
-                keep32 = self._device_postprocess and hasattr(self, '_route_on_device_f32in') and \
-                    type(self)._router is getattr(type(self), '_engine_router', None)
-                dates, array = read_qlateral(lateral_file, self.cfg.var_t, keep_float32=keep32)
+                dates, array = read_qlateral(lateral_file, self.cfg.var_t, keep_float32=self._own_engine_path())
                 yield dates, array, lateral_file, discharge_file
         elif self.cfg.grid_runoff_files and self.cfg.grid_weights_file:
             # gridded runoff -> catchment inflow on the device (TransformMuskingum.py:38-51 -> runoff.runoff_to_qlateral).  A
-            # router that can take the runoff itself (`_router_device_runoff`) gets the prepared source instead of the
-            # (time, river) array, so the inflow is computed on its way into the engine's records
+            # router on its own engine path gets the prepared source instead of the (time, river) array, so the inflow is
+            # computed on the device, where the engine takes that on its way into the engine's records (_device.route_file)
             from ..runoff import prepare_runoff, runoff_to_qlateral
             kw = dict(grid_weights_file=self.cfg.grid_weights_file, var_runoff=self.cfg.var_grid_runoff, var_x=self.cfg.var_x,
                       var_y=self.cfg.var_y, var_t=self.cfg.var_t, var_river_id=self.cfg.var_river_id,
@@ -45,7 +43,7 @@ class TransformMuskingum(Muskingum, ABC):
             for runoff_file, discharge_file in zip(self.cfg.grid_runoff_files, self.cfg.discharge_files):
                 self.logger.info('-' * 60)
                 self.logger.debug(f'Calculating qlateral: {runoff_file}')
-                if self._takes_runoff_source():
+                if self._own_engine_path():
                     src = prepare_runoff(runoff_file, **kw)
                     if not src.irregular:
                         yield src.time_index.astype('datetime64[s]'), src, runoff_file, discharge_file
@@ -57,9 +55,7 @@ class TransformMuskingum(Muskingum, ABC):
     def _file_rows(self, lateral_file):
         """(dates, nc3.RowBlock) where the router can take a qlateral file's rows straight from the file -- a flat (NetCDF-3) float32
         variable, the router's own engine path and the default discharge writer -- else None."""
-        if not (self._device_postprocess and hasattr(self, '_route_file_to_file') and hasattr(self._plan, 'rapid_route_dev')
-                and type(self)._router is getattr(type(self), '_engine_router', None) and '_write_discharges' not in self.__dict__
-                and type(self)._write_discharges is Muskingum._write_discharges):
+        if not (self._own_engine_path() and '_write_discharges' not in self.__dict__ and type(self)._write_discharges is Muskingum._write_discharges):
             return None
         from .. import nc3
         from ..io import _decode_cf_time
@@ -71,32 +67,6 @@ class TransformMuskingum(Muskingum, ABC):
             return _decode_cf_time(values, atts['units']), blk
         except (KeyError, ValueError):
             return None
-
-    def _takes_runoff_source(self) -> bool:
-        return (self._device_postprocess and hasattr(self, '_route_on_device') and hasattr(self._plan, 'rapid_route_dev')
-                and type(self)._router is getattr(type(self), '_engine_router', None))
-
-    def _router_device_runoff(self, source, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
-        """Gridded runoff of one file routed without leaving the GPU: the runoff block and the weight table go up once,
-        rr_runoff_to_qlateral_dev writes the catchment inflow as device rows (volumes for RapidMuskingum, depths for
-        UnitMuskingum), and the router's device path takes it from there.  RapidMuskingum overrides this with the call that
-        computes the inflow inside the record pass (rr_rapid_route_runoff_dev) where that applies."""
-        from ..engine import runoff_to_qlateral_dev
-        from ._device import Arena
-        T, n = source.runoff_tp.shape[0], self.A.shape[0]
-        if source.river_ids.shape[0] != n or T != self.num_runoff_steps:
-            raise ValueError(f'gridded runoff covers {source.river_ids.shape[0]} rivers x {T} steps, the network and time options '
-                             f'expect {n} x {self.num_runoff_steps}')
-        block = source.point_major()
-        with Arena(self.cfg.device) as arena:
-            d_block, d_ptr, d_idx = arena.put(block), arena.put(source.indptr), arena.put(source.indices)
-            d_w = arena.put(source.weights)
-            d_area = arena.put(source.area) if self._as_volumes else None
-            d_lat = arena.empty(T * n * 8)
-            runoff_to_qlateral_dev(n, block.shape[0], T, d_ptr, d_idx, d_w, d_block, block.dtype == np.float32, 1, block.shape[1], d_area,
-                                   source.flags, d_lat, device=self.cfg.device)
-            arena.release(d_block)
-            return self._route_on_device(arena, d_lat, T, rows_per_output)
 
     def _validate_router_configs(self) -> None:
         laterals = list(self.cfg.qlateral_files or [])
@@ -138,29 +108,24 @@ class TransformMuskingum(Muskingum, ABC):
         self.c4 = self.c1 + self.c2
         self._network_time_signature = steps
 
-    def _route_one_file(self, qlateral: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
-        """(final state, float32 discharge at dt_discharge) of one file.  The file stays on the GPU from the lateral
-        upload to the float32 rows unless a subclass brings its own `_router` (the reference's extension point), the
-        engine is not the HIP plan, or the file does not fit on the card: then `_router` + the post-processing of
-        TransformMuskingum.py:128-142 on the host."""
+    def _own_engine_path(self, plan_call: str = 'rapid_route_dev') -> bool:
+        """Whether this router keeps its files on the GPU: device post-processing is on, `_router` is the engine's own (a subclass that
+        brings its own `_router`, the reference's extension point, gets the host path) and the plan has the device calls (feature test
+        on `plan_call`: a stand-in plan without it gets the host path)."""
+        return (self._device_postprocess and type(self)._router is getattr(type(self), '_engine_router', None)
+                and hasattr(self._plan, plan_call))
+
+    def _route_one_file(self, source, sink=None) -> tuple[np.ndarray, np.ndarray | None]:
+        """(final state, float32 discharge at dt_discharge) of one file: on the GPU from the lateral upload to the float32 rows
+        (_device.route_file, which also decides when a file must take the host path after all), or on the host."""
+        if self._own_engine_path():
+            from ._device import route_file
+            return route_file(self, source, sink)
+        return self._route_on_host(source)
+
+    def _route_on_host(self, qlateral: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
+        """`_router` + the post-processing of TransformMuskingum.py:128-142 on the host."""
         per = self.num_runoff_steps_per_discharge
-        from ..runoff import RunoffSource
-        if isinstance(qlateral, RunoffSource):
-            from .._lib import RR_E_UNSUPPORTED, RRError
-            from ._device import DeviceOutOfMemory
-            try:
-                return self._router_device_runoff(qlateral, per)
-            except (DeviceOutOfMemory, RRError) as e:
-                if isinstance(e, RRError) and e.code != RR_E_UNSUPPORTED:
-                    raise
-                qlateral = qlateral.to_array(self._as_volumes)      # the two-step form: (time, river) rows, then the routing call
-        own_router = type(self)._router is getattr(type(self), '_engine_router', None)
-        if self._device_postprocess and own_router and hasattr(self._plan, 'rapid_route_dev'):
-            from ._device import DeviceOutOfMemory
-            try:
-                return self._router_device(qlateral, per)
-            except DeviceOutOfMemory as e:
-                self.logger.warning(f'file does not fit on the device ({e}); routing it in chunks from host memory')
         q_t, q_array = self._router(qlateral)
         if per > 1:
             q_array = q_array.reshape((-1, per, q_array.shape[1])).mean(axis=1)
@@ -207,19 +172,10 @@ class TransformMuskingum(Muskingum, ABC):
         self._set_network_and_time_dependent_vectors(dates)
         self.logger.debug('Starting routing computation')
         t0 = time.perf_counter()
-        from ..nc3 import RowBlock
-        written = False
         if routed is not None:
             q_t, q_array, seconds = routed
-        else:
-            if isinstance(qlateral, RowBlock):
-                q_t = self._route_file_to_file(qlateral, dates[::self.num_runoff_steps_per_discharge], discharge_file, runoff_file)
-                written = q_t is not None
-                if not written:      # the fused form does not apply to this call, or the file does not fit the card: the file as an array
-                    from ..io import read_qlateral
-                    qlateral = read_qlateral(runoff_file, self.cfg.var_t, keep_float32=True)[1]
-            if not written:
-                q_t, q_array = self._route_one_file(qlateral)
+        else:      # (a file's rows go to the discharge file where the engine takes them from file to file: no array comes back then)
+            q_t, q_array = self._route_one_file(qlateral, (discharge_file, dates[::self.num_runoff_steps_per_discharge], runoff_file))
             seconds = time.perf_counter() - t0
         reach_steps = self.A.shape[0] * self.num_runoff_steps * self.num_routing_steps_per_runoff
         self.logger.log(PROGRESS, f'{reach_steps / max(seconds, 1e-9):.3e} reach-steps/s '
@@ -231,7 +187,7 @@ class TransformMuskingum(Muskingum, ABC):
         if self.num_runoff_steps_per_discharge > 1:
             self.logger.debug('Resampling dates and discharges to specified timestep')
             dates = dates[::self.num_runoff_steps_per_discharge]
-        if not written:
+        if q_array is not None:
             self.logger.debug('Writing Discharge Array to File')
             self._write_discharges(dates, q_array, discharge_file, runoff_file)
 
@@ -241,8 +197,7 @@ class TransformMuskingum(Muskingum, ABC):
     def _ensemble_batching(self) -> bool:
         """The router batches ensemble members where it has the group call, the plan has the ensemble call (feature test: a stand-in plan
         without it keeps the loop) and its own engine path and device post-processing are in force."""
-        return (hasattr(self, '_route_ensemble_group') and hasattr(self._plan, 'rapid_route_ensemble') and self._device_postprocess
-                and type(self)._router is getattr(type(self), '_engine_router', None))
+        return hasattr(self, '_route_ensemble_group') and self._own_engine_path('rapid_route_ensemble')
 
     def _joins_ensemble_group(self, pending: list, item) -> bool:
         dates, qlateral = item[0], item[1]
@@ -287,14 +242,23 @@ class TransformMuskingum(Muskingum, ABC):
     def _router(self, qlateral: np.ndarray) -> tuple[np.ndarray, np.ndarray]:
         """(final state float64[n], discharge float64[T, n]) for one input file, host arrays."""
 
-    @abstractmethod
-    def _router_device(self, qlateral: np.ndarray, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
-        """(final state float64[n], discharge float32[T / rows_per_output, n]) with the whole file on the device."""
+    # ---- what the per-file device driver (_device.route_file) asks of a router with an engine path of its own (`_engine_router`) ----
+    #   _lateral_coefficient()            put the router's coefficients on the plan (they stay there until recomputed)
+    #   _device_state(arena) -> state     upload the router's state; the handle goes to the engine calls and to _device_state_back
+    #   _device_state_back(state)         the final state float64[n] after a routing call the engine took
+    #   _device_calls()                   {(rows in, rows out): call(state, d_in, T, d_out)}: in 'f64' | 'f32' | 'runoff', out 'f32' | 'f64'
+    def _device_lower(self, arena, state, kind: str, d_rows, T: int):
+        """(kind, rows) the router makes of rows the engine refused in every form of their own, or None."""
+        return None
 
     def _check_lateral(self, qlateral: np.ndarray, keep_float32: bool = False) -> np.ndarray:
         qlateral = np.asarray(qlateral)
         ql = np.ascontiguousarray(qlateral, dtype=np.float32 if keep_float32 and qlateral.dtype == np.float32 else np.float64)
-        if ql.shape != (self.num_runoff_steps, self.A.shape[0]):
-            raise ValueError(f'lateral inflow has shape {ql.shape}, expected '
-                             f'({self.num_runoff_steps}, {self.A.shape[0]}) from the time options')
+        self._check_shape(ql.shape)
         return ql
+
+    def _check_shape(self, shape: tuple) -> None:
+        """The rows of one input, an array's or a file's, are those the time options and the network expect."""
+        if tuple(shape) != (self.num_runoff_steps, self.A.shape[0]):
+            raise ValueError(f'lateral inflow has shape {tuple(shape)}, expected '
+                             f'({self.num_runoff_steps}, {self.A.shape[0]}) from the time options')

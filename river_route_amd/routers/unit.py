@@ -59,120 +59,58 @@ class UnitMuskingum(TransformMuskingum):
 
     _engine_router = _router
 
-    def _router_device(self, qlateral: np.ndarray, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
-        from .._lib import RR_E_UNSUPPORTED, RRError
-        from ._device import Arena
+    # ---- the hooks of the per-file device driver (_device.route_file) ----
+    def _lateral_coefficient(self) -> None:
+        """The convolved inflow enters the routing step as it is: three coefficients, no fourth."""
         self._check_kernel()
-        depth = self._check_lateral(qlateral, keep_float32=True)
-        if depth.dtype == np.float32:      # a float32 file: uploaded as it is, converted in the pass that convolves it into the engine's records
-            try:
-                with Arena(self.cfg.device) as arena:
-                    return self._route_on_device_f32in(arena, arena.put(depth), depth.shape[0], rows_per_output)
-            except RRError as e:
-                if e.code != RR_E_UNSUPPORTED:
-                    raise
-            depth = depth.astype(np.float64)
-        with Arena(self.cfg.device) as arena:
-            return self._route_on_device(arena, arena.put(depth), depth.shape[0], rows_per_output)
-
-    def _route_file_to_file(self, rows, dates_out, discharge_file, runoff_file):
-        """One runoff-depth file whose float32 rows lie flat in the file (nc3.RowBlock) -> the discharge file without a host array of
-        either: engine.rows_upload, rr_unit_route_uh_f32in_dev (convolution fused in, the file's byte order converted in the kernels),
-        nc3.create_discharge_file, engine.rows_download.  Returns the router state (UnitMuskingum.py:95-97), or None where the fused
-        form does not apply or the file does not fit the card -- the UH state is then as it was."""
-        from .. import nc3
-        from .._lib import RR_E_ALLOC, RR_E_UNSUPPORTED, RRError
-        from ..engine import rows_download, rows_upload
-        from ._device import Arena, DeviceOutOfMemory
-        self._check_kernel()
-        T, n, nsub, per = rows.rows, self.A.shape[0], self.num_routing_steps_per_runoff, self.num_runoff_steps_per_discharge
-        if T != self.num_runoff_steps:
-            raise ValueError(f'lateral inflow has shape ({T}, {rows.cols}), expected ({self.num_runoff_steps}, {n}) from the time options')
-        n_ks = self._uh.kernel.shape[0]
         self._upload_coefficients(None, ('unit',))
-        seed = self._seed()
-        dev = self.cfg.device
-        try:
-            with Arena(dev) as arena:
-                d_depth = arena.empty(T * n * 4)
-                d_out = arena.empty((T // per) * n * 4)
-                d_kern = arena.put(self._uh.kernel)
-                d_state = arena.put(np.ascontiguousarray(self._uh.state, dtype=np.float64))
-                d_qch, d_qfull, d_final = arena.put(seed), arena.put(seed), arena.empty(n * 8)
-                rows_upload(d_depth, n * 4, rows.path, rows.offset, rows.pitch, n * 4, T, device=dev)
-                self._plan.set_row_format(rows.big_endian, True)
-                try:
-                    self._plan.unit_route_uh_f32in_dev(d_qch, d_qfull, d_final, d_kern, d_state, n_ks, d_depth, T, nsub, discharge32=d_out, factor=per)
-                finally:
-                    self._plan.set_row_format(False, False)
-                out = nc3.create_discharge_file(discharge_file, dates_out, self.river_ids, self.cfg.var_river_id, self.cfg.var_discharge, runoff_file)
-                rows_download(d_out, n * 4, out.path, out.offset, out.pitch, n * 4, T // per, device=dev)
-                state = d_final.download(np.float64, (n,))
-                self._uh.state = d_state.download(np.float64, self._uh.kernel.shape)
-                return state
-        except DeviceOutOfMemory:
-            return None
-        except RRError as e:
-            if e.code not in (RR_E_UNSUPPORTED, RR_E_ALLOC):
-                raise
-            return None
 
-    def _route_on_device_f32in(self, arena, d_depth32, T: int, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
-        """Runoff depths on the device as (T, n) float32 rows -> (router state, float32 discharge rows): rr_unit_route_uh_f32in_dev,
-        bit for bit what the float64 rows give (float32 -> float64 is exact).  RR_E_UNSUPPORTED (a call the time-tiled kernel does not
-        take, more than 64 kernel steps) leaves the UH state as it was: the caller converts the rows and takes the float64 path."""
-        self._check_kernel()
+    def _check_shape(self, shape: tuple) -> None:
+        self._check_kernel()      # (first, as before the depths were ever looked at: a kernel of another network is the error to report)
+        super()._check_shape(shape)
+
+    def _device_state(self, arena):
+        """Kernel and UH state, the seed as channel and as full discharge of the inner reaches, and room for the router state the
+        fused calls write (UnitMuskingum.py:95-97)."""
+        from types import SimpleNamespace
+        seed = self._seed()
+        kern, uh = arena.put(self._uh.kernel), arena.put(np.ascontiguousarray(self._uh.state, dtype=np.float64))
+        return SimpleNamespace(kern=kern, uh=uh, q_ch=arena.put(seed), q_full=arena.put(seed), final=arena.empty(self.A.shape[0] * 8), conv=None, T=0)
+
+    def _device_state_back(self, s) -> np.ndarray:
+        """The router state, then the UH state: an input the engine refused in every form has left it as it was."""
         n = self.A.shape[0]
-        n_ks, nsub = self._uh.kernel.shape[0], self.num_routing_steps_per_runoff
-        self._upload_coefficients(None, ('unit',))
-        seed = self._seed()
-        d_kern = arena.put(self._uh.kernel)
-        d_state = arena.put(np.ascontiguousarray(self._uh.state, dtype=np.float64))
-        d_qch, d_qfull, d_final = arena.put(seed), arena.put(seed), arena.empty(n * 8)
-        d_f32 = arena.empty((T // rows_per_output) * n * 4)
-        self._plan.unit_route_uh_f32in_dev(d_qch, d_qfull, d_final, d_kern, d_state, n_ks, d_depth32, T, nsub,
-                                           discharge32=d_f32, factor=rows_per_output)
-        q_array = d_f32.download(np.float32, (T // rows_per_output, n))
-        state = d_final.download(np.float64, (n,))
-        self._uh.state = d_state.download(np.float64, self._uh.kernel.shape)
-        return state, q_array
+        if s.conv is None:
+            state = s.final.download(np.float64, (n,))
+        else:
+            state = s.conv.download(np.float64, (n,), offset=(s.T - 1) * n * 8)    # headwaters keep the last lateral row
+            state[self.inner_idx] = s.q_full.download(np.float64, self.inner_idx.shape)
+        self._uh.state = s.uh.download(np.float64, self._uh.kernel.shape)
+        return state
 
-    def _route_on_device(self, arena, d_depth, T: int, rows_per_output: int) -> tuple[np.ndarray, np.ndarray]:
-        """Runoff depths already on the device, (T, n) float64 rows -> (router state, float32 discharge rows).  Where the
-        engine takes it (time-tiled call, at most 64 kernel steps) the convolution is fused into the pass that turns rows
-        into records (rr_unit_route_uh_dev): the convolved lateral never exists as rows; otherwise rr_uh_convolve_dev, then
-        the routing call."""
-        from .._lib import RR_E_UNSUPPORTED, RRError
+    def _device_calls(self) -> dict:
+        """The engine call per (rows in, rows out).  Runoff depths, float64 or float32 rows: the convolution fused into the pass that turns
+        rows into records, so the convolved lateral never exists as rows (a time-tiled call, at most 64 kernel steps; float32 discharge
+        only).  'conv', the convolved rows of _device_lower: the routing calls."""
+        plan, nsub, per, n_ks = self._plan, self.num_routing_steps_per_runoff, self.num_runoff_steps_per_discharge, self._uh.kernel.shape[0]
+        return {
+            ('f64', 'f32'): lambda s, d_depth, T, d_out: plan.unit_route_uh_dev(
+                s.q_ch, s.q_full, s.final, s.kern, s.uh, n_ks, d_depth, T, nsub, discharge32=d_out, factor=per),
+            ('f32', 'f32'): lambda s, d_depth, T, d_out: plan.unit_route_uh_f32in_dev(
+                s.q_ch, s.q_full, s.final, s.kern, s.uh, n_ks, d_depth, T, nsub, discharge32=d_out, factor=per),
+            ('conv', 'f32'): lambda s, d_conv, T, d_out: plan.unit_route_f32_dev(s.q_ch, s.q_full, d_conv, T, d_out, T, nsub, per),
+            ('conv', 'f64'): lambda s, d_conv, T, d_out: plan.unit_route_dev(s.q_ch, s.q_full, d_conv, T, d_out, T, T, nsub),
+        }
+
+    def _device_lower(self, arena, s, kind: str, d_depth, T: int):
+        """Float64 depths the fused call refused: rr_uh_convolve_dev into rows of their own, ('conv', rows).  Float32 depths: None, the
+        driver widens them."""
         from ..engine import uh_convolve_dev
-        from ._device import float32_rows
-        self._check_kernel()
-        n = self.A.shape[0]
-        n_ks, nsub = self._uh.kernel.shape[0], self.num_routing_steps_per_runoff
-        self._upload_coefficients(None, ('unit',))
-        seed = self._seed()
-        d_kern = arena.put(self._uh.kernel)
-        d_state = arena.put(np.ascontiguousarray(self._uh.state, dtype=np.float64))
-        d_qch, d_qfull, d_final = arena.put(seed), arena.put(seed), arena.empty(n * 8)
-        d_f32 = arena.empty((T // rows_per_output) * n * 4)
-        try:
-            self._plan.unit_route_uh_dev(d_qch, d_qfull, d_final, d_kern, d_state, n_ks, d_depth, T, nsub,
-                                         discharge32=d_f32, factor=rows_per_output)
-            q_array = d_f32.download(np.float32, (T // rows_per_output, n))
-            state = d_final.download(np.float64, (n,))
-        except RRError as e:
-            if e.code != RR_E_UNSUPPORTED:
-                raise
-            arena.release(d_f32)
-            d_conv = arena.empty(T * n * 8)
-            uh_convolve_dev(d_kern, d_state, d_depth, d_conv, T, n_ks, n, device=self.cfg.device)
-            q_array = float32_rows(
-                arena, T, n, rows_per_output,
-                fused=lambda d32: self._plan.unit_route_f32_dev(d_qch, d_qfull, d_conv, T, d32, T, nsub, rows_per_output),
-                plain=lambda d64: self._plan.unit_route_dev(d_qch, d_qfull, d_conv, T, d64, T, T, nsub))
-            state = d_conv.download(np.float64, (n,), offset=(T - 1) * n * 8)    # headwaters keep the last lateral row
-            state[self.inner_idx] = d_qfull.download(np.float64, seed.shape)
-        self._uh.state = d_state.download(np.float64, self._uh.kernel.shape)
-        return state, q_array
+        if kind != 'f64':
+            return None
+        s.conv, s.T = arena.empty(T * self.A.shape[0] * 8), T
+        uh_convolve_dev(s.kern, s.uh, d_depth, s.conv, T, self._uh.kernel.shape[0], self.A.shape[0], device=self.cfg.device)
+        return 'conv', s.conv
 
     def _write_final_state(self) -> None:
         super()._write_final_state()

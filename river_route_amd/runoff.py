@@ -105,7 +105,7 @@ class RunoffSource:
     (time, points) runoff block, the CSR weights (proportion x unit conversion, duplicates summed, ascending point order
     as the reference's csr_matrix), catchment areas, flags, the time axis and the river ids in column order.  The routers
     upload it as it is, so that the catchment inflow is computed on the GPU and routed from there without a trip through host
-    memory (TransformMuskingum._router_device_runoff; rr_rapid_route_runoff_dev takes the same pieces and computes the inflow
+    memory (routers/_device.py: _runoff_forms; rr_rapid_route_runoff_dev takes the same pieces and computes the inflow
     on the way into the engine's records); `to_array()` is the reference's (time, river) array."""
     runoff_tp: np.ndarray
     indptr: np.ndarray

@@ -515,6 +515,96 @@ def test_device_file_path_equals_host_path(case, monkeypatch):
             np.testing.assert_array_equal(a, b)
 
 
+GOLDEN_ROUTES = ('rapid_seq', 'rapid_seq_resample', 'unit_seq')
+
+
+def golden_route(name, case):
+    """One of the golden sequential runs above, by its tag in routers.npz: (router, what the writer got)."""
+    g = case['g']
+    if name == 'unit_seq':
+        kp, us = _unit_files(case)
+        return drive(rr.UnitMuskingum, case, [g['depth0'], g['depth1']], channel_state_init_file=case['init'], dt_routing=1200,
+                     uh_kernel_file=kp, uh_state_init_file=us)
+    steps = dict(rapid_seq=dict(dt_routing=900), rapid_seq_resample=dict(dt_routing=1800, dt_discharge=3 * 3600))[name]
+    return drive(rr.RapidMuskingum, case, [g['vol0'], g['vol1']], channel_state_init_file=case['init'], **steps)
+
+
+def check_golden(name, case, r, got):
+    check(case, name, r, got)
+    if name == 'unit_seq':
+        want = case['g']['unit_seq/uh_state_final']
+        np.testing.assert_allclose(r._uh.state, want, rtol=0, atol=1e-12 * float(np.abs(want).max()))
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('switch', ['RR_WAVE=0', 'RR_WAVE=1', 'RR_DIRECT=0'])
+@pytest.mark.parametrize('name', GOLDEN_ROUTES)
+def test_refused_forms_give_the_golden_results(case, monkeypatch, name, switch):
+    """The forms the per-file driver falls to when the engine refuses the one before: with the streaming kernel for every call
+    (RR_WAVE=0) every call that writes float32 rows itself is refused, so the float64 call and rr_resample_cast_dev run (and
+    UnitMuskingum's convolution as a pass of its own before them); RR_WAVE=1 and RR_DIRECT=0 move the same calls onto the time-tiled
+    kernel and the record path.  (The switches are read when route() creates the plan.)  Each ends in the reference's results."""
+    from river_route_amd import engine
+    monkeypatch.setenv(*switch.split('='))
+    casts = []
+    resample = engine.resample_cast_dev
+    monkeypatch.setattr(engine, 'resample_cast_dev', lambda *a, **k: (casts.append(a[1:4]), resample(*a, **k))[1])
+    r, got = golden_route(name, case)
+    print(f'{name} {switch}: {len(casts)} resample casts, last kernel {r._plan.last_kernel()}')
+    check_golden(name, case, r, got)
+    if switch == 'RR_WAVE=0':
+        assert len(casts) == 2      # one per file: the plain leg ran
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize('name', GOLDEN_ROUTES)
+def test_refused_arena_allocation_ends_in_the_golden_results(case, monkeypatch, name):
+    """Every device allocation a clean route() makes through the per-file arena (rows, state, outputs), refused in a run of its own
+    (RR_ALLOC_FAIL_AT=k, read when route() creates the plan: k counts the process's allocations from there): the file takes the host
+    path, no exception leaves route(), the results are the reference's and nothing stays allocated once the plan is closed.  The
+    allocations outside the arena -- plan creation, the reservations of the calls -- are not in the set: a refusal there is an error the
+    routers hand on.  (More than 100 arena allocations: the first 100.)"""
+    import gc
+    from river_route_amd.engine import dev_alloc_stats
+    from river_route_amd.routers import _device
+    from test_gpu_devbuf import arm
+    made_at, refused_at = [], []
+    arena_empty = _device.Arena.empty
+
+    def watched(self, nbytes):
+        made_at.append(dev_alloc_stats()['made'])
+        try:
+            return arena_empty(self, nbytes)
+        except _device.DeviceOutOfMemory:
+            refused_at.append(made_at[-1])
+            raise
+    monkeypatch.setattr(_device.Arena, 'empty', watched)
+
+    def route(k):
+        """One route() with the k-th allocation refused (0: none): ([index of each arena allocation], [of the refused ones])."""
+        del made_at[:], refused_at[:]
+        gc.collect()
+        before = dev_alloc_stats()
+        if k:
+            monkeypatch.setenv('RR_ALLOC_FAIL_AT', str(k))
+        try:
+            r, got = golden_route(name, case)
+        finally:
+            monkeypatch.delenv('RR_ALLOC_FAIL_AT', raising=False)
+            arm(0)
+        check_golden(name, case, r, got)
+        r._plan.close()
+        assert dev_alloc_stats()['live'] == before['live'], (k, dev_alloc_stats(), before)
+        return [m - before['made'] + 1 for m in made_at], [m - before['made'] + 1 for m in refused_at]
+
+    ks, none = route(0)
+    assert len(ks) >= 6 and not none, ks      # two files: rows in, state, rows out at the least
+    print(f'{name}: arena allocations at {ks}')
+    for k in ks[:100]:
+        _, refused = route(k)
+        assert refused == [k], (k, refused)
+
+
 # SURVEY section 8 row f3 on both boxes: the builders are host code (pinned by reference goldens, runs here); on the GPU
 # box (`-m gpu`) the same kernels also drive the HIP convolution against the oracle.
 BOX = pytest.mark.parametrize('box', ['host', pytest.param('gpu_box', marks=pytest.mark.gpu)])

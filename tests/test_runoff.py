@@ -340,7 +340,7 @@ def test_router_with_grid_runoff_files(backend, case, tmp_path, monkeypatch, rou
 @pytest.mark.parametrize('per,cumulative,fused', [(1, False, True), (4, True, True), (3, False, False)])
 def test_router_grid_runoff_through_the_fused_call(case, tmp_path, monkeypatch, per, cumulative, fused):
     """RapidMuskingum on two grid-runoff files of 96 rows at dt_runoff = dt_routing = 900 s: long enough for the time-tiled kernel, so
-    RapidMuskingum._router_device_runoff returns from rr_rapid_route_runoff_dev (arena uploads, dtypes of the CSR arrays,
+    the per-file driver (_device.route_file) returns from rr_rapid_route_runoff_dev (arena uploads, dtypes of the CSR arrays,
     source.flags, float32 means of `per` rows, the final state's download) -- except with three rows per output row, which do not
     divide a record batch of 128: the fused call answers RR_E_UNSUPPORTED and the two-step form runs.  The reference is the same
     router with the oracle engine injected, driven with brute_force volumes for the same grids.  One fused case has
