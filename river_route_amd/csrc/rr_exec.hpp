@@ -181,6 +181,7 @@ struct rr_plan {
     int64_t wave_K = 0;          // ticks per task (multiple of 16); 0 = chosen per call
     Schedule sch;                // prepare_call: the schedule of the call about to start (or running, or just ended)
     int64_t kc_cap = int64_t{1} << 20;      // longest task (record chunks) the device had room for; 0: no record ring fits, the plan streams
+    int64_t nb_cap = kRecMaxLaunchBatches;  // most record batches per launch the device had room for (the ring holds one batch more for each beyond the first)
     TileSet ts{&tp};              // the tiles' device side: tmeta, pmeta, perm, coef {c1row, c2, c3}, the carried state
     DevBuf<int32_t> d_tinv;
     DevBuf<int32_t> d_inner_idx;
@@ -568,7 +569,7 @@ CallShape call_shape(Mode mode, int64_t T, int64_t nsub, const Rows &io, bool st
 // lag ticks later than a headwater's does not widen it.  The ring may take five eighths of the card; a deep network that
 // does not fit gets shorter tasks, then the streaming kernel.
 //
-// The choice is a pure function of the plan, the call's shape and kc_cap (lowered only when the device refuses an
+// The choice is a pure function of the plan, the call's shape, kc_cap and nb_cap (lowered only when the device refuses an
 // allocation), so rr_plan_reserve and the call it prepares for agree on it.
 //
 // host (the host-pointer entry points): the rows reach the time-tiled kernel through the PCIe pipeline's device rings (reserve_core
@@ -632,7 +633,7 @@ Schedule choose_schedule(const rr_plan *P, const CallShape &s)
         // The plain record passes take nb batches per launch in long calls -- the call lengths of pick_KC's long tasks; a shorter call's
         // ring stays as it was -- and the out-pass holds finished batches back until it has nb of them: nb - 1 more batches of ring.  The
         // largest nb whose ring fits the bounds below at the longest task that fits (RR_REC_BATCHES: that many in every call).
-        const int64_t nb_max = P->rec_batches_forced || total >= 16384 ? std::max<int64_t>(1, P->rec_batches) : 1;
+        const int64_t nb_max = P->rec_batches_forced || total >= 16384 ? std::max<int64_t>(1, std::min<int64_t>(P->rec_batches, P->nb_cap)) : 1;
         ok = false;
         // a part of a cut network that feeds another GPU keeps to 64 ticks: every tile level delays its boundary series by one
         // task, and the GPU downstream waits for it (10M reaches on 8 GPUs: whole job 7.2 against 7.1 x 10^11 reach-steps/s in the
@@ -682,7 +683,8 @@ int reserve_core(rr_plan *P, const CallShape &s, Schedule *out)
         if (sch.kernel == Kernel::Direct) return fail(RR_E_ALLOC, "route: the skeleton's record ring does not fit on the device");
         if (sch.kernel == Kernel::Tick) return fail(RR_E_ALLOC, "route: the work rows of the streaming kernel do not fit on the device");
         if (s.members > 0) return fail(RR_E_ALLOC, "route: the record rings of " + std::to_string(s.members) + " ensemble members do not fit on the device");      // (kc_cap is the plan's: a smaller group is the remedy)
-        P->kc_cap = sch.KC / 2;      // shorter tasks, a smaller ring; 0: this plan streams
+        if (sch.rec_nb > 1) P->nb_cap = sch.rec_nb / 2;      // fewer record batches per launch first: the ring loses the batches the out-pass held back
+        else P->kc_cap = sch.KC / 2;      // then shorter tasks, a smaller ring; 0: this plan streams
     }
     int rc = P->d_mrows.reserve(sch.mrows);
     if (!rc) rc = P->d_stage.reserve(sch.stage);

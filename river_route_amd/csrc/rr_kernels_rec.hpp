@@ -24,8 +24,39 @@ constexpr int kRecInThreads = kRecThreads, kRecOutThreads = kRecThreads;      //
 constexpr int kRecInCols = kRecCols, kRecOutCols = kRecCols;                  // columns of a tile of k_rec_in / k_rec_out
 constexpr int kRecRows = 16 * kRecBatch;    // tick-rows of one batch
 // Batches one launch of k_rec_in / k_rec_out walks in a long call (rr_exec.hpp: choose_schedule, session_advance_tile): the rows and
-// records at a batch's edge are read once per launch instead of once per batch, in the same LDS tile.
+// records at a batch's edge are read once per launch instead of once per batch, in the same LDS tile.  Eight by default: 259.8 against
+// 263.9 ms per year at 1M reaches for 4.3 GB more ring, inside three times the parent's spread (profiles/r08_rec_stream_ab.txt): four.
 constexpr int kRecLaunchBatches = 4, kRecMaxLaunchBatches = 8;
+
+// Cache policy of the four access streams of k_rec_in / k_rec_out, one hint per stream: true = non-temporal (the `nt` bit of the
+// global load / store: the line is marked for early eviction), false = the default policy.  Every row and every record of these
+// passes is used once.  A hint changes the instruction's cache bits only, never what a wave issues or in what order (the batch loop
+// of k_rec_in stays sixteen loads, eight stores, a barrier, vmcnt(23) ... vmcnt(8); registers, LDS and scratch are unchanged).  The
+// fused convolution and gridded-runoff in-passes keep the default (kRecStreamsDefault).  Measured at 1M reaches, each hint alone and
+// together (profiles/r08_rec_stream_ab.txt), per year against 263.9 ms:
+//   in_recs   k_rec_in 86.3 -> 84.5 ms, the year -3.8 ms: the records no longer displace the row lines still to be read;
+//   out_recs  k_rec_out 80.8 -> 74.8 ms, the year -5.8 ms, where the discharge goes to a short cyclic sink (bench.py's 128 rows, a
+//             streaming caller's ring): the sink's lines stay in L2 and are overwritten there (273 -> 211 GB written back); with
+//             4,096 sink rows nothing is rewritten in time and the hint changes nothing (293.5 against 292.7 ms);
+//   both      -8.4 ms (255.5): kept.  in_rows: k_rec_in 86.3 -> 101.2 ms, out_rows: k_rec_out 80.8 -> 94.2 ms: both refused.
+struct RecStreamPolicy {
+    bool in_rows;       // k_rec_in: params-order rows, loaded
+    bool in_recs;       // k_rec_in: records, stored
+    bool out_recs;      // k_rec_out: records, loaded
+    bool out_rows;      // k_rec_out: params-order rows (float64 or float32 means), stored
+};
+constexpr RecStreamPolicy kRecStreamsDefault{false, false, false, false};
+constexpr RecStreamPolicy kRecStreams{false, true, true, false};
+template <bool NT, typename T> __device__ __forceinline__ T stream_load(const T *p)
+{
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <bool NT, typename T> __device__ __forceinline__ void stream_store(T *p, T v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
 
 struct RecPermArgs {
     double *rec;
@@ -87,7 +118,7 @@ __device__ __forceinline__ uint32_t ring_chunk(const Div32 &chunks, uint32_t fir
 // BATCH records per column of batch `batch`, from tick-row kRecRows * batch - 15 on (the fused convolution takes two batches at a time).
 // smeta / sscale: the tile's column metadata and scale in LDS (k_rec_in keeps them there: loaded with the rows, no registers
 // held across the stores), or NULL: read from the plan's arrays.
-template <bool SUB, int THREADS = kRecThreads, int BATCH = kRecBatch, bool LDSMETA = false, int COLS = kRecCols>
+template <bool SUB, int THREADS = kRecThreads, int BATCH = kRecBatch, bool LDSMETA = false, int COLS = kRecCols, bool NT = kRecStreamsDefault.in_recs>
 __device__ __forceinline__ void write_records(const RecPermArgs &a, const double *tile, int64_t col0, int64_t batch, int64_t tick_first, int64_t row_first,
                                               const int2 *smeta = nullptr, const double *sscale = nullptr)
 {
@@ -136,7 +167,7 @@ __device__ __forceinline__ void write_records(const RecPermArgs &a, const double
         }
         double2 *dst = reinterpret_cast<double2 *>(a.rec + rec_elem(chunk, a.np, p)) + part;
         typedef double d2 __attribute__((ext_vector_type(2)));
-        *reinterpret_cast<d2 *>(dst) = d2{v0, v1};
+        stream_store<NT>(reinterpret_cast<d2 *>(dst), d2{v0, v1});
     }
 }
 
@@ -205,7 +236,8 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
     auto group_of = [](int t) -> int { return (t / kRecInCols) & (G - 1); };
     auto load = [&](int64_t t, int64_t i) -> double {
         const int64_t off = a.rows.offset(t < 0 ? 0 : (t >= a.T ? a.T - 1 : t)) + i;
-        return IN32 ? (double)f32_from_file(a.rows_in32[off], a.in32_sel) : a.rows.base[off];
+        if constexpr (IN32) return (double)f32_from_file(stream_load<kRecStreams.in_rows>(a.rows_in32 + off), a.in32_sel);
+        else return stream_load<kRecStreams.in_rows>(a.rows.base + off);
     };
     {
         const int c = tid & (kRecInCols - 1), r0 = group_of(tid);
@@ -286,7 +318,7 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
                 if (!SUB || r < need) v[q] = load(row_next + r, i);
             }
         }
-        write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, wscale);
+        write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols, kRecStreams.in_recs>(a, tile, col0, a.batch + b - 1, tick_first, row_first, smeta, wscale);
 #pragma unroll
         for (int q = 0; q < KPT; ++q) {
             const int r = r0 + q * G;
@@ -312,7 +344,7 @@ __global__ __launch_bounds__(kRecInThreads, 4) void k_rec_in(const RecArgsOf<ENS
         const int t = fresh_tid(tid);
         if (t < kRecInCols && col0 + t < a.n && (smeta[t].y & kColInpass)) a.hw_carry[col0 + t] = shw[1][t];      // (written by this thread; a replica writes nothing)
     }
-    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, wscale);
+    write_records<SUB, kRecInThreads, kRecBatch, true, kRecInCols, kRecStreams.in_recs>(a, tile, col0, a.batch + nb - 1, tick_first, row_first, smeta, wscale);
 }
 
 // The in-pass with the unit-hydrograph convolution fused in (UnitHydrograph.py:93-107, direct form): the tile is COMPUTED
@@ -488,7 +520,7 @@ __global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS>
                 const int piece = it * kRecOutThreads + tid;
                 const int k = (piece >> 3) % (kRecBatch + 1), part = piece & 7;
                 const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)((meta[it].y & kLagMask) >> 4) + k);
-                v[it] = reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, meta[it].x))[part];
+                v[it] = stream_load<kRecStreams.out_recs>(reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, meta[it].x)) + part);
             }
         }
 #pragma unroll
@@ -523,7 +555,7 @@ __global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS>
                 const int nsub = SUB ? (int)a.nsub.d : 1;
                 double acc = out(recs[c][o + q * step + nsub - 1]);
                 for (int j = 1; j < (int)a.factor.d; ++j) acc += out(recs[c][o + q * step + j * nsub + nsub - 1]);
-                a.rows32[(q0 + q) * a.rows.ld + io] = f32_to_file((float)(a.factor.d > 1 ? acc / (double)a.factor.d : acc), a.out32_sel);
+                stream_store<kRecStreams.out_rows>(a.rows32 + ((q0 + q) * a.rows.ld + io), f32_to_file((float)(a.factor.d > 1 ? acc / (double)a.factor.d : acc), a.out32_sel));
             }
         } else {
             for (int r = tid / kRecOutCols; r < kRecRows; r += kRecOutThreads / kRecOutCols) {
@@ -532,9 +564,9 @@ __global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS>
                 if (SUB) {
                     uint32_t sub;
                     const uint32_t row = a.nsub.div((uint32_t)tick, sub);
-                    if (sub + 1 == a.nsub.d) a.rows.row(row)[io] = recs[c][o + r];
+                    if (sub + 1 == a.nsub.d) stream_store<kRecStreams.out_rows>(a.rows.row(row) + io, recs[c][o + r]);
                 } else {
-                    a.rows.row(tick)[io] = out(recs[c][o + r]);
+                    stream_store<kRecStreams.out_rows>(a.rows.row(tick) + io, out(recs[c][o + r]));
                 }
             }
         }
@@ -549,7 +581,7 @@ __global__ __launch_bounds__(kRecOutThreads) void k_rec_out(const RecArgsOf<ENS>
             const int2 m = smeta[piece / (kRecBatch * 8)];
             const int k = 1 + (piece >> 3) % kRecBatch, part = piece & 7;
             const uint32_t chunk = ring_chunk(a.rec_chunks, chunk_first, (uint32_t)((m.y & kLagMask) >> 4) + k);
-            v[it] = reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, m.x))[part];
+            v[it] = stream_load<kRecStreams.out_recs>(reinterpret_cast<const d2 *>(a.rec + rec_elem(chunk, a.np, m.x)) + part);
         }
         write_rows(kRecRows * (a.batch + b - 1));
         const int kc = tid >> 3, kp = tid & 7;      // the piece of the last record this thread moves to the front
