@@ -116,6 +116,12 @@ struct AdjointCall {
     int32_t *pslot() const { return reinterpret_cast<int32_t *>(scratch); }      // params order; the engine-order map follows it
     int32_t *slot() const { return pslot() + n; }
     dim3 reduce_grid() const { return dim3((unsigned)((n + kBlock - 1) / kBlock), (unsigned)L.splits, (unsigned)members); }
+    template <bool ENS> AdjMergeRanges<ENS> merge_ranges() const      // what the merges fold: the slab's ranges, of every member
+    {
+        AdjMergeRanges<ENS> r{L.splits};
+        if constexpr (ENS) r.members = members;
+        return r;
+    }
 };
 
 // A check that is an entry point's own: after which shared ones it is tested (the plan's boundary check, the sizes, the lateral rows,
@@ -250,6 +256,17 @@ void adjoint_reduce_args(const AdjointCall &c, Args &r)
     r.n = c.n; r.total_substeps = c.S; r.steps_per_split = c.L.steps_per_split; r.dmax = (int32_t)c.dmax; r.nsub = Div32((uint32_t)c.nsub);
 }
 
+// The kernel forms of a checked call, stated once for both routers: enqueue(ENS, GAUGES) with the two flags as std::bool_constant.  A
+// gauge call with one member runs the single-member kernels, so the single call's bits; a batch call runs the member forms whatever the
+// member count; a plain call the single-member forms.
+template <class Enqueue>
+void adjoint_forms(const AdjointKind &K, const AdjointCall &c, Enqueue enqueue)
+{
+    const bool ens = K.gauges ? c.members > 1 : K.batch;
+    if (K.gauges) ens ? enqueue(std::true_type{}, std::true_type{}) : enqueue(std::false_type{}, std::true_type{});
+    else ens ? enqueue(std::true_type{}, std::false_type{}) : enqueue(std::false_type{}, std::false_type{});
+}
+
 // ---- RapidMuskingum ----
 
 // What a checked call enqueues.  ENS: a batched call (rr_rapid_adjoint_batch_dev) -- the member-batched kernels on grids with a member
@@ -271,20 +288,15 @@ void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double 
     if (grad_out && !GAUGES) {
         const int64_t count = T * n;
         const dim3 g((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192), M);
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_mask_batch, g, dim3(kBlock), 0, st, c.mtape, grad_out, discharge, count, 1.0 / (double)nsub, L.mtape_pitch, out_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_mask, g, dim3(kBlock), 0, st, c.mtape, grad_out, discharge, count, 1.0 / (double)nsub);
+        hipLaunchKernelGGL(k_adj_mask<ENS>, g, dim3(kBlock), 0, st, c.mtape, grad_out, discharge, count, 1.0 / (double)nsub,
+                           args_if<ENS>(AdjMaskMember{L.mtape_pitch, out_pitch}));
         c.rows_between(0, c.mtape, c.egrad, L.mtape_pitch, L.row_pitch);
     }
     if (grad_coef) {
         if (lateral) c.rows_between(0, lateral, c.elat, lat_pitch, L.row_pitch);
         const dim3 g((unsigned)((n + kBlock - 1) / kBlock), M);
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_tape_init_batch, g, dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n,
-                               L.qtape_pitch, c.q0_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_tape_init, g, dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n);
+        hipLaunchKernelGGL(k_adj_tape_init<ENS>, g, dim3(kBlock), 0, st, c.qtape, q0, (const int32_t *)P->d_perm, (const int32_t *)P->d_lag, n,
+                           args_if<ENS>(AdjTapeInitMember{L.qtape_pitch, c.q0_pitch}));
         TickArgsOf<ENS> a{};
         if constexpr (ENS) { a.tape_pitch = L.qtape_pitch; a.in_pitch = L.row_pitch; a.scratch_pitch = L.scratch_pitch; }
         const auto tick = lateral ? (c.one ? k_tick<true, true, ENS> : k_tick<true, false, ENS>) : (c.one ? k_tick<false, true, ENS> : k_tick<false, false, ENS>);
@@ -295,10 +307,8 @@ void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double 
     if (GAUGES && grad_out) {
         const int64_t count = T * c.n_gauges;
         const dim3 g((unsigned)std::min<int64_t>((count + kBlock - 1) / kBlock, 8192), M);
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_mask_batch, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, count, 1.0 / (double)nsub, count, out_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_mask, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, count, 1.0 / (double)nsub);
+        hipLaunchKernelGGL(k_adj_mask<ENS>, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, count, 1.0 / (double)nsub,
+                           args_if<ENS>(AdjMaskMember{count, out_pitch}));
         hipLaunchKernelGGL(k_adj_gauge_fill, grid1(n), dim3(kBlock), 0, st, c.pslot(), n);
         hipLaunchKernelGGL(k_adj_gauge_scatter, grid1(c.n_gauges), dim3(kBlock), 0, st, c.pslot(), c.gauges, c.n_gauges);
         hipLaunchKernelGGL(k_adj_gauge_slots, grid1(n), dim3(kBlock), 0, st, c.slot(), (const int32_t *)c.pslot(), (const int32_t *)P->d_perm, n);
@@ -317,25 +327,18 @@ void rapid_adjoint_enqueue(const AdjointCall &c, const double *q0, const double 
         if constexpr (ENS) { r.qtape_pitch = L.qtape_pitch; r.mtape_pitch = L.mtape_pitch; r.lat_pitch = L.row_pitch; r.slab_pitch = L.slab_pitch; }
         hipLaunchKernelGGL((c.one ? k_adj_reduce<true, ENS> : k_adj_reduce<false, ENS>), c.reduce_grid(), dim3(kBlock), 0, st, r);
     }
-    if (grad_coef || grad_q0) {
-        if constexpr (ENS)      // without dL/dq0 only member 0's blocks have work: they fold every member's ranges
-            hipLaunchKernelGGL(k_adj_merge_batch, dim3((unsigned)((n + kBlock - 1) / kBlock), grad_q0 ? M : 1u), dim3(kBlock), 0, st,
-                               (const double *)c.slab, L.splits, c.members, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2, (const double *)P->d_c3, n, S,
-                               (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0, L.mtape_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_merge, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, (const double *)c.mtape,
-                               (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
-                               (const double *)P->d_c3, n, S, (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0);
+    if (grad_coef || grad_q0) {      // without dL/dq0 only member 0's blocks have work: they fold every member's ranges
+        dim3 g = grid1(n);
+        g.y = grad_q0 ? M : 1u;
+        hipLaunchKernelGGL(k_adj_merge<ENS>, g, dim3(kBlock), 0, st, (const double *)c.slab, c.merge_ranges<ENS>(), (const double *)c.mtape,
+                           (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const int32_t *)P->d_perm, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, S, (int32_t)c.dmax, lateral ? 1 : 0, grad_coef, grad_q0,
+                           args_if<ENS>(AdjMergeMember{L.mtape_pitch}));
     }
     if (grad_lateral) {
         const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)std::min<int64_t>(T, 65535), M);
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_rows_batch, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const double *)P->d_c4, n, T, nsub, S, (int32_t)c.dmax, L.row_pitch, L.mtape_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_rows, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag, (const double *)P->d_c4, n,
-                               T, nsub, S, (int32_t)c.dmax);
+        hipLaunchKernelGGL(k_adj_rows<ENS>, g, dim3(kBlock), 0, st, c.egrad, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                           (const double *)P->d_c4, n, T, nsub, S, (int32_t)c.dmax, args_if<ENS>(AdjRowsMember{L.row_pitch, L.mtape_pitch}));
         c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
     }
 }
@@ -353,11 +356,9 @@ int rapid_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const d
         {AdjOwn::GradOut, K.gauges && c.discharge && !c.grad_out, RR_E_INVALID, ": discharge_g and grad_out_g come together or not at all"},
         {AdjOwn::GradOut, grad_lateral && !lateral, RR_E_INVALID, ": grad_lateral of a channel-only call (lateral is NULL)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-    if (K.gauges) {      // one member: the single-member kernels, so the single call's bits
-        if (c.members > 1) rapid_adjoint_enqueue<true, true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
-        else rapid_adjoint_enqueue<false, true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
-    } else if (K.batch) rapid_adjoint_enqueue<true>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
-    else rapid_adjoint_enqueue<false>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    adjoint_forms(K, c, [&](auto ens, auto gauges) {
+        rapid_adjoint_enqueue<decltype(ens)::value, decltype(gauges)::value>(c, q0, grad_qfinal, grad_lateral, grad_q0, grad_coef);
+    });
     HIPCHK(hipGetLastError());
     return RR_OK;
 }
@@ -382,26 +383,19 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
     double *const qch = c.scratch + 2 * n, *const qch0e = qch + n, *const gcf = qch0e + n, *const gff = gcf + n;      // member m's: m scratch pitches on
     const bool tape = grad_coef && ni > 0;
     const unsigned col_blocks = (unsigned)((n + kBlock - 1) / kBlock), row_blocks = (unsigned)std::min<int64_t>(T, 65535);
+    dim3 inner_grid = grid1(ni);      // the kernels over the inner reaches
+    inner_grid.y = M;
     // dL/d(discharge) with the forward's output rule in params order (in the mu tape's memory, free until the reverse ticks), then engine order
     if (grad_out && !GAUGES) {
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_mask_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
-                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub, L.mtape_pitch, out_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_mask_unit, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
-                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub);
+        hipLaunchKernelGGL((k_adj_mask_unit<ENS, false>), dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.mtape, grad_out, discharge,
+                           UnitMaskColumns<false>{P->d_inv}, (const int32_t *)P->d_child_ptr, n, T, 1.0 / (double)nsub,
+                           args_if<ENS>(UnitMaskMember{L.mtape_pitch, out_pitch}));
         c.rows_between(0, c.mtape, c.egrad, L.mtape_pitch, L.row_pitch);
     }
     if (ni > 0 && (tape || grad_qch_final || grad_qfull_final)) {
-        if constexpr (ENS) {
-            dim3 g = grid1(ni);
-            g.y = M;
-            hipLaunchKernelGGL(k_adj_unit_in_batch, g, dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff,
-                               grad_qch_final, grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni,
-                               L.qtape_pitch, L.scratch_pitch, c.state_pitch);
-        } else
-            hipLaunchKernelGGL(k_adj_unit_in, grid1(ni), dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff,
-                               grad_qch_final, grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni);
+        hipLaunchKernelGGL(k_adj_unit_in<ENS>, inner_grid, dim3(kBlock), 0, st, c.qtape, qch, qch0e, tape ? q_full0 : nullptr, q_ch0, gcf, gff,
+                           grad_qch_final, grad_qfull_final, (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, n, (int32_t)ni,
+                           args_if<ENS>(UnitInMember{L.qtape_pitch, L.scratch_pitch, c.state_pitch}));
     }
     if (tape) {      // k_tick_unit on its one-weight branch
         c.rows_between(0, lateral, c.elat, lat_pitch, L.row_pitch);
@@ -418,13 +412,9 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
     // enqueued already.  With no inner reach the row pass still reads both.
     if (GAUGES && grad_out) {
         const dim3 g((unsigned)((c.n_gauges + kBlock - 1) / kBlock), row_blocks, M);
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_mask_unit_gauges_batch, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, c.gauges,
-                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, c.n_gauges, T, 1.0 / (double)nsub, T * c.n_gauges,
-                               out_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_mask_unit_gauges, g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge, c.gauges,
-                               (const int32_t *)P->d_inv, (const int32_t *)P->d_child_ptr, c.n_gauges, T, 1.0 / (double)nsub);
+        hipLaunchKernelGGL((k_adj_mask_unit<ENS, true>), g, dim3(kBlock), 0, st, c.gblock(), grad_out, discharge,
+                           UnitMaskColumns<true>{c.gauges, P->d_inv}, (const int32_t *)P->d_child_ptr, c.n_gauges, T, 1.0 / (double)nsub,
+                           args_if<ENS>(UnitMaskMember{T * c.n_gauges, out_pitch}));
         hipLaunchKernelGGL(k_adj_gauge_fill, grid1(n), dim3(kBlock), 0, st, c.pslot(), n);
         hipLaunchKernelGGL(k_adj_gauge_scatter, grid1(c.n_gauges), dim3(kBlock), 0, st, c.pslot(), c.gauges, c.n_gauges);
         hipLaunchKernelGGL(k_adj_gauge_slots, grid1(n), dim3(kBlock), 0, st, c.slot(), (const int32_t *)c.pslot(), (const int32_t *)P->d_perm, n);
@@ -449,51 +439,22 @@ void unit_adjoint_enqueue(const AdjointCall &c, int64_t ni, const double *q_ch0,
         }
         hipLaunchKernelGGL((c.one ? k_adj_reduce_unit<true, ENS> : k_adj_reduce_unit<false, ENS>), c.reduce_grid(), dim3(kBlock), 0, st, r);
     }
-    if (grad_coef) {
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_merge_unit_batch, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, c.members,
-                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_perm, n, grad_coef);
-        else
-            hipLaunchKernelGGL(k_adj_merge_unit, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, L.splits, (const int32_t *)P->d_child_ptr,
-                               (const int32_t *)P->d_perm, n, grad_coef);
+    if (grad_coef)
+        hipLaunchKernelGGL(k_adj_merge_unit<ENS>, grid1(n), dim3(kBlock), 0, st, (const double *)c.slab, c.merge_ranges<ENS>(),
+                           (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_perm, n, grad_coef);
+    if (grad_qch0 || grad_qfull0)
+        hipLaunchKernelGGL(k_adj_state_unit<ENS>, inner_grid, dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
+                           (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
+                           (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax, args_if<ENS>(UnitStateMember{L.mtape_pitch}));
+    if (grad_lateral) {      // a gauge call's blocks are read here for the last time: the permutation after it takes their rows back
+        UnitRowsCotangent<GAUGES> cot{c.egrad_out()};
+        if constexpr (GAUGES) { cot.slot = c.slot(); cot.n_gauges = c.n_gauges; }
+        hipLaunchKernelGGL((k_adj_rows_unit<ENS, GAUGES>), dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, cot,
+                           grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
+                           (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
+                           nsub, S, (int32_t)c.dmax, args_if<ENS>(UnitRowsMember{L.row_pitch, L.scratch_pitch, L.mtape_pitch}));
+        c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
     }
-    if (grad_qch0 || grad_qfull0) {
-        if constexpr (ENS) {
-            dim3 g = grid1(ni);
-            g.y = M;
-            hipLaunchKernelGGL(k_adj_state_unit_batch, g, dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
-                               (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
-                               (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax, L.mtape_pitch);
-        } else
-            hipLaunchKernelGGL(k_adj_state_unit, grid1(ni), dim3(kBlock), 0, st, grad_qch0, grad_qfull0, (const double *)c.mtape,
-                               (const int32_t *)P->d_inner_pos, (const int32_t *)P->d_lag, (const int32_t *)P->d_adj_down, (const double *)P->d_c2,
-                               (const double *)P->d_c3, n, (int32_t)ni, S, (int32_t)c.dmax);
-    }
-    if (grad_lateral && GAUGES) {      // the blocks are read here for the last time: the permutation after it takes their rows back
-        const double *const gff_rows = grad_qfull_final ? (const double *)gff : nullptr;
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_rows_unit_gauges_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
-                               (const int32_t *)c.slot(), c.n_gauges, gff_rows, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
-                               nsub, S, (int32_t)c.dmax, L.row_pitch, L.scratch_pitch, L.mtape_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_rows_unit_gauges, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
-                               (const int32_t *)c.slot(), c.n_gauges, gff_rows, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
-                               nsub, S, (int32_t)c.dmax);
-    } else if (grad_lateral) {
-        if constexpr (ENS)
-            hipLaunchKernelGGL(k_adj_rows_unit_batch, dim3(col_blocks, row_blocks, M), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
-                               grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
-                               nsub, S, (int32_t)c.dmax, L.row_pitch, L.scratch_pitch, L.mtape_pitch);
-        else
-            hipLaunchKernelGGL(k_adj_rows_unit, dim3(col_blocks, row_blocks), dim3(kBlock), 0, st, c.egrad, c.egrad_out(),
-                               grad_qfull_final ? (const double *)gff : nullptr, (const double *)c.mtape, (const int32_t *)P->d_lag,
-                               (const int32_t *)P->d_child_ptr, (const int32_t *)P->d_adj_down, (const double *)P->d_w, (const double *)P->d_c2, n, T,
-                               nsub, S, (int32_t)c.dmax);
-    }
-    if (grad_lateral) c.rows_between(1, c.egrad, grad_lateral, L.row_pitch, lat_pitch);
 }
 
 int unit_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const double *q_ch0, const double *q_full0, const double *grad_qch_final,
@@ -518,13 +479,10 @@ int unit_adjoint(const char *who, const AdjointKind &K, AdjointCall &c, const do
          K.gauges ? ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch >= T * n)"
                   : ": a member pitch shorter than one member's states or rows (state_pitch: 0 or >= n_inner; lat_pitch, out_pitch >= T * n)"}});
     if (rc) return rc == kAdjNothing ? RR_OK : rc;
-    if (K.gauges) {      // one member: the single-member kernels, so the single call's bits
-        if (c.members > 1)
-            unit_adjoint_enqueue<true, true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
-        else
-            unit_adjoint_enqueue<false, true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
-    } else if (K.batch) unit_adjoint_enqueue<true>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
-    else unit_adjoint_enqueue<false>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral, grad_qch0, grad_qfull0, grad_coef);
+    adjoint_forms(K, c, [&](auto ens, auto gauges) {
+        unit_adjoint_enqueue<decltype(ens)::value, decltype(gauges)::value>(c, ni, q_ch0, q_full0, grad_qch_final, grad_qfull_final, grad_lateral,
+                                                                            grad_qch0, grad_qfull0, grad_coef);
+    });
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

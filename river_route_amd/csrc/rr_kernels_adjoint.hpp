@@ -16,7 +16,8 @@
 // slab and scratch rows at member pitches (64-bit element counts).  The templated kernels take a trailing ENS flag and an args
 // struct with the pitches appended, and form every index as (ENS ? index + offset : index), so their single-member instantiations
 // are the code they were (rr_kernels_tick.hpp: TickEnsArgs); the member is blockIdx.y, in the reduction, whose y is the sub-step
-// range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling that runs the same body on the member's pointers.
+// range, blockIdx.z.  The plain one-pass kernels take a leading ENS flag, scalar parameters and, last, what the member form adds
+// (ArgsIf below); their body is a __forceinline__ function that the member form runs on the member's pointers.
 //
 // Gauge form (rr_rapid_adjoint_gauges_dev): dL/d(discharge) is given at G gauged reaches only.  The reverse
 // tick takes a trailing GAUGES flag and an args struct with the slot map appended: a position reads slot[p] and, where that is >= 0,
@@ -25,6 +26,20 @@
 #pragma once
 
 namespace {
+
+// The last parameter of a one-pass kernel: the pitches its member form takes besides the plain form's arguments, and nothing in the
+// plain form.  The plain parameters stay scalars in one order for all forms and the empty struct comes last, where it moves no
+// argument: anywhere else it takes eight bytes and moves every later offset, and one args struct in place of the scalars changes the
+// kernarg loads of every form.  What a form adds in the middle of the list rides in a small struct with its neighbour instead
+// (AdjMergeRanges, UnitMaskColumns, UnitRowsCotangent), which lays the arguments out as scalars would
+// (profiles/adjoint_kernels_refactor_ab.md).
+struct NoArgs {};
+template <bool ON, class A> using ArgsIf = typename std::conditional<ON, A, NoArgs>::type;
+template <bool ON, class A> ArgsIf<ON, A> args_if(const A &a)
+{
+    if constexpr (ON) return a;
+    else return {};
+}
 
 struct AdjTickArgs {
     const int32_t *lag;        // [n] engine order (no boundary flags: the adjoint refuses partitioned plans)
@@ -113,16 +128,14 @@ __device__ __forceinline__ void adj_tape_init(double *qtape, const double *q0, c
     if (p >= n) return;
     qtape[(int64_t)((lag[p] & kLagMask) + 1) * n + p] = q0[perm[p]];
 }
+// ENS: member blockIdx.y, its tape at tape_pitch, its q0 at q0_pitch (0: one q0 for every member)
+struct AdjTapeInitMember { int64_t tape_pitch, q0_pitch; };
+template <bool ENS>
 __global__ __launch_bounds__(kBlock) void k_adj_tape_init(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag,
-                                                          int64_t n)
+                                                          int64_t n, const ArgsIf<ENS, AdjTapeInitMember> mp)
 {
+    if constexpr (ENS) { qtape += (int64_t)blockIdx.y * mp.tape_pitch; q0 += (int64_t)blockIdx.y * mp.q0_pitch; }
     adj_tape_init(qtape, q0, perm, lag, n);
-}
-// member blockIdx.y: its tape at tape_pitch, its q0 at q0_pitch (0: one q0 for every member)
-__global__ __launch_bounds__(kBlock) void k_adj_tape_init_batch(double *qtape, const double *q0, const int32_t *perm, const int32_t *lag,
-                                                                int64_t n, int64_t tape_pitch, int64_t q0_pitch)
-{
-    adj_tape_init(qtape + (int64_t)blockIdx.y * tape_pitch, q0 + (int64_t)blockIdx.y * q0_pitch, perm, lag, n);
 }
 
 // dL/d(discharge) in params order with the forward's clamp and mean applied: the discharge row is max(mean, 0), so a value
@@ -132,17 +145,17 @@ __device__ __forceinline__ void adj_mask(double *dst, const double *grad_out, co
     for (int64_t k = (int64_t)blockIdx.x * kBlock + threadIdx.x; k < count; k += (int64_t)gridDim.x * kBlock)
         dst[k] = discharge[k] > 0.0 ? grad_out[k] * inv_nsub : 0.0;
 }
+// ENS: member blockIdx.y, its destination rows at dst_pitch, its discharge and dL/d(discharge) rows at row_pitch
+struct AdjMaskMember { int64_t dst_pitch, row_pitch; };
+template <bool ENS>
 __global__ __launch_bounds__(kBlock) void k_adj_mask(double *dst, const double *grad_out, const double *discharge, int64_t count,
-                                                     double inv_nsub)
+                                                     double inv_nsub, const ArgsIf<ENS, AdjMaskMember> mp)
 {
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        dst += m * mp.dst_pitch; grad_out += m * mp.row_pitch; discharge += m * mp.row_pitch;
+    }
     adj_mask(dst, grad_out, discharge, count, inv_nsub);
-}
-// member blockIdx.y: its destination rows at dst_pitch, its discharge and dL/d(discharge) rows at row_pitch
-__global__ __launch_bounds__(kBlock) void k_adj_mask_batch(double *dst, const double *grad_out, const double *discharge, int64_t count,
-                                                           double inv_nsub, int64_t dst_pitch, int64_t row_pitch)
-{
-    const int64_t m = blockIdx.y;
-    adj_mask(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, count, inv_nsub);
 }
 
 // The slot map of a gauge call, three launches in stream order: pslot[n] (params order) filled with -1, pslot[gauges[j]] = j, then
@@ -247,24 +260,27 @@ __device__ __forceinline__ void adj_merge(const double *slab, int64_t splits, co
         grad_q0[i] = v;
     }
 }
-__global__ __launch_bounds__(kBlock) void k_adj_merge(const double *slab, int64_t splits, const double *mtape, const int32_t *lag,
+// ENS: member blockIdx.y writes its own dL/dq0 row (grad_q0[members][n]) from its mu tape at tape_pitch.  The coefficient gradients
+// are one sum over the members: the slab [members][splits][4][n] is contiguous (adjoint_layout), so the blocks of member 0 fold all
+// members x splits ranges in storage order -- members ascending, within a member the ranges in order -- and the others leave
+// grad_coef alone.
+template <bool ENS> struct AdjMergeRanges { int64_t splits; };      // the ranges a merge folds: splits, or splits x members
+template <> struct AdjMergeRanges<true> { int64_t splits, members; };
+struct AdjMergeMember { int64_t tape_pitch; };
+template <bool ENS>
+__global__ __launch_bounds__(kBlock) void k_adj_merge(const double *slab, const AdjMergeRanges<ENS> r, const double *mtape, const int32_t *lag,
                                                       const int32_t *down, const int32_t *perm, const double *c2, const double *c3,
                                                       int64_t n, int64_t total_substeps, int32_t dmax, int has_lateral,
-                                                      double *grad_coef, double *grad_q0)
+                                                      double *grad_coef, double *grad_q0, const ArgsIf<ENS, AdjMergeMember> mp)
 {
-    adj_merge(slab, splits, mtape, lag, down, perm, c2, c3, n, total_substeps, dmax, has_lateral, grad_coef, grad_q0);
-}
-// Member blockIdx.y writes its own dL/dq0 row (grad_q0[members][n]) from its mu tape.  The coefficient gradients are one sum over
-// the members: the slab [members][splits][4][n] is contiguous (adjoint_layout), so the blocks of member 0 fold all members x splits
-// ranges in storage order -- members ascending, within a member the ranges in order -- and the others leave grad_coef alone.
-__global__ __launch_bounds__(kBlock) void k_adj_merge_batch(const double *slab, int64_t splits, int64_t members, const double *mtape,
-                                                            const int32_t *lag, const int32_t *down, const int32_t *perm, const double *c2,
-                                                            const double *c3, int64_t n, int64_t total_substeps, int32_t dmax,
-                                                            int has_lateral, double *grad_coef, double *grad_q0, int64_t tape_pitch)
-{
-    const int64_t m = blockIdx.y;
-    adj_merge(slab, splits * members, mtape + m * tape_pitch, lag, down, perm, c2, c3, n, total_substeps, dmax, has_lateral,
-              m == 0 ? grad_coef : nullptr, grad_q0 ? grad_q0 + m * n : nullptr);
+    int64_t ranges = r.splits;
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        ranges *= r.members; mtape += m * mp.tape_pitch;
+        if (m != 0) grad_coef = nullptr;
+        if (grad_q0) grad_q0 += m * n;
+    }
+    adj_merge(slab, ranges, mtape, lag, down, perm, c2, c3, n, total_substeps, dmax, has_lateral, grad_coef, grad_q0);
 }
 
 // dL/dql[t, p] = c4dt[p] * sum of mu over the sub-steps of row t, engine order (the rows then go to params order through the
@@ -282,17 +298,15 @@ __device__ __forceinline__ void adj_rows(double *dst, const double *mtape, const
         dst[t * n + p] = c * m;
     }
 }
+// ENS: member blockIdx.z (y walks the rows), its gradient rows at dst_pitch, its mu tape at tape_pitch
+struct AdjRowsMember { int64_t dst_pitch, tape_pitch; };
+template <bool ENS>
 __global__ __launch_bounds__(kBlock) void k_adj_rows(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
-                                                     int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
+                                                     int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax,
+                                                     const ArgsIf<ENS, AdjRowsMember> mp)
 {
+    if constexpr (ENS) { dst += (int64_t)blockIdx.z * mp.dst_pitch; mtape += (int64_t)blockIdx.z * mp.tape_pitch; }
     adj_rows(dst, mtape, lag, c4, n, T, nsub, total_substeps, dmax);
-}
-// member blockIdx.z (y walks the rows): its gradient rows at dst_pitch, its mu tape at tape_pitch
-__global__ __launch_bounds__(kBlock) void k_adj_rows_batch(double *dst, const double *mtape, const int32_t *lag, const double *c4, int64_t n,
-                                                           int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax, int64_t dst_pitch,
-                                                           int64_t tape_pitch)
-{
-    adj_rows(dst + (int64_t)blockIdx.z * dst_pitch, mtape + (int64_t)blockIdx.z * tape_pitch, lag, c4, n, T, nsub, total_substeps, dmax);
 }
 
 }  // namespace

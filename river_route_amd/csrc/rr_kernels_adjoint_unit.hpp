@@ -20,16 +20,18 @@
 // share every read-only plan array; member m owns a q tape, a mu tape, engine-order lateral and gradient rows, slab and six scratch
 // rows at member pitches (64-bit element counts).  The templated kernels take a trailing ENS flag and an args struct with the pitches
 // appended and form every index as (ENS ? index + offset : index); the member is blockIdx.y, in the reduction, whose y is the
-// sub-step range, blockIdx.z.  The plain one-pass kernels have a *_batch sibling on the member's pointers: three share a
-// __forceinline__ body with their kernel, two (rows, merge) repeat its statements (see k_adj_merge_unit_batch).
+// sub-step range, blockIdx.z.  The plain one-pass kernels take a leading ENS flag and, last, the member form's pitches (ArgsIf in
+// rr_kernels_adjoint.hpp); the member's offsets go onto the pointers first, behind `if constexpr (ENS)`, and the statements that
+// follow are written once for both forms.
 //
 // Gauge form (rr_unit_adjoint_gauges_dev): dL/d(discharge) is given at G gauged reaches only, as masked (T, G)
 // blocks, and the slot map of rr_kernels_adjoint.hpp (k_adj_gauge_fill / _scatter / _slots) says which column a position reads.  What
-// differs from the Rapid gauge form is the headwater: its cotangent passes into dL/d(lateral) as it is, so the mask
-// (k_adj_mask_unit_gauges) needs the position of every gauge and the row pass (k_adj_rows_unit_gauges) reads the block too, not only
-// the reverse tick (k_adj_tick_unit with a trailing GAUGES flag).  Every other position starts from 0.0, which is what the dense form
-// reads there, so the sums are the dense call's on the same values.  The existing kernels are not touched: the gauge kernels repeat
-// the statements of theirs (section 12e: a shared inlined body reordered the single-member kernels).
+// differs from the Rapid gauge form is the headwater: its cotangent passes into dL/d(lateral) as it is, so the mask needs the
+// position of every gauge and the row pass reads the block too, not only the reverse tick: k_adj_mask_unit and k_adj_rows_unit take
+// a GAUGES flag after ENS, k_adj_tick_unit a trailing one.  Every other position starts from 0.0, which is what the dense form reads
+// there, so the sums are the dense call's on the same values.  What a gauge form reads besides the dense form's arguments stands
+// where the separate gauge kernels had it, in a small struct with its neighbour (UnitMaskColumns, UnitRowsCotangent), and the
+// statements are the dense form's but for the reads behind `if constexpr (GAUGES)`.
 #pragma once
 
 namespace {
@@ -114,65 +116,33 @@ __global__ __launch_bounds__(kBlock) void k_adj_tick_unit(const UnitAdjTickArgsO
 
 // dL/d(discharge) in params order with the forward's output rule applied: an inner reach's row is max(mean, 0), a headwater's is
 // its lateral inflow as it is.  One column per lane, rows strided over blockIdx.y.
-__device__ __forceinline__ void adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
-                                              const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
+// GAUGES: grad_out and discharge are (T, n), n the number of gauges, column j being reach gauges[j]; the masked block (dst, dense)
+// stays in gauge order.  gauges[] is not range-checked here: the caller vouches for distinct indices in [0, n_reaches).
+// ENS: member blockIdx.z, its destination rows at dst_pitch (a gauge call's blocks are adjacent: T * n), its discharge and
+// dL/d(discharge) rows at row_pitch.
+struct UnitMaskMember { int64_t dst_pitch, row_pitch; };
+template <bool GAUGES> struct UnitMaskColumns { const int32_t *inv; };      // the engine position of column i: inv[i], or inv[gauges[i]]
+template <> struct UnitMaskColumns<true> { const int32_t *gauges, *inv; };
+template <bool ENS, bool GAUGES>
+__global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const double *grad_out, const double *discharge,
+                                                          const UnitMaskColumns<GAUGES> col, const int32_t *child_ptr, int64_t n, int64_t T,
+                                                          double inv_nsub, const ArgsIf<ENS, UnitMaskMember> mp)
 {
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.z;
+        dst += m * mp.dst_pitch; grad_out += m * mp.row_pitch; discharge += m * mp.row_pitch;
+    }
     const int64_t i = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (i >= n) return;
-    const int32_t p = inv[i];
+    int32_t p;
+    if constexpr (GAUGES) p = col.inv[col.gauges[i]];
+    else p = col.inv[i];
     const bool hw = child_ptr[p] == child_ptr[p + 1];
     for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
         const int64_t k = t * n + i;
         const double g = grad_out[k];
         dst[k] = hw ? g : (discharge[k] > 0.0 ? g * inv_nsub : 0.0);
     }
-}
-__global__ __launch_bounds__(kBlock) void k_adj_mask_unit(double *dst, const double *grad_out, const double *discharge, const int32_t *inv,
-                                                          const int32_t *child_ptr, int64_t n, int64_t T, double inv_nsub)
-{
-    adj_mask_unit(dst, grad_out, discharge, inv, child_ptr, n, T, inv_nsub);
-}
-// member blockIdx.z (y walks the rows): its destination rows at dst_pitch, its discharge and dL/d(discharge) rows at row_pitch
-__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_batch(double *dst, const double *grad_out, const double *discharge,
-                                                                const int32_t *inv, const int32_t *child_ptr, int64_t n, int64_t T,
-                                                                double inv_nsub, int64_t dst_pitch, int64_t row_pitch)
-{
-    const int64_t m = blockIdx.z;
-    adj_mask_unit(dst + m * dst_pitch, grad_out + m * row_pitch, discharge + m * row_pitch, inv, child_ptr, n, T, inv_nsub);
-}
-
-// The gauge form: grad_out and discharge are (T, n_gauges), column j being reach gauges[j]; the masked block (dst, dense, T x
-// n_gauges) stays in gauge order.  One gauge per lane, rows strided over blockIdx.y; the expression per element is adj_mask_unit's.
-// gauges[] is not range-checked here: the caller vouches for distinct indices in [0, n).
-__device__ __forceinline__ void adj_mask_unit_gauges(double *dst, const double *grad_out, const double *discharge, const int32_t *gauges,
-                                                     const int32_t *inv, const int32_t *child_ptr, int64_t n_gauges, int64_t T, double inv_nsub)
-{
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= n_gauges) return;
-    const int32_t p = inv[gauges[j]];
-    const bool hw = child_ptr[p] == child_ptr[p + 1];
-    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
-        const int64_t k = t * n_gauges + j;
-        const double g = grad_out[k];
-        dst[k] = hw ? g : (discharge[k] > 0.0 ? g * inv_nsub : 0.0);
-    }
-}
-__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_gauges(double *dst, const double *grad_out, const double *discharge,
-                                                                 const int32_t *gauges, const int32_t *inv, const int32_t *child_ptr,
-                                                                 int64_t n_gauges, int64_t T, double inv_nsub)
-{
-    adj_mask_unit_gauges(dst, grad_out, discharge, gauges, inv, child_ptr, n_gauges, T, inv_nsub);
-}
-// member blockIdx.z (y walks the rows): its block at dst_pitch (T * n_gauges: the blocks are adjacent), its discharge_g and grad_out_g
-// at gauge_pitch
-__global__ __launch_bounds__(kBlock) void k_adj_mask_unit_gauges_batch(double *dst, const double *grad_out, const double *discharge,
-                                                                       const int32_t *gauges, const int32_t *inv, const int32_t *child_ptr,
-                                                                       int64_t n_gauges, int64_t T, double inv_nsub, int64_t dst_pitch,
-                                                                       int64_t gauge_pitch)
-{
-    const int64_t m = blockIdx.z;
-    adj_mask_unit_gauges(dst + m * dst_pitch, grad_out + m * gauge_pitch, discharge + m * gauge_pitch, gauges, inv, child_ptr, n_gauges, T,
-                         inv_nsub);
 }
 
 // Inner-indexed vectors to engine positions: the tape's first rows (q_full0 where the reach below reads its "old" value), the
@@ -192,24 +162,24 @@ __device__ __forceinline__ void adj_unit_in(double *qtape, double *qch, double *
     if (grad_qch_final) gcf[p] = grad_qch_final[k];
     if (grad_qfull_final) gff[p] = grad_qfull_final[k];
 }
+// ENS: member blockIdx.y, its tape at tape_pitch, its scratch rows (qch, qch0, gcf, gff) at scratch_pitch, its states at state_pitch
+// (0: one pair of states for every member), its final-state gradients [members][n_inner], dense
+struct UnitInMember { int64_t tape_pitch, scratch_pitch, state_pitch; };
+template <bool ENS>
 __global__ __launch_bounds__(kBlock) void k_adj_unit_in(double *qtape, double *qch, double *qch0, const double *q_full0, const double *q_ch0,
                                                         double *gcf, double *gff, const double *grad_qch_final, const double *grad_qfull_final,
-                                                        const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner)
+                                                        const int32_t *inner_pos, const int32_t *lag, int64_t n, int32_t n_inner,
+                                                        const ArgsIf<ENS, UnitInMember> mp)
 {
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y, ms = m * mp.scratch_pitch;
+        qtape += m * mp.tape_pitch; qch += ms; qch0 += ms; gcf += ms; gff += ms;
+        if (q_full0) q_full0 += m * mp.state_pitch;
+        if (q_ch0) q_ch0 += m * mp.state_pitch;
+        if (grad_qch_final) grad_qch_final += m * n_inner;
+        if (grad_qfull_final) grad_qfull_final += m * n_inner;
+    }
     adj_unit_in(qtape, qch, qch0, q_full0, q_ch0, gcf, gff, grad_qch_final, grad_qfull_final, inner_pos, lag, n, n_inner);
-}
-// member blockIdx.y: its tape at tape_pitch, its scratch rows (qch, qch0, gcf, gff) at scratch_pitch, its states at state_pitch
-// (0: one pair of states for every member), its final-state gradients [members][n_inner], dense
-__global__ __launch_bounds__(kBlock) void k_adj_unit_in_batch(double *qtape, double *qch, double *qch0, const double *q_full0,
-                                                              const double *q_ch0, double *gcf, double *gff, const double *grad_qch_final,
-                                                              const double *grad_qfull_final, const int32_t *inner_pos, const int32_t *lag,
-                                                              int64_t n, int32_t n_inner, int64_t tape_pitch, int64_t scratch_pitch,
-                                                              int64_t state_pitch)
-{
-    const int64_t m = blockIdx.y, ms = m * scratch_pitch;
-    adj_unit_in(qtape + m * tape_pitch, qch + ms, qch0 + ms, q_full0 ? q_full0 + m * state_pitch : nullptr,
-                q_ch0 ? q_ch0 + m * state_pitch : nullptr, gcf + ms, gff + ms, grad_qch_final ? grad_qch_final + m * n_inner : nullptr,
-                grad_qfull_final ? grad_qfull_final + m * n_inner : nullptr, inner_pos, lag, n, n_inner);
 }
 
 struct UnitAdjReduceArgs {
@@ -279,34 +249,23 @@ __global__ __launch_bounds__(kBlock) void k_adj_reduce_unit(const UnitAdjReduceA
 }
 
 // Merge of the ranges in order, scattered to params order; zeros on headwaters (their coefficients are never read).
-__global__ __launch_bounds__(kBlock) void k_adj_merge_unit(const double *slab, int64_t splits, const int32_t *child_ptr, const int32_t *perm,
-                                                           int64_t n, double *grad_coef)
-{
-    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const int32_t i = perm[p];
-    double g[3] = {0.0, 0.0, 0.0};
-    if (child_ptr[p] != child_ptr[p + 1])
-        for (int64_t k = 0; k < splits; ++k)
-#pragma unroll
-            for (int c = 0; c < 3; ++c) g[c] += slab[(k * 3 + c) * n + p];
-    grad_coef[i] = g[0]; grad_coef[n + i] = g[1]; grad_coef[2 * n + i] = g[2];
-}
-// The coefficient gradients are one sum over the members: the slab [members][splits][3][n] is contiguous (adjoint_layout), so one
+// ENS: the coefficient gradients are one sum over the members: the slab [members][splits][3][n] is contiguous (adjoint_layout), so one
 // member's worth of blocks folds all members x splits ranges in storage order -- members ascending, within a member its ranges in order.
-// The fold is written out again here, and k_adj_rows_unit_batch's body below, where the other siblings share a __forceinline__ body
-// with their kernel: inlined, these two bodies changed the instruction order of the single-member kernels, whose code section 12e keeps.
-__global__ __launch_bounds__(kBlock) void k_adj_merge_unit_batch(const double *slab, int64_t splits, int64_t members, const int32_t *child_ptr,
-                                                                 const int32_t *perm, int64_t n, double *grad_coef)
+template <bool ENS>
+__global__ __launch_bounds__(kBlock) void k_adj_merge_unit(const double *slab, const AdjMergeRanges<ENS> r, const int32_t *child_ptr,
+                                                           const int32_t *perm, int64_t n, double *grad_coef)
 {
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     const int32_t i = perm[p];
     double g[3] = {0.0, 0.0, 0.0};
-    if (child_ptr[p] != child_ptr[p + 1])
-        for (int64_t k = 0; k < splits * members; ++k)
+    if (child_ptr[p] != child_ptr[p + 1]) {
+        int64_t ranges = r.splits;
+        if constexpr (ENS) ranges *= r.members;
+        for (int64_t k = 0; k < ranges; ++k)
 #pragma unroll
             for (int c = 0; c < 3; ++c) g[c] += slab[(k * 3 + c) * n + p];
+    }
     grad_coef[i] = g[0]; grad_coef[n + i] = g[1]; grad_coef[2 * n + i] = g[2];
 }
 
@@ -325,73 +284,49 @@ __device__ __forceinline__ void adj_state_unit(double *grad_qch0, double *grad_q
         grad_qfull0[k] = d >= 0 ? c2[d] * mtape[(tau - 1) * n + d] : 0.0;
     }
 }
+// ENS: member blockIdx.y, its rows of grad_qch0 / grad_qfull0 [members][n_inner] from its mu tape at tape_pitch
+struct UnitStateMember { int64_t tape_pitch; };
+template <bool ENS>
 __global__ __launch_bounds__(kBlock) void k_adj_state_unit(double *grad_qch0, double *grad_qfull0, const double *mtape, const int32_t *inner_pos,
                                                            const int32_t *lag, const int32_t *down, const double *c2, const double *c3, int64_t n,
-                                                           int32_t n_inner, int64_t total_substeps, int32_t dmax)
+                                                           int32_t n_inner, int64_t total_substeps, int32_t dmax,
+                                                           const ArgsIf<ENS, UnitStateMember> mp)
 {
+    if constexpr (ENS) {
+        const int64_t m = blockIdx.y;
+        mtape += m * mp.tape_pitch;
+        if (grad_qch0) grad_qch0 += m * n_inner;
+        if (grad_qfull0) grad_qfull0 += m * n_inner;
+    }
     adj_state_unit(grad_qch0, grad_qfull0, mtape, inner_pos, lag, down, c2, c3, n, n_inner, total_substeps, dmax);
-}
-// member blockIdx.y: its rows of grad_qch0 / grad_qfull0 [members][n_inner] from its mu tape at tape_pitch
-__global__ __launch_bounds__(kBlock) void k_adj_state_unit_batch(double *grad_qch0, double *grad_qfull0, const double *mtape,
-                                                                 const int32_t *inner_pos, const int32_t *lag, const int32_t *down,
-                                                                 const double *c2, const double *c3, int64_t n, int32_t n_inner,
-                                                                 int64_t total_substeps, int32_t dmax, int64_t tape_pitch)
-{
-    const int64_t m = blockIdx.y;
-    adj_state_unit(grad_qch0 ? grad_qch0 + m * n_inner : nullptr, grad_qfull0 ? grad_qfull0 + m * n_inner : nullptr, mtape + m * tape_pitch,
-                   inner_pos, lag, down, c2, c3, n, n_inner, total_substeps, dmax);
 }
 
 // dL/dl[t, p] in engine order (g and dst may be the same rows: a lane reads its own element before it writes it):
 //   inner      sum over the row's sub-steps of phi[s,p] = g[t,p] + [s=S] gff[p] + c1[d] mu[s,d] + c2[d] mu[s+1,d]
 //   headwater  dL/dout[t,p] + (c1[d] + c2[d]) * sum over the row's sub-steps of mu[s,d]
 // The downstream reach ran sub-step ts one reverse tick before this position's slot for ts, and ts + 1 two ticks before.
-__global__ __launch_bounds__(kBlock) void k_adj_rows_unit(double *dst, const double *g, const double *gff, const double *mtape, const int32_t *lag,
-                                                          const int32_t *child_ptr, const int32_t *down, const double *w, const double *c2,
-                                                          int64_t n, int64_t T, int64_t nsub, int64_t total_substeps, int32_t dmax)
+// GAUGES: g is the masked (T, n_gauges) block and slot the engine-order map, so a position's dL/d(discharge) is the block's element
+// at (t, slot[p]) or 0.0; a headwater needs it as much as an inner reach (its row is dL/dout + ...).  dst and the block are different
+// memory there.
+// ENS: member blockIdx.z (y walks the rows), its gradient rows (dst, g) at row_pitch -- its block T * n_gauges doubles after the
+// previous member's --, its dL/d(q_full final) row at gf_pitch, its mu tape at tape_pitch.
+struct UnitRowsMember { int64_t row_pitch, gf_pitch, tape_pitch; };
+template <bool GAUGES> struct UnitRowsCotangent { const double *g; };      // dL/d(discharge): dense rows, or the blocks and their slot map
+template <> struct UnitRowsCotangent<true> { const double *g; const int32_t *slot; int64_t n_gauges; };
+template <bool ENS, bool GAUGES>
+__global__ __launch_bounds__(kBlock) void k_adj_rows_unit(double *dst, const UnitRowsCotangent<GAUGES> cot, const double *gff, const double *mtape,
+                                                          const int32_t *lag, const int32_t *child_ptr, const int32_t *down, const double *w,
+                                                          const double *c2, int64_t n, int64_t T, int64_t nsub, int64_t total_substeps,
+                                                          int32_t dmax, const ArgsIf<ENS, UnitRowsMember> mp)
 {
-    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
-    const bool hw = child_ptr[p] == child_ptr[p + 1];
-    const int32_t d = down[p];
-    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
-    const double *md = mtape + (d >= 0 ? d : 0);
-    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
-        const double gv = g ? g[t * n + p] : 0.0;
-        double v;
-        if (hw) {
-            double m = 0.0;
-            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
-            v = __builtin_fma(c1d + c2d, m, gv);
-        } else {
-            v = 0.0;
-            for (int64_t k = 0; k < nsub; ++k) {
-                const int64_t ts = t * nsub + k;
-                double phi = gv;
-                if (ts == total_substeps - 1 && gff) phi += gff[p];
-                if (d >= 0) {
-                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
-                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
-                }
-                v += phi;
-            }
-        }
-        dst[t * n + p] = v;
+    const double *g = cot.g;
+    if constexpr (ENS) {
+        const int64_t member = blockIdx.z;
+        dst += member * mp.row_pitch; mtape += member * mp.tape_pitch;
+        if constexpr (GAUGES) { if (g) g += member * T * cot.n_gauges; }
+        else if (g) g += member * mp.row_pitch;
+        if (gff) gff += member * mp.gf_pitch;
     }
-}
-// member blockIdx.z (y walks the rows): its gradient rows (dst, g) at row_pitch, its dL/d(q_full final) row at gf_pitch, its mu tape
-// at tape_pitch; k_adj_rows_unit's statements on the member's pointers
-__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_batch(double *dst, const double *g, const double *gff, const double *mtape,
-                                                                const int32_t *lag, const int32_t *child_ptr, const int32_t *down,
-                                                                const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
-                                                                int64_t total_substeps, int32_t dmax, int64_t row_pitch, int64_t gf_pitch,
-                                                                int64_t tape_pitch)
-{
-    const int64_t member = blockIdx.z;
-    dst += member * row_pitch; mtape += member * tape_pitch;
-    if (g) g += member * row_pitch;
-    if (gff) gff += member * gf_pitch;
     const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
     if (p >= n) return;
     const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
@@ -399,90 +334,12 @@ __global__ __launch_bounds__(kBlock) void k_adj_rows_unit_batch(double *dst, con
     const int32_t d = down[p];
     const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
     const double *md = mtape + (d >= 0 ? d : 0);
+    int32_t j = -1;                                                            // the gauge column of this position
+    if constexpr (GAUGES) j = g ? cot.slot[p] : -1;
     for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
-        const double gv = g ? g[t * n + p] : 0.0;
-        double v;
-        if (hw) {
-            double m = 0.0;
-            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
-            v = __builtin_fma(c1d + c2d, m, gv);
-        } else {
-            v = 0.0;
-            for (int64_t k = 0; k < nsub; ++k) {
-                const int64_t ts = t * nsub + k;
-                double phi = gv;
-                if (ts == total_substeps - 1 && gff) phi += gff[p];
-                if (d >= 0) {
-                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
-                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
-                }
-                v += phi;
-            }
-        }
-        dst[t * n + p] = v;
-    }
-}
-
-// The gauge form of the row pass: g is the masked (T, n_gauges) block and slot the engine-order map, so a position's dL/d(discharge)
-// is the block's element at (t, slot[p]) or 0.0; a headwater needs it as much as an inner reach (its row is dL/dout + ...).  dst and
-// the block are different memory here.  k_adj_rows_unit's statements otherwise (repeated, not shared: see k_adj_merge_unit_batch).
-__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_gauges(double *dst, const double *g, const int32_t *slot, int64_t n_gauges, const double *gff,
-                                                                 const double *mtape, const int32_t *lag, const int32_t *child_ptr, const int32_t *down,
-                                                                 const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
-                                                                 int64_t total_substeps, int32_t dmax)
-{
-    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
-    const bool hw = child_ptr[p] == child_ptr[p + 1];
-    const int32_t d = down[p];
-    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
-    const double *md = mtape + (d >= 0 ? d : 0);
-    const int32_t j = g ? slot[p] : -1;      // the gauge column of this position
-    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
-        const double gv = j >= 0 ? g[t * n_gauges + j] : 0.0;
-        double v;
-        if (hw) {
-            double m = 0.0;
-            if (d >= 0) for (int64_t k = 0; k < nsub; ++k) m += md[(base - (t * nsub + k) - 1) * n];
-            v = __builtin_fma(c1d + c2d, m, gv);
-        } else {
-            v = 0.0;
-            for (int64_t k = 0; k < nsub; ++k) {
-                const int64_t ts = t * nsub + k;
-                double phi = gv;
-                if (ts == total_substeps - 1 && gff) phi += gff[p];
-                if (d >= 0) {
-                    phi = __builtin_fma(c1d, md[(base - ts - 1) * n], phi);
-                    if (ts < total_substeps - 1) phi = __builtin_fma(c2d, md[(base - ts - 2) * n], phi);
-                }
-                v += phi;
-            }
-        }
-        dst[t * n + p] = v;
-    }
-}
-// member blockIdx.z: its gradient rows at row_pitch, its block T * n_gauges doubles after the previous member's, the rest as in
-// k_adj_rows_unit_batch
-__global__ __launch_bounds__(kBlock) void k_adj_rows_unit_gauges_batch(double *dst, const double *g, const int32_t *slot, int64_t n_gauges,
-                                                                       const double *gff, const double *mtape, const int32_t *lag, const int32_t *child_ptr,
-                                                                       const int32_t *down, const double *w, const double *c2, int64_t n, int64_t T, int64_t nsub,
-                                                                       int64_t total_substeps, int32_t dmax, int64_t row_pitch, int64_t gf_pitch, int64_t tape_pitch)
-{
-    const int64_t member = blockIdx.z;
-    dst += member * row_pitch; mtape += member * tape_pitch;
-    if (g) g += member * T * n_gauges;
-    if (gff) gff += member * gf_pitch;
-    const int64_t p = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (p >= n) return;
-    const int64_t base = total_substeps - 1 + dmax - (lag[p] & kLagMask);      // this position's reverse tick of forward sub-step 0
-    const bool hw = child_ptr[p] == child_ptr[p + 1];
-    const int32_t d = down[p];
-    const double c1d = d >= 0 ? w[p] : 0.0, c2d = d >= 0 ? c2[d] : 0.0;
-    const double *md = mtape + (d >= 0 ? d : 0);
-    const int32_t j = g ? slot[p] : -1;      // the gauge column of this position
-    for (int64_t t = blockIdx.y; t < T; t += gridDim.y) {
-        const double gv = j >= 0 ? g[t * n_gauges + j] : 0.0;
+        double gv;
+        if constexpr (GAUGES) gv = j >= 0 ? g[t * cot.n_gauges + j] : 0.0;
+        else gv = g ? g[t * n + p] : 0.0;
         double v;
         if (hw) {
             double m = 0.0;
