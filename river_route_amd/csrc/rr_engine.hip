@@ -275,47 +275,25 @@ int rr_plan_set_coeffs(rr_plan *P, const double *lhs_off_data, const double *c2,
     const int64_t n = H.n;
     if (n > 0 && (!c2 || !c3 || (H.n_edges > 0 && !lhs_off_data)))
         return fail(RR_E_INVALID, "rr_plan_set_coeffs: null coefficient array");
-    std::vector<double> w(n), a2(n), a3(n), a4(n, 0.0);
-    for (int64_t p = 0; p < n; ++p) {
-        const int32_t i = H.perm[p];
-        const int32_t e = H.edge_of[i];
-        w[p] = e >= 0 ? -lhs_off_data[e] : 0.0;
-        a2[p] = c2[i];
-        a3[p] = c3[i];
-        if (c4_dt) a4[p] = c4_dt[i];
-    }
-    // the time-tiled kernel keeps ONE upstream weight per reach; per-edge weights (never produced by the
+    // the plan's coefficient set; the time-tiled kernel keeps ONE upstream weight per reach: per-edge weights (never produced by the
     // reference's callers) fall back to the streaming kernel
-    std::vector<double> c1row(n, 0.0);
-    bool uniform = true;
-    for (int64_t p = 0; p < n; ++p) {
-        const int32_t u0 = H.child_ptr[p], u1 = H.child_ptr[p + 1];
-        if (u1 > u0) c1row[p] = w[u0];
-        for (int32_t u = u0 + 1; u < u1; ++u) if (w[u] != w[u0]) uniform = false;
-    }
-    P->weights_uniform = uniform;
-    rc = dev_upload(P->d_w, w);
-    if (!rc) rc = dev_upload(P->d_c1row_h, c1row);
-    if (!rc && P->tp.ok) {      // the same in tile order; a ghost computes nothing
-        const rr::TilePlan &TP = P->tp;
-        P->h_coef.assign(3 * TP.np, 0.0);
-        for (int64_t p = 0; p < TP.np; ++p) {
-            if (TP.lag[p] & kTileGhostBit) continue;
-            const int32_t i = TP.perm[p];
-            P->h_coef[3 * p] = c1row[H.inv[i]]; P->h_coef[3 * p + 1] = c2[i]; P->h_coef[3 * p + 2] = c3[i];
-        }
+    rr::LagCoef L;
+    std::vector<double> c1row((size_t)n);      // per reach
+    P->weights_uniform = rr::lag_coef(H, lhs_off_data, c2, c3, c4_dt, L, c1row.data()) < 0;
+    rc = dev_upload(P->d_w, L.w);
+    if (!rc) rc = dev_upload(P->d_c1row_h, L.c1row);
+    if (!rc && P->tp.ok) {
+        lay_tile_coef(P, rr::ReachCoef{c1row.data(), c2, c3, 1});
         // which headwaters the in-pass routes depends on their coefficients: the position tables and column metadata again, then the coefficients
         if (!P->meta_lag.empty()) rc = upload_tile_meta(P, P->meta_lag, P->meta_xpos, P->meta_flags);
         if (!rc) rc = upload_tile_coef(P);
     }
-    {   // direct row path: {c1row, c2, c3, c4dt} per column, kept on the host too (rr_plan_set_boundary lays the direct plan out again)
-        P->h_dcoef.assign(4 * (size_t)n, 0.0);
-        for (int64_t i = 0; i < n; ++i) { P->h_dcoef[4 * i] = c1row[H.inv[i]]; P->h_dcoef[4 * i + 1] = c2[i]; P->h_dcoef[4 * i + 2] = c3[i]; P->h_dcoef[4 * i + 3] = c4_dt ? c4_dt[i] : 0.0; }
-        if (!rc) rc = upload_direct_coef(P);
-    }
-    if (!rc) rc = dev_upload(P->d_c2, a2);
-    if (!rc) rc = dev_upload(P->d_c3, a3);
-    if (!rc) rc = dev_upload(P->d_c4, a4);
+    P->h_reach_coef.resize(4 * (size_t)n);      // the plan's one host copy of the set: rr_plan_set_boundary lays tables out from it again
+    rr::reach_coef(n, c1row.data(), c2, c3, c4_dt, P->h_reach_coef.data());
+    if (!rc) rc = upload_direct_coef(P);
+    if (!rc) rc = dev_upload(P->d_c2, L.c2);
+    if (!rc) rc = dev_upload(P->d_c3, L.c3);
+    if (!rc) rc = dev_upload(P->d_c4, L.c4);
     if (!rc && c4_dt && n > 0) {
         hipError_t e = hipMemcpy(P->d_c4_params, c4_dt, (size_t)n * sizeof(double), hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));
@@ -574,8 +552,9 @@ int rr_plan_set_boundary(rr_plan *P, int64_t n_ghost, const int64_t *ghost_reach
         }
         std::vector<int32_t> tflags(TP.tile_flags);      // a tile with a boundary export stores it tick by tick
         for (int64_t e = 0; e < n_export; ++e) tflags[TP.tile_of[TP.inv[export_reaches[e]]]] |= kTileExports;
+        if (!P->h_reach_coef.empty()) lay_tile_coef(P, rr::table_rows(P->h_reach_coef.data()));      // zeros at the new boundary ghosts
         rc = upload_tile_meta(P, tlag, P->export_inside ? TP.xpos : txpos, tflags);
-        if (!rc) rc = upload_tile_coef(P);      // zeros at the boundary ghosts
+        if (!rc) rc = upload_tile_coef(P);
         std::vector<int2> gm((size_t)n_ghost);
         for (int64_t g = 0; g < n_ghost; ++g) { const int32_t p = TP.inv[ghost_reaches[g]]; gm[g] = make_int2(p, TP.lag[p] & kLagMask); }
         DevBuf<int2> ghostmeta;      // the plan keeps the table it has until this one is whole
@@ -833,44 +812,21 @@ int rr_plan_set_member_coeffs(rr_plan *P, int64_t members, const double *lhs_off
     if (pitch < n || (members > 1 && lhs_pitch < H.n_edges))
         return fail(RR_E_INVALID, "rr_plan_set_member_coeffs: a pitch is shorter than a member (pitch >= n, lhs_pitch >= the number of edges)");
     if (!TP.ok) return fail(RR_E_UNSUPPORTED, "rr_plan_set_member_coeffs: the network does not take the time-tiled kernel");
-    // per reach: the edges leaving its upstream reaches, as rr_plan_set_coeffs walks them (the first one's weight is the reach's c1row)
-    std::vector<int32_t> up_ptr((size_t)n + 1, 0), up_edge((size_t)H.n_edges);
-    for (int64_t p = 0; p < n; ++p) {
-        const int32_t i = H.perm[p];
-        up_ptr[i + 1] = H.child_ptr[p + 1] - H.child_ptr[p];
-    }
-    for (int64_t i = 0; i < n; ++i) up_ptr[i + 1] += up_ptr[i];
-    for (int64_t p = 0; p < n; ++p) {
-        const int32_t i = H.perm[p];
-        for (int32_t u = H.child_ptr[p], k = 0; u < H.child_ptr[p + 1]; ++u, ++k) up_edge[up_ptr[i] + k] = H.edge_of[H.perm[u]];
-    }
-    const int64_t np = TP.np;
-    std::vector<double> coef, c1row((size_t)n);
-    try { coef.assign((size_t)(members * 3 * np), 0.0); }
+    const size_t staged = (size_t)(members * 3 * TP.np);
+    std::unique_ptr<double[]> coef;      // the members' tile-order tables, 3 np apart (not filled here: tile_coef writes every position)
+    std::vector<double> c1row, w;        // one member's c1row per reach; its edge weights in lag order
+    try { coef.reset(new double[staged]); c1row.resize((size_t)n); }
     catch (const std::bad_alloc &) { return fail(RR_E_ALLOC, "rr_plan_set_member_coeffs: out of host memory for the members' tables"); }
     for (int64_t m = 0; m < members; ++m) {
-        const double *lhs = lhs_off_data ? lhs_off_data + m * lhs_pitch : nullptr, *m2 = c2 + m * pitch, *m3 = c3 + m * pitch;
-        for (int64_t i = 0; i < n; ++i) {
-            const int32_t e0 = up_ptr[i], e1 = up_ptr[i + 1];
-            const double w0 = e1 > e0 ? -lhs[up_edge[e0]] : 0.0;
-            for (int32_t e = e0 + 1; e < e1; ++e)
-                if (-lhs[up_edge[e]] != w0)
-                    return fail(RR_E_UNSUPPORTED, "rr_plan_set_member_coeffs: member " + std::to_string(m) + " has per-edge weights (two tributaries of reach " + std::to_string(i) +
-                                                      " differ): the time-tiled kernel keeps one upstream weight per reach, and a parameter ensemble has no streaming fallback");
-            c1row[i] = w0;
-        }
-        double *mc = coef.data() + m * 3 * np;
-        for (int64_t p = 0; p < np; ++p) {
-            if (TP.lag[p] & kTileGhostBit) continue;      // a ghost computes nothing: zeros
-            const int32_t i = TP.perm[p];
-            mc[3 * p] = c1row[i]; mc[3 * p + 1] = m2[i]; mc[3 * p + 2] = m3[i];
-        }
-        for (int32_t i : P->ghost_reach) { const int64_t p = TP.inv[i]; mc[3 * p] = mc[3 * p + 1] = mc[3 * p + 2] = 0.0; }      // (upload_tile_coef: a boundary ghost too)
+        const int64_t i = rr::tributary_weight(H, lhs_off_data ? lhs_off_data + m * lhs_pitch : nullptr, w, c1row.data());
+        if (i >= 0) return fail(RR_E_UNSUPPORTED, "rr_plan_set_member_coeffs: member " + std::to_string(m) + " has per-edge weights (two tributaries of reach " + std::to_string(i) +
+                                              " differ): the time-tiled kernel keeps one upstream weight per reach, and a parameter ensemble has no streaming fallback");
+        rr::tile_coef(TP, rr::ReachCoef{c1row.data(), c2 + m * pitch, c3 + m * pitch, 1}, kTileGhostBit, P->ghost_reach, coef.get() + m * 3 * TP.np);
     }
     P->mc_sets = 0;      // until both tables are whole
-    rc = P->d_mcoef.reserve(members * 3 * np);
+    rc = P->d_mcoef.reserve(members * 3 * TP.np);
     if (!rc) rc = P->d_mc4.reserve(members * n);
-    if (!rc) rc = dev_upload(P->d_mcoef, coef);
+    if (!rc) rc = dev_upload(P->d_mcoef.get(), coef.get(), staged);
     if (!rc && n > 0) {
         const hipError_t e = hipMemcpy2D(P->d_mc4, (size_t)n * sizeof(double), c4_dt, (size_t)pitch * sizeof(double), (size_t)n * sizeof(double), (size_t)members, hipMemcpyHostToDevice);
         if (e != hipSuccess) rc = fail(RR_E_HIP, hipGetErrorString(e));

@@ -198,7 +198,7 @@ struct rr_plan {
     DevBuf<double> d_coef_hw;
     DevBuf<double> d_hwcoef;      // [3 n] {c1row, c2, c3} per params column, for k_rec_in
     DevBuf<double> d_hwq;         // [n] k_rec_in's carry: a column's discharge after the last batch turned into records; launch_state_in: the call's initial state
-    std::vector<double> h_coef;      // the same on the host: boundary ghosts of a partitioned network get zeros (upload_tile_coef)
+    std::vector<double> h_coef;      // ts.coef on the host: rr::tile_coef of the plan's set for its boundary ghosts, filled by lay_tile_coef alone
     DevBuf<double> d_esq, d_ess, d_esi;      // the carried state of an ensemble's members, np apart
     int64_t ens_cap = 0;             // members they have room for (rr_plan_reserve_ensemble)
     // Parameter ensembles (rr_plan_set_member_coeffs): member m's {c1row, c2, c3} per position in tile order, zeros at ghosts -- what ts.coef
@@ -234,7 +234,7 @@ struct rr_plan {
     DevBuf<int32_t> d_kholecol;
     DevBuf<int2> d_kholemeta;         // per hole {position in the skeleton, lag}: the out-pass that patches the holes
     DevBuf<int2> d_kghostmeta;        // per boundary ghost {position of the skeleton's ghost that mirrors it, lag}: the in-pass of the ghost series
-    std::vector<double> h_dcoef;         // {c1row, c2, c3, c4dt} per column as rr_plan_set_coeffs got them
+    std::vector<double> h_reach_coef;    // the plan's coefficient set: {c1row, c2, c3, c4dt} per reach (rr::reach_coef): d_dcoef, and what rr_plan_set_boundary lays the tile tables out from again
     int32_t direct_block = 0;            // tile capacity the plan was built with (rr_plan_set_boundary lays the direct plan out again)
     int64_t n_kholes = 0;
     bool in32_big_endian = false, out32_big_endian = false;      // rr_plan_set_row_format: float32 rows as a big-endian file stores them
@@ -288,12 +288,15 @@ void dev_mem_free(void *p)
 namespace {
 
 template <typename T>
-int dev_upload(T *dst, const std::vector<T> &src)
+int dev_upload(T *dst, const T *src, size_t count)
 {
-    if (src.empty()) return RR_OK;
-    HIPCHK(hipMemcpy(dst, src.data(), src.size() * sizeof(T), hipMemcpyHostToDevice));
+    if (count == 0) return RR_OK;
+    HIPCHK(hipMemcpy(dst, src, count * sizeof(T), hipMemcpyHostToDevice));
     return RR_OK;
 }
+
+template <typename T>
+int dev_upload(T *dst, const std::vector<T> &src) { return dev_upload(dst, src.data(), src.size()); }
 
 template <typename T>
 int dev_upload(const DevBuf<T> &dst, const std::vector<T> &src) { return dev_upload(dst.get(), src); }
@@ -355,31 +358,27 @@ int upload_tile_meta(rr_plan *P, const std::vector<int32_t> &lag, const std::vec
     return rc;
 }
 
-// Coefficients in tile order.  A ghost computes nothing: a tile ghost (mirror of a reach another tile owns) and a boundary
-// ghost of a partitioned network (a reach another GPU owns) both publish what arrives in their record, which is what the
-// short tick's three multiply-adds do with zero coefficients.
+// The plan's coefficient set in tile order, on the host: which headwaters the in-pass routes depends on it (upload_tile_meta), so it is
+// laid out before the position tables go up -- by rr_plan_set_coeffs, and by rr_plan_set_boundary for the new boundary ghosts.
+void lay_tile_coef(rr_plan *P, const rr::ReachCoef &reach)
+{
+    P->h_coef.resize(3 * (size_t)P->tp.np);
+    rr::tile_coef(P->tp, reach, kTileGhostBit, P->ghost_reach, P->h_coef.data());
+}
+
+// The tile-order tables on the device: ts.coef and its masked forms (rr_plan.hpp: tile_coef).
 int upload_tile_coef(rr_plan *P)
 {
     if (P->h_coef.empty()) return RR_OK;
-    std::vector<double> coef(P->h_coef);
-    for (int32_t i : P->ghost_reach) { const int64_t p = P->tp.inv[i]; coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0; }
-    int rc = dev_upload(P->ts.coef, coef);
-    if (rc) return rc;
-    {   // RapidMuskingum's short tick where the in-pass routes headwaters: those publish their record, as a ghost does
-        std::vector<double> hw(coef);
-        for (int64_t p = 0; p < P->tp.np; ++p)
-            if (P->hw_elig[p]) hw[3 * p] = hw[3 * p + 1] = hw[3 * p + 2] = 0.0;
-        rc = dev_upload(P->d_coef_hw, hw);
-        if (rc) return rc;
-        std::vector<double> col(3 * (size_t)P->h.n);      // (a boundary ghost's zeros: its column is not routed by the in-pass)
-        for (int64_t i = 0; i < P->h.n; ++i) for (int k = 0; k < 3; ++k) col[3 * i + k] = coef[3 * (int64_t)P->tp.inv[i] + k];
-        rc = dev_upload(P->d_hwcoef, col);
-        if (rc) return rc;
-    }
-    // UnitMuskingum's short tick: a headwater publishes its lateral inflow (_numba_kernels.py:122-123), which zero coefficients do too
-    for (int64_t p = 0; p < P->tp.np; ++p)
-        if ((P->tp.ccnt[p] & 0xFFFFu) == 0) coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0;
-    return dev_upload(P->d_coef_unit, coef);
+    std::vector<double> masked(P->h_coef), col(3 * (size_t)P->h.n);
+    int rc = dev_upload(P->ts.coef, P->h_coef);
+    rr::zero_tile_coef(masked.data(), P->hw_elig);      // RapidMuskingum's short tick where the in-pass routes headwaters
+    if (!rc) rc = dev_upload(P->d_coef_hw, masked);
+    rr::column_coef(P->tp, P->h_coef.data(), P->h.n, col.data());      // (a boundary ghost's zeros: its column is not routed by the in-pass)
+    if (!rc) rc = dev_upload(P->d_hwcoef, col);
+    // UnitMuskingum's short tick (_numba_kernels.py:122-123), on the same copy: an in-pass headwater has no upstream position either
+    rr::zero_tile_coef_headwaters(P->tp, masked.data());
+    return rc ? rc : dev_upload(P->d_coef_unit, masked);
 }
 
 // ---- kernel pickers: the instantiation a call gets, one function per kernel family.  They name every form the engine has and no other. ----
@@ -454,21 +453,14 @@ int upload_direct_plan(rr_plan *P)
     return rc;
 }
 
-// Coefficients of the direct row path from the host copy rr_plan_set_coeffs keeps: per column for the lanes, per position for the skeleton
-// (a ghost position computes nothing: zeros, as in upload_tile_coef).
+// Coefficients of the direct row path: the per-reach table for the lanes, the skeleton's tile-order table for its k_tile launches.
 int upload_direct_coef(rr_plan *P)
 {
-    if (!P->dp.ok || P->device < 0 || P->h_dcoef.empty()) return RR_OK;
-    int rc = dev_upload(P->d_dcoef, P->h_dcoef);
-    const rr::TilePlan &K = P->dp.skel;
-    std::vector<double> kc(3 * (size_t)K.np, 0.0);
-    for (int64_t p = 0; p < K.np; ++p) {
-        if (K.lag[p] & kTileGhostBit) continue;
-        const int64_t i = K.perm[p];
-        kc[3 * p] = P->h_dcoef[4 * i]; kc[3 * p + 1] = P->h_dcoef[4 * i + 1]; kc[3 * p + 2] = P->h_dcoef[4 * i + 2];
-    }
-    if (!rc) rc = dev_upload(P->ks.coef, kc);
-    return rc;
+    if (!P->dp.ok || P->device < 0 || P->h_reach_coef.empty()) return RR_OK;
+    int rc = dev_upload(P->d_dcoef, P->h_reach_coef);
+    std::vector<double> kc(3 * (size_t)P->dp.skel.np);
+    rr::tile_coef(P->dp.skel, rr::table_rows(P->h_reach_coef.data()), kTileGhostBit, {}, kc.data());
+    return rc ? rc : dev_upload(P->ks.coef, kc);
 }
 
 // The two-phase tiled permutation params order <-> lag order of the streaming kernel (k_perm_a / k_perm_b).  Built when a

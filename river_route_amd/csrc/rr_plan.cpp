@@ -636,7 +636,7 @@ int build_host_plan(int64_t n, const int32_t *indptr, const int32_t *indices, Ho
     }
 
     // ---- engine positions: levels in DESCENDING distance, bfs order inside a level ----
-    P.perm.resize(n); P.inv.resize(n); P.lag.resize(n);
+    P.perm.resize(n); P.inv.resize(n); P.lag.resize(n); P.edge_lag.resize(n);
     P.lag_start.assign(P.depth + 1, 0);
     int64_t base = 0;
     for (int32_t d = dmax; d >= 0; --d) {
@@ -648,7 +648,7 @@ int build_host_plan(int64_t n, const int32_t *indptr, const int32_t *indices, Ho
             const int64_t p = base + (r - a);
             P.perm[p] = bfs[r];
             P.inv[bfs[r]] = (int32_t)p;
-            P.lag[p] = lag;
+            P.lag[p] = lag; P.edge_lag[p] = P.edge_of[bfs[r]];
         }
         base += b - a;
     }
@@ -682,5 +682,59 @@ int build_host_plan(int64_t n, const int32_t *indptr, const int32_t *indices, Ho
     for (int64_t i = 0; i < n; ++i) if (!is_hw((int32_t)i)) P.inner_pos.push_back(P.inv[i]);
     return RR_OK;
 }
+
+// ---- coefficient tables ----
+
+static void zero_row(double *coef, int64_t p) { coef[3 * p] = coef[3 * p + 1] = coef[3 * p + 2] = 0.0; }
+
+// The walk both derivations share, in lag order: the positions flowing into p come before it and follow each other.  each(p, i, w0) gets
+// every position, its reach and the weight of the reach's first tributary.
+template <typename Each>
+static int64_t walk_tributaries(const HostPlan &H, const double *lhs_off_data, std::vector<double> &w, Each each)
+{
+    w.resize((size_t)H.n);
+    int64_t differ = -1;
+    for (int64_t p = 0; p < H.n; ++p) {
+        const int32_t i = H.perm[p], u0 = H.child_ptr[p], u1 = H.child_ptr[p + 1];
+        w[p] = H.edge_lag[p] >= 0 ? -lhs_off_data[H.edge_lag[p]] : 0.0;      // (a +0.0 entry gives -0.0)
+        for (int32_t u = u0 + 1; u < u1; ++u)
+            if (w[u] != w[u0] && (differ < 0 || i < differ)) differ = i;
+        each(p, i, u1 > u0 ? w[u0] : 0.0);
+    }
+    return differ;
+}
+
+int64_t tributary_weight(const HostPlan &H, const double *lhs, std::vector<double> &w, double *c1row) { return walk_tributaries(H, lhs, w, [&](int64_t, int32_t i, double w0) { c1row[i] = w0; }); }
+
+int64_t lag_coef(const HostPlan &H, const double *lhs_off_data, const double *c2, const double *c3, const double *c4_dt, LagCoef &L, double *c1row)
+{
+    for (std::vector<double> *column : {&L.c1row, &L.c2, &L.c3, &L.c4}) column->resize((size_t)H.n);
+    return walk_tributaries(H, lhs_off_data, L.w, [&](int64_t p, int32_t i, double w0) {
+        c1row[i] = L.c1row[p] = w0; L.c2[p] = c2[i]; L.c3[p] = c3[i]; L.c4[p] = c4_dt ? c4_dt[i] : 0.0;
+    });
+}
+
+void reach_coef(int64_t n, const double *c1row, const double *c2, const double *c3, const double *c4_dt, double *out)
+{
+    for (int64_t i = 0; i < n; ++i) {
+        out[4 * i] = c1row[i]; out[4 * i + 1] = c2[i]; out[4 * i + 2] = c3[i]; out[4 * i + 3] = c4_dt ? c4_dt[i] : 0.0;
+    }
+}
+
+void tile_coef(const TilePlan &T, const ReachCoef &reach, int32_t tile_ghost, const std::vector<int32_t> &boundary_ghosts, double *out)
+{
+    for (int64_t p = 0; p < T.np; ++p) {
+        if (T.lag[p] & tile_ghost) { zero_row(out, p); continue; }
+        const int64_t at = reach.stride * T.perm[p];      // the reach's row of a table, or its index in a member's arrays
+        out[3 * p] = reach.c1row[at]; out[3 * p + 1] = reach.c2[at]; out[3 * p + 2] = reach.c3[at];
+    }
+    for (int32_t i : boundary_ghosts) zero_row(out, T.inv[i]);
+}
+
+void zero_tile_coef(double *coef, const std::vector<uint8_t> &zero) { for (size_t p = 0; p < zero.size(); ++p) if (zero[p]) zero_row(coef, (int64_t)p); }
+
+void zero_tile_coef_headwaters(const TilePlan &T, double *coef) { for (int64_t p = 0; p < T.np; ++p) if ((T.ccnt[p] & 0xFFFFu) == 0) zero_row(coef, p); }
+
+void column_coef(const TilePlan &T, const double *coef, int64_t n, double *out) { for (int64_t i = 0; i < n; ++i) std::copy_n(coef + 3 * (int64_t)T.inv[i], 3, out + 3 * i); }
 
 }  // namespace rr

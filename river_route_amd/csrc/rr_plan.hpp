@@ -31,6 +31,7 @@ struct HostPlan {
     std::vector<uint16_t> hw_children;  // [n] how many of p's upstream reaches are headwaters (they come first)
     std::vector<int64_t> lag_start;  // [depth+1] first engine position with lag >= d
     std::vector<int32_t> edge_of;    // [n]   CSC entry index of the edge leaving params index i, -1 at outlets
+    std::vector<int32_t> edge_lag;   // [n]   the same per engine position: edge_of[perm[p]]
     std::vector<int32_t> inner_pos;  // [n_inner] engine position of the k-th inner reach (ascending params order)
     std::vector<int32_t> down;       // [n]   downstream params index, -1 at outlets
 };
@@ -165,6 +166,35 @@ void build_direct_plan(const std::vector<int32_t> &down, const std::vector<int32
 // Depth-first post-order of a forest given by downstream indices in any order (include/rr_hip.h: rr_postorder).  False: an index out of
 // range or a cycle.
 bool postorder(const int64_t *down, int64_t n, int64_t *order);
+
+// ---- coefficient tables: how a coefficient set becomes the table a kernel reads ----
+//
+// lhs_off_data [n_edges] (per CSC entry; may be null where the network has no edge), c2, c3 [n], c4_dt [n] or null (zeros then).
+//
+// The derivation.  c1row of a reach is minus the lhs_off_data entry of the edge leaving its first upstream reach, in child_ptr's order;
+// +0.0 at a headwater: c1row[n], params order.  On the way it fills w[n], lag order: the weight of the edge LEAVING each position (every
+// edge keeps its own).  The time-tiled kernel keeps ONE upstream weight per reach: returns the first reach (params index) two of whose
+// tributaries' weights differ, or -1.
+int64_t tributary_weight(const HostPlan &H, const double *lhs_off_data, std::vector<double> &w, double *c1row);
+// The plan's own set: the same walk and result, and on the way the lag-order arrays of the streaming kernel and the adjoint, each [n]:
+// w as above, c1row, and the caller's arrays gathered.
+struct LagCoef { std::vector<double> w, c1row, c2, c3, c4; };
+int64_t lag_coef(const HostPlan &H, const double *lhs_off_data, const double *c2, const double *c3, const double *c4_dt, LagCoef &L, double *c1row);
+// The per-reach table, {c1row, c2, c3, c4dt} per reach in params order, out[4 n]: the derived c1row beside the caller's arrays.
+void reach_coef(int64_t n, const double *c1row, const double *c2, const double *c3, const double *c4_dt, double *out);
+// Where a layout reads a reach's {c1row, c2, c3}: the rows of a per-reach table, or a parameter-ensemble member's own arrays beside its c1row.
+struct ReachCoef { const double *c1row, *c2, *c3; int64_t stride; };
+inline ReachCoef table_rows(const double *reach) { return {reach, reach + 1, reach + 2, 4}; }
+// The tile-order table of any tile plan: {c1row, c2, c3} per position, out[3 T.np].  A position that computes nothing holds three
+// zeros: one with `tile_ghost` in T.lag[] (it publishes the record of a reach another tile owns) and the position of each reach of
+// `boundary_ghosts` (params indices: reaches another GPU owns).  Zero coefficients make the short tick publish what arrives.
+void tile_coef(const TilePlan &T, const ReachCoef &reach, int32_t tile_ghost, const std::vector<int32_t> &boundary_ghosts, double *out);
+// Its masked forms, made on tile_coef's result.  Three zeros where zero[p] != 0 (the in-pass headwaters: published, as a ghost is) ...
+void zero_tile_coef(double *coef, const std::vector<uint8_t> &zero);
+// ... and at the positions without upstream positions (UnitMuskingum's short tick: a headwater publishes its lateral inflow).
+void zero_tile_coef_headwaters(const TilePlan &T, double *coef);
+// Per params column, out[3 n]: the row of the reach's own position (k_rec_in routes columns).
+void column_coef(const TilePlan &T, const double *coef, int64_t n, double *out);
 
 // Returns 0 or an RR_E_* code with a message in err.
 int build_host_plan(int64_t n, const int32_t *indptr, const int32_t *indices, HostPlan &plan, std::string &err);
