@@ -35,8 +35,8 @@ _ERRORS = {
 def build(fast: bool = False, out_dir: str | None = None) -> str:
     """Compile the oracle with gcc if its shared object is missing or stale; returns the .so path."""
     name = 'librr_oracle_fast.so' if fast else 'librr_oracle.so'
-    # the parity checker holds the extended-precision arbiter too (rr_oracle_ld.c); the timed baseline is the fp64 loops alone
-    srcs = [os.path.join(_HERE, f) for f in (('rr_oracle.c',) if fast else ('rr_oracle.c', 'rr_oracle_ld.c'))]
+    # the parity checker holds the extended-precision arbiters too (rr_oracle_ld.c, rr_oracle_adj.c); the timed baseline is the fp64 loops alone
+    srcs = [os.path.join(_HERE, f) for f in (('rr_oracle.c',) if fast else ('rr_oracle.c', 'rr_oracle_ld.c', 'rr_oracle_adj.c'))]
     out = os.path.join(out_dir or _HERE, name)
     if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(src) for src in srcs):
         return out
@@ -66,7 +66,32 @@ def _bind(lib: C.CDLL) -> C.CDLL:
         lib.orcl_uh_convolve.argtypes = [_i64, _i64, _i64, _f64p, _f64p, _f64p, _f64p]
         for f in ('orcl_muskingum_route', 'orcl_rapid_route', 'orcl_unit_route', 'orcl_uh_convolve'):
             getattr(lib, f).restype = C.c_int
+    if hasattr(lib, 'orcl_rapid_adjoint'):    # the adjoint arbiter (rr_oracle_adj.c): in the parity checker only
+        _bind_adjoint(lib)
     return lib
+
+
+def _bind_adjoint(lib: C.CDLL) -> C.CDLL:
+    o = C.c_void_p      # optional arrays: NULL or the address of a float64 array
+    for f in ('orc_rapid_adjoint', 'orcl_rapid_adjoint'):
+        getattr(lib, f).argtypes = [_i64, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p, o, o, o, _i64, _i64,
+                                    _f64p, _f64p, o, _f64p, _f64p, o, _f64p]
+        getattr(lib, f).restype = C.c_int
+    for f in ('orc_unit_adjoint', 'orcl_unit_adjoint'):
+        getattr(lib, f).argtypes = [_i64, _i32p, _i32p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, o, o, o, _i64, _i64,
+                                    _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p, _f64p]
+        getattr(lib, f).restype = C.c_int
+    return lib
+
+
+def build_adjoint_reordered(out_dir: str) -> C.CDLL:
+    """rr_oracle_adj.c alone, its fp64 loops summing the terms of every recursion and the tributaries of every reach in the reverse
+    order, with fused multiply-adds: a second correctly rounded evaluation, for measuring what a change of order costs (the K of
+    tests/per_reach.assert_per_element).  Built into `out_dir`, never beside the sources."""
+    out = os.path.join(out_dir, 'librr_oracle_adj_reordered.so')
+    subprocess.check_call(['gcc', '-std=c11', '-O2', '-march=native', '-fno-fast-math', '-ffp-contract=fast', '-DORC_ADJ_REORDER',
+                           '-fPIC', '-shared', '-o', out, os.path.join(_HERE, 'rr_oracle_adj.c'), '-lm'])
+    return _bind_adjoint(C.CDLL(out))
 
 
 _LIBS: dict[str, C.CDLL] = {}
@@ -162,6 +187,90 @@ def unit_route_ld(lhs_indptr, lhs_indices, lhs_off_data, a_inner_indptr, a_inner
         _f64(c1_inner), _f64(c2_inner), _f64(c3_inner),
         np.ascontiguousarray(hw_idx, dtype=np.int64), np.ascontiguousarray(inner_idx, dtype=np.int64),
         q_ch, q_full, _f64(convolved_lateral), discharge_array, raw_array, T, num_substeps))
+
+
+class Adjoint:
+    """What an adjoint arbiter call returns: each gradient, the scale of each (the sum of the absolute values of the terms that
+    were added to make it) and `raw`, the unclamped interval means of the forward it ran."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def _opt(a):
+    """(the array kept alive, its address or None)"""
+    if a is None:
+        return None, None
+    a = _f64(a)
+    return a, a.ctypes.data
+
+
+def _rapid_adjoint(fn, csc_indptr, csc_indices, c1, c2, c3, c4_dt, q0, qlateral, grad_out, grad_qfinal, T, num_substeps):
+    n = q0.shape[0]
+    T = int(qlateral.shape[0] if qlateral is not None else T)
+    assert T >= 1 and num_substeps >= 1
+    ql, ql_p = _opt(qlateral)
+    go, go_p = _opt(grad_out)
+    gf, gf_p = _opt(grad_qfinal)
+    assert (ql is None or ql.shape == (T, n)) and (go is None or go.shape == (T, n)) and (gf is None or gf.shape == (n,))
+    r = Adjoint(grad_coef=np.zeros((4, n)), grad_q0=np.zeros(n), grad_lateral=None if ql is None else np.zeros((T, n)),
+                scale_coef=np.zeros((4, n)), scale_q0=np.zeros(n), scale_lateral=None if ql is None else np.zeros((T, n)),
+                raw=np.zeros((T, n)))
+    _check(fn(n, _i32(csc_indptr), _i32(csc_indices), _f64(c1), _f64(c2), _f64(c3), _f64(c4_dt), _f64(q0), ql_p, go_p, gf_p, T,
+              num_substeps, r.grad_coef, r.grad_q0, None if ql is None else r.grad_lateral.ctypes.data, r.scale_coef, r.scale_q0,
+              None if ql is None else r.scale_lateral.ctypes.data, r.raw))
+    return r
+
+
+def rapid_adjoint(csc_indptr, csc_indices, c1, c2, c3, c4_dt, q0, qlateral, grad_out, grad_qfinal, num_substeps, T=None, *, lib_=None):
+    """The gradient of L through rapid_route (per-reach c1: lhs_off_data = -c1[indices]) in fp64, by the plain loops of
+    rr_oracle_adj.c.  qlateral None: channel-only routing of T rows.  grad_out (T, n) = dL/ddischarge and grad_qfinal (n) may be
+    None.  `lib_`: another build of the same source (build_adjoint_reordered)."""
+    return _rapid_adjoint((lib_ or lib()).orc_rapid_adjoint, csc_indptr, csc_indices, c1, c2, c3, c4_dt, q0, qlateral, grad_out,
+                          grad_qfinal, T, num_substeps)
+
+
+def rapid_adjoint_ld(csc_indptr, csc_indices, c1, c2, c3, c4_dt, q0, qlateral, grad_out, grad_qfinal, num_substeps, T=None):
+    """rapid_adjoint in long double, every output rounded to double once: the arbiter."""
+    return _rapid_adjoint(lib().orcl_rapid_adjoint, csc_indptr, csc_indices, c1, c2, c3, c4_dt, q0, qlateral, grad_out,
+                          grad_qfinal, T, num_substeps)
+
+
+def _unit_adjoint(fn, csc_indptr, csc_indices, c1, c2, c3, q_ch0, q_full0, lateral, grad_out, grad_qch_final, grad_qfull_final,
+                  num_substeps):
+    lateral = _f64(lateral)
+    T, n = lateral.shape
+    ni = q_ch0.shape[0]
+    assert T >= 1 and num_substeps >= 1 and q_full0.shape == (ni,)
+    go, go_p = _opt(grad_out)
+    gc, gc_p = _opt(grad_qch_final)
+    gf, gf_p = _opt(grad_qfull_final)
+    assert (go is None or go.shape == (T, n)) and (gc is None or gc.shape == (ni,)) and (gf is None or gf.shape == (ni,))
+    m = max(ni, 1)
+    r = Adjoint(grad_coef=np.zeros((3, n)), grad_qch0=np.zeros(m), grad_qfull0=np.zeros(m), grad_lateral=np.zeros((T, n)),
+                scale_coef=np.zeros((3, n)), scale_states=np.zeros(2 * m), scale_lateral=np.zeros((T, n)), raw=np.zeros((T, n)))
+    _check(fn(n, _i32(csc_indptr), _i32(csc_indices), _f64(c1), _f64(c2), _f64(c3), _f64(np.resize(q_ch0, m) if ni else np.zeros(1)),
+              _f64(np.resize(q_full0, m) if ni else np.zeros(1)), lateral, go_p, gc_p, gf_p, T, num_substeps,
+              r.grad_coef, r.grad_qch0, r.grad_qfull0, r.grad_lateral, r.scale_coef, r.scale_states, r.scale_lateral, r.raw))
+    r.scale_qch0, r.scale_qfull0 = r.scale_states[:ni].copy(), r.scale_states[ni:2 * ni].copy()
+    r.grad_qch0, r.grad_qfull0 = r.grad_qch0[:ni], r.grad_qfull0[:ni]
+    return r
+
+
+def unit_adjoint(csc_indptr, csc_indices, c1, c2, c3, q_ch0, q_full0, lateral, grad_out, grad_qch_final, grad_qfull_final,
+                 num_substeps, *, lib_=None):
+    """The gradient of L through unit_route with the callers' unit edge weights, in fp64 (rr_oracle_adj.c): the CSC arrays and
+    the coefficients are the whole network's, in params order; the states and their gradients are indexed by inner reach
+    (ascending params order), as Plan.unit_adjoint_dev takes them.  Any of the three cotangents may be None."""
+    return _unit_adjoint((lib_ or lib()).orc_unit_adjoint, csc_indptr, csc_indices, c1, c2, c3, q_ch0, q_full0, lateral, grad_out,
+                         grad_qch_final, grad_qfull_final, num_substeps)
+
+
+def unit_adjoint_ld(csc_indptr, csc_indices, c1, c2, c3, q_ch0, q_full0, lateral, grad_out, grad_qch_final, grad_qfull_final,
+                    num_substeps):
+    """unit_adjoint in long double, every output rounded to double once: the arbiter."""
+    return _unit_adjoint(lib().orcl_unit_adjoint, csc_indptr, csc_indices, c1, c2, c3, q_ch0, q_full0, lateral, grad_out,
+                         grad_qch_final, grad_qfull_final, num_substeps)
 
 
 def uh_convolve_ld(kernel, state, lateral):

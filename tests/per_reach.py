@@ -10,7 +10,11 @@ e_j(got) <= K max(E_orc, 2^-52) S_j with K = 16; where S_j == 0 it holds +0.0 in
 
 K = 16: a correctly rounded loop in another operation order (the same C loop built with fused multiply-adds) stayed within
 4.8 x E_orc over 16 cases (6k ... 300k reaches, random and chain-grown networks, 1 and 3 sub-steps); 16 leaves about 3 x for a
-kernel that also sums a reach's tributaries in another order."""
+kernel that also sums a reach's tributaries in another order.
+
+The second half of the module is the same for the routing gradients (test_adjoint_oracle.py on the CPU, test_gpu_grad_per_reach.py on
+the GPU box): the per-element rule against the adjoint arbiter (oracle/rr_oracle_adj.c), the chain to dL/dk and
+dL/dx, and the one table of cases both files run."""
 import functools
 import os
 import sys
@@ -124,6 +128,10 @@ def network(name):
         net = synth.synth_network(N, seed=21)
     elif name == 'postorder':
         net = synth.synth_network(N, seed=21, order='postorder')
+    elif name == 'synth20k':
+        net = synth.synth_network(20_000, seed=23)
+    elif name == 'synth524544':      # 2,049 column blocks of 256: the adjoint's reduction has one sub-step range
+        net = synth.synth_network(524_544, seed=25)
     elif name == 'chain97':
         net = synth.synth_network_chain(N, p_chain=0.97, n_outlets=7, p_third=0.3)
     else:
@@ -138,6 +146,8 @@ def network(name):
             down = np.full(5001, 5000, dtype=np.int64)
         elif name == 'lone':
             down = np.full(777, -1, dtype=np.int64)
+        elif name == 'y3':          # two reaches into one
+            down = np.array([2, 2, -1], dtype=np.int64)
         else:
             raise ValueError(name)
         down[-1] = -1
@@ -320,3 +330,293 @@ def unit_case(net_name, regime, T, nsub, n_ks=0, f32_lat=False):
         qc_o, qc_e = qf_o.copy(), qf_e.copy()
     inputs = Ref(n=n, indptr=indptr, indices=indices, c1=c1, c2=c2, c3=c3, hw_idx=hw_idx, inner_idx=inner_idx, ni=ni, kern=kern, lat=lat, args=args)
     return inputs, refs
+
+
+# ------------------------------------------------------------------------------------------------ gradients
+# The routing adjoints against the adjoint arbiter (oracle/rr_oracle_adj.c), every output element at ITS OWN scale: the arbiter
+# returns, next to each gradient, the sum of the absolute values of the terms that were added to make it.  With `exact` the
+# long-double result, `scale` that array and `orc` the fp64 build of the same loops:  E_orc = max |orc - exact| / scale over
+# scale > 0, recomputed in every test;  got passes when |got - exact| <= K_ADJ max(E_orc, 2^-52) scale at every element, is 0 where
+# scale == 0 and has its NaNs where the arbiter has them.  K_ADJ is measured, not chosen: test_adjoint_oracle.py builds the fp64 loops
+# a second time in the reverse summation order with fused multiply-adds and asserts that K_ADJ follows from the worst ratio by the
+# rule of section 2c.
+
+K_ADJ = 32.0
+DT_RUNOFF = 3600.0
+ADJ_TARGET_BLOCKS, ADJ_BLOCK = 2048, 256      # rr_adjoint.hpp: kAdjTargetBlocks; rr_common.hpp: kBlock
+
+
+def element_error(orc, exact, scale):
+    """E_orc of the rule above for one output array."""
+    live = scale > 0
+    if not live.any():
+        return 0.0
+    with np.errstate(invalid='ignore'):
+        r = np.abs(np.asarray(orc)[live] - exact[live]) / scale[live]
+    return float(np.nanmax(r, initial=0.0))
+
+
+def assert_per_element(got, orc, exact, scale, what, K=K_ADJ):
+    """The rule of DESIGN.md section 2c.  Returns the worst |got - exact| / (max(E_orc, 2^-52) scale)."""
+    got, orc, exact, scale = (np.asarray(a, dtype=np.float64) for a in (got, orc, exact, scale))
+    assert got.shape == orc.shape == exact.shape == scale.shape, f'{what}: shapes {got.shape}, {orc.shape}, {exact.shape}, {scale.shape}'
+    unit = max(element_error(orc, exact, scale), EPS)
+    assert np.array_equal(np.isnan(got), np.isnan(exact)), f'{what}: NaN pattern differs from the arbiter\'s'
+    dead = scale == 0
+    assert not got[dead].any(), f'{what}: {int(np.count_nonzero(got[dead]))} nonzero values where the gradient is structurally zero'
+    live = ~dead & ~np.isnan(exact)
+    if not live.any():
+        return 0.0
+    ratio = np.abs(got[live] - exact[live]) / scale[live] / unit
+    w = int(np.argmax(ratio))
+    at = tuple(int(v[w]) for v in np.nonzero(live))
+    assert ratio[w] <= K, (f'{what}: element {at} is off by {ratio[w]:.3g} x the fp64 arbiter\'s own error at the element\'s scale '
+                           f'(got {got[at]:.17g}, exact {exact[at]:.17g}, scale {scale[at]:.3g}, E_orc {unit:.3g}; allowed {K:g} x)')
+    return float(ratio[w])
+
+
+def coefficient_jacobian(k, x, dt, with_c4=True, dt_runoff=DT_RUNOFF):
+    """(dc/dk, dc/dx), each [4 or 3, n]: the derivatives of c1, c2, c3 (and c4dt = (c1 + c2) / dt_runoff) of a reach by its own k, x,
+    from rr.grad.muskingum_coefficients under torch autograd on the host."""
+    import torch
+    import river_route_amd as rr
+    rows_k, rows_x = [], []
+    for j in range(4 if with_c4 else 3):
+        kt, xt = torch.tensor(np.asarray(k), requires_grad=True), torch.tensor(np.asarray(x), requires_grad=True)
+        c = rr.grad.muskingum_coefficients(kt, xt, dt)
+        cj = (c[0] + c[1]) / dt_runoff if j == 3 else c[j]
+        gk, gx = torch.autograd.grad(cj.sum(), (kt, xt))
+        rows_k.append(gk.numpy())
+        rows_x.append(gx.numpy())
+    return np.stack(rows_k), np.stack(rows_x)
+
+
+def chain_to_kx(jac, grad_coef, scale_coef):
+    """dL/dk (or dL/dx) = sum_j dL/dc_j dc_j/dk and its scale sum_j scale_cj |dc_j/dk|."""
+    return (grad_coef * jac).sum(axis=0), (scale_coef * np.abs(jac)).sum(axis=0)
+
+
+def adjoint_splits(n, T, nsub, members=1):
+    """(splits, steps_per_split) of the adjoints' reduction: the arithmetic of adjoint_layout (rr_adjoint.hpp), restated."""
+    S = T * nsub
+    col_blocks = -(-n // ADJ_BLOCK) * members
+    want = max(1, -(-ADJ_TARGET_BLOCKS // col_blocks))
+    splits = max(1, min(want, S))
+    steps = -(-S // splits)
+    return -(-S // steps), steps
+
+
+# name: (network, T, nsub, members, (splits, steps_per_split) expected, regimes)
+ADJ_CASES = {
+    'ragged ranges': ('random', 353, 1, 1, (71, 5), ('benign', 'clamp')),
+    'ranges across rows': ('chain', 500, 3, 1, (167, 9), ('benign', 'clamp')),
+    'one range': ('synth524544', 6, 1, 1, (1, 6), ('benign', 'clamp')),
+    'fan-in star': ('star', 40, 2, 1, (80, 1), ('benign', 'clamp')),
+    'fan-in comb': ('comb', 40, 2, 1, (80, 1), ('benign', 'clamp')),
+    'fan-in wide': ('wide', 40, 2, 1, (80, 1), ('benign', 'clamp')),
+    'no edges': ('lone', 40, 2, 1, (80, 1), ('benign',)),
+    'long record': ('y3', 65_552, 1, 1, (1987, 33), ('benign',)),      # the smallest T above 65,535 + 16 (DESIGN.md section 2c)
+    'batch': ('synth20k', 48, 2, 4, (7, 14), ('benign',)),
+    'partial losses': ('random', 2, 3, 1, (6, 1), ('benign',)),      # run with the losses 'channel', 'final', 'outlet' only
+}
+
+
+def adjoint_inputs(case, regime, member=0, loss='both'):
+    """(k, x, ql, q0, G, Gf) of a case: the draws of test_gpu_grad.py (lateral volumes per DT_RUNOFF from `low` upward, a state in
+    [0, 3], standard-normal cotangents); 'clamp' is its clamp / negative-c3 draw (k[::3] = 300, lateral from -1.5) with a zero-mean lateral."""
+    net_name, T, nsub, _, _, _ = ADJ_CASES[case]
+    down, k, x = network(net_name)
+    n = down.size
+    k = k.copy()
+    low, high = 0.0, 2.0
+    if regime == 'clamp':      # (up to 1.5, not 2: with a positive mean the inflow that gathers along a chain keeps all but its head above zero)
+        k[::3] = 300.0
+        low, high = -1.5, 1.5
+    else:
+        assert regime == 'benign', regime
+    seed = sum(map(ord, case)) * 7 + (1 if regime == 'clamp' else 0) + 1000 * member
+    rng = np.random.default_rng(seed)
+    ql = rng.uniform(low, high, (T, n)) * DT_RUNOFF
+    q0 = rng.uniform(0.0, 3.0, n)
+    G, Gf = rng.standard_normal((T, n)), rng.standard_normal(n)
+    return k, x, ql, q0, G, Gf
+
+
+class AdjRef(Ref):
+    pass
+
+
+def rapid_adjoint_refs(indptr, indices, c, q0, ql, G, Gf, nsub, T=None):
+    """(orc, exact) of one RapidMuskingum adjoint call: the fp64 and the long-double run of the arbiter."""
+    from oracle import oracle
+    args = (indptr, indices, c[0], c[1], c[2], c[3], q0, ql, G, Gf, nsub, T)
+    return oracle.rapid_adjoint(*args), oracle.rapid_adjoint_ld(*args)
+
+
+N_GAUGES = 37
+
+
+def gauge_columns(case):
+    """37 gauged reaches of a case, in no order: headwaters and inner reaches among them, the outlet (the last reach) the first."""
+    down = network(ADJ_CASES[case][0])[0]
+    n = down.size
+    inner = inner_reaches(down)
+    hw = np.setdiff1d(np.arange(n), inner)
+    rng = np.random.default_rng(37)
+    g = np.concatenate([[n - 1], rng.choice(hw, 12, replace=False), rng.choice(inner[inner != n - 1], N_GAUGES - 13, replace=False)])
+    assert np.unique(g).size == N_GAUGES
+    g[1:] = rng.permutation(g[1:])
+    return g.astype(np.int32)
+
+
+def gauge_cotangent(case, G):
+    """dL/ddischarge of a gauge loss at full width: zero off the gauge columns."""
+    G0 = np.zeros_like(G)
+    g = gauge_columns(case)
+    G0[:, g] = G[:, g]
+    return G0
+
+
+@functools.lru_cache(maxsize=6)
+def rapid_adjoint_case(case, regime, member=0, loss='both', shared=False):
+    """Inputs and references of a RapidMuskingum case, computed once.  loss: 'both' (dL/ddischarge and dL/dq_final), 'final' (dL/dq_final
+    alone), 'outlet' (dL/ddischarge in the last row at the last reach alone), 'channel' (no laterals), 'gauges' (dL/ddischarge at
+    gauge_columns alone, and dL/dq_final).  shared: the member starts from member 0's state."""
+    net_name, T, nsub, _, _, _ = ADJ_CASES[case]
+    down = network(net_name)[0]
+    indptr, indices = csc_from_down(down)
+    k, x, ql, q0, G, Gf = adjoint_inputs(case, regime, member)
+    if shared:
+        q0 = adjoint_inputs(case, regime, 0)[3]
+    if loss == 'gauges':
+        G = gauge_cotangent(case, G)
+    if loss == 'final':
+        G = None
+    elif loss == 'outlet':
+        G0 = np.zeros_like(G)
+        G0[-1, -1] = G[-1, -1]
+        G, Gf = G0, None
+    elif loss == 'channel':
+        ql = None
+    c1, c2, c3 = coefficients_at(k, x, DT_RUNOFF / nsub)
+    c = np.stack([c1, c2, c3, (c1 + c2) / DT_RUNOFF])
+    orc, exact = rapid_adjoint_refs(indptr, indices, c, q0, ql, G, Gf, nsub, T)
+    return AdjRef(n=down.size, T=T, nsub=nsub, indptr=indptr, indices=indices, k=k, x=x, c=c, ql=ql, q0=q0, G=G, Gf=Gf, orc=orc, exact=exact)
+
+
+def coefficients_at(k, x, dt):
+    from oracle import oracle
+    return oracle.muskingum_coefficients(k, x, dt)
+
+
+def rapid_outputs(r):
+    """[(name, orc, exact, scale)] of a rapid_adjoint_case."""
+    out = [(f'dL/dc{j + 1}' if j < 3 else 'dL/dc4dt', r.orc.grad_coef[j], r.exact.grad_coef[j], r.exact.scale_coef[j]) for j in range(4)]
+    out.append(('dL/dq0', r.orc.grad_q0, r.exact.grad_q0, r.exact.scale_q0))
+    if r.ql is not None:
+        out.append(('dL/dlateral', r.orc.grad_lateral, r.exact.grad_lateral, r.exact.scale_lateral))
+    return out
+
+
+def forward_margin(orc_raw, exact_raw):
+    """The clamp condition of section 2c: the number of elements whose unclamped mean sits within the forward rule's bound of zero without
+    being zero, 0 < |raw| <= K E_orc,fwd S_j (K = 16, the forward rule's), and the share of elements the clamp is active on."""
+    S = scales(exact_raw)
+    e_fwd = max(oracle_error(orc_raw, exact_raw, S), EPS)
+    near = (np.abs(exact_raw) > 0) & (np.abs(exact_raw) <= K * e_fwd * S[None, :])
+    return int(near.sum()), float((exact_raw <= 0).mean())
+
+
+def inner_reaches(down):
+    """The inner reaches (those with tributaries) in ascending params order: the index of UnitMuskingum's states."""
+    has_up = np.zeros(down.size, dtype=bool)
+    has_up[down[down >= 0]] = True
+    return np.flatnonzero(has_up)
+
+
+def unit_adjoint_inputs(case, regime, member=0):
+    """(k, x, lat, q_ch0, q_full0, G, Gc, Gf) of a case: the draws of test_grad_unit.unit_inputs (lateral inflow from `low` x 50 upward,
+    states in [0, 80] and [0, 120], standard-normal cotangents) in the regimes of adjoint_inputs."""
+    net_name, T, nsub, _, _, _ = ADJ_CASES[case]
+    down, k, x = network(net_name)
+    n, ni = down.size, inner_reaches(down).size
+    k = k.copy()
+    low, high = 0.0, 2.0
+    if regime == 'clamp':
+        k[::3] = 300.0
+        low, high = -1.5, 1.5
+    else:
+        assert regime == 'benign', regime
+    rng = np.random.default_rng(sum(map(ord, case)) * 11 + (1 if regime == 'clamp' else 0) + 1000 * member + 5)
+    return (k, x, rng.uniform(low, high, (T, n)) * 50.0, rng.uniform(0.0, 80.0, ni), rng.uniform(0.0, 120.0, ni),
+            rng.standard_normal((T, n)), rng.standard_normal(ni), rng.standard_normal(ni))
+
+
+@functools.lru_cache(maxsize=6)
+def unit_adjoint_case(case, regime, member=0, loss='both', shared=False):
+    """Inputs and references of a UnitMuskingum case, computed once.  loss: 'both' (all three cotangents), 'final' (those of the final
+    states alone), 'outlet' (dL/ddischarge in the last row at the last reach alone), 'gauges' (dL/ddischarge at gauge_columns alone, and
+    those of the final states).  shared: the member starts from member 0's states."""
+    from oracle import oracle
+    net_name, T, nsub, _, _, _ = ADJ_CASES[case]
+    down = network(net_name)[0]
+    indptr, indices = csc_from_down(down)
+    k, x, lat, qc0, qf0, G, Gc, Gf = unit_adjoint_inputs(case, regime, member)
+    if shared:
+        qc0, qf0 = unit_adjoint_inputs(case, regime, 0)[3:5]
+    if loss == 'gauges':
+        G = gauge_cotangent(case, G)
+    if loss == 'final':
+        G = None
+    elif loss == 'outlet':
+        G0 = np.zeros_like(G)
+        G0[-1, -1] = G[-1, -1]
+        G, Gc, Gf = G0, None, None
+    c = np.stack(coefficients_at(k, x, DT_RUNOFF / nsub))
+    args = (indptr, indices, c[0], c[1], c[2], qc0, qf0, lat, G, Gc, Gf, nsub)
+    return AdjRef(n=down.size, ni=qc0.size, inner=inner_reaches(down), T=T, nsub=nsub, indptr=indptr, indices=indices, k=k, x=x, c=c, lat=lat,
+                  q_ch0=qc0, q_full0=qf0, G=G, Gc=Gc, Gf=Gf, orc=oracle.unit_adjoint(*args), exact=oracle.unit_adjoint_ld(*args))
+
+
+def unit_outputs(r):
+    """[(name, orc, exact, scale)] of a unit_adjoint_case."""
+    out = [(f'dL/dc{j + 1}', r.orc.grad_coef[j], r.exact.grad_coef[j], r.exact.scale_coef[j]) for j in range(3)]
+    return out + [('dL/dq_ch0', r.orc.grad_qch0, r.exact.grad_qch0, r.exact.scale_qch0),
+                  ('dL/dq_full0', r.orc.grad_qfull0, r.exact.grad_qfull0, r.exact.scale_qfull0),
+                  ('dL/dlateral', r.orc.grad_lateral, r.exact.grad_lateral, r.exact.scale_lateral)]
+
+
+def member_sum(rows):
+    """The members' coefficient rows summed in member order in long double, rounded once."""
+    acc = np.zeros(rows[0].shape, dtype=np.longdouble)
+    for r in rows:
+        acc = acc + r
+    return acc.astype(np.float64)
+
+
+def every_case():
+    """(case, regime, member, loss, shared) of every definition of the table: each case in its regimes (a batch: every member, with its
+    own state and with the shared one), the gauge losses on the ragged-ranges case and the partial losses on the fan-in comb."""
+    out = []
+    for case, (_, _, _, members, _, regimes) in ADJ_CASES.items():
+        for regime in regimes if case != PARTIAL_CASE else ():
+            for m in range(members):
+                out.append((case, regime, m, 'both', False))
+                if members > 1 and m:
+                    out.append((case, regime, m, 'both', True))
+    out += [('ragged ranges', 'benign', m, 'gauges', False) for m in range(3)]
+    out += [(PARTIAL_CASE, 'benign', 0, loss, False) for loss in ('channel', 'final', 'outlet')]
+    return out
+
+
+PARTIAL_CASE = 'partial losses'
+
+
+def adjoint_work_bytes(n, depth, T, nsub, router, members=1, n_gauges=0, grad_rows=True):
+    """What the sizers of the adjoint calls return (include/rr_hip.h), from adjoint_splits: a sizer that answers this number laid its
+    reduction out in the sub-step ranges the case table says."""
+    S = T * nsub
+    splits, _ = adjoint_splits(n, T, nsub, members)
+    slab_rows, scratch_rows = (4, 2) if router == 'rapid' else (3, 6)
+    per_member = 2 * S + 2 * depth + (2 if grad_rows else 1) * T + slab_rows * splits + scratch_rows
+    return 8 * (n * members * per_member + max(n * min(T, 16), members * T * n_gauges))

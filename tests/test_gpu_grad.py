@@ -2,7 +2,9 @@
 the forward is the production route call, bit for bit; every gradient (k, x, qlateral, q0, through the discharge and through
 q_final) agrees with torch autograd through the pure-torch restatement of tests/test_grad.py (checked there against the
 oracle) to rtol 1e-9; gradcheck; windows against one call; repeat runs bit-identical; a 100k-reach directional difference;
-and the ABI's refusals."""
+and the ABI's refusals.  The restatement is a dense solve per sub-step, so these cases stop at 2,000 reaches, where the reduction has one
+sub-step per range: the sizes beyond it, and every element at its own scale, are tests/test_gpu_grad_per_reach.py's (DESIGN.md
+section 2c)."""
 import numpy as np
 import pytest
 import torch

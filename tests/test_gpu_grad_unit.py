@@ -3,7 +3,8 @@ k_adj_merge_unit, k_adj_rows_unit; rr_uh_adjoint_dev: k_uh_adjoint_depth, k_uh_a
 call, bit for bit; every gradient (k, x, lateral or depth, uh_kernel, uh_state, q_ch0, q_full0) agrees with torch autograd through
 the pure-torch restatements of tests/test_grad_unit.py (checked there against the oracle) to rtol 1e-9; gradcheck; windows against
 one call; repeat runs bit-identical; a 100k-reach directional difference; and the ABI's refusals.  Case for case the grid of
-tests/test_gpu_grad.py."""
+tests/test_gpu_grad.py; the sizes beyond the dense restatement (several sub-steps per range of the reduction, more than 65,535 rows)
+and every element at its own scale are tests/test_gpu_grad_per_reach.py's."""
 import numpy as np
 import pytest
 import torch
