@@ -635,6 +635,32 @@ int rr_metrics_adjoint_dev(int device, int64_t n, int64_t rows, const void *y_tr
                            int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
                            void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream);
 
+/* ---- skill scores and their adjoint over records with gaps (DESIGN.md sections 9 and 12c, "Missing observations") ----
+ * rr_metrics_update_missing_dev is rr_metrics_update_dev, and rr_metrics_adjoint_missing_dev is rr_metrics_adjoint_dev, with one
+ * rule added: element (r, j) is MISSING when y_true[r, j], as stored (float or double), is NaN.  The pair (y_true[r, j],
+ * y_pred[r, pred_columns[j]]) is then left out of every sum of column j, and y_pred there is never looked at (a NaN there changes
+ * nothing).  Inf is not missing.  A NaN of y_pred at a KEPT row poisons the column as in rr_metrics_update_dev.  Each column is
+ * scored over its own kept pairs: state[0 * n + j] (the count) is N_j, the number kept, and rr_metrics_finish_dev and the adjoint's
+ * constants divide by it.  N_j = 0: all five scores NaN; N_j = 1: mean error, mean absolute error and mean square error finite,
+ * Pearson r and KGE NaN; the constant-column and zero-mean rules are those of rr_metrics_finish_dev.
+ * The argument lists, the refusals and the work memory (rr_metrics_work_bytes, rr_metrics_adjoint_work_bytes) are those of the two
+ * calls without the rule; the state is finished by rr_metrics_finish_dev.  Updates with and without the rule may be mixed on one
+ * state: the state then holds every pair of the plain updates (a NaN among them poisons the column) and the kept pairs of the
+ * others, and its count is their sum.
+ * Adjoint: `state` is the one rr_metrics_update_missing_dev left over the same rows.  At a kept element column j adds the share of
+ * rr_metrics_adjoint_dev, with N_j and the kept pairs' moments in its constants; at a missing element its share is exactly 0.0,
+ * never NaN, whatever the constants are.  With a column map every share is masked by its own y_true column, so a column of y_pred
+ * scored twice gets the kept share alone where the other is missing.  Every element rr_metrics_adjoint_dev would write is
+ * written.  "A NaN score with a gradient other than 0 makes the column's gradient NaN" holds at the kept rows; a column with
+ * N_j = 0 adds zeros.  No atomics: the same inputs give the same bits. */
+int rr_metrics_update_missing_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                                  const void *y_pred, int pred_is_f32, int64_t pred_pitch, const int32_t *pred_columns, double *state,
+                                  void *work, int64_t work_bytes, void *stream);
+int rr_metrics_adjoint_missing_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                                   const void *y_pred, int pred_is_f32, int64_t pred_pitch, const double *state, const double *grad_scores,
+                                   int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
+                                   void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream);
+
 /* ---- adjoint of gridded runoff -> catchment inflow (rr.grad.runoff_to_qlateral) ----
  * The gradient of a scalar loss L through one rr_runoff_to_qlateral_dev call with respect to the runoff block and to the weights.
  * n_rivers, n_points, T, the CSR arrays, runoff with its type and strides, area and flags are those of the forward call;

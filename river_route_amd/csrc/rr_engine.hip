@@ -16,7 +16,8 @@
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
 // rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp, rr_kernels_adjoint_unit.hpp (device code), rr_exec.hpp (plan object, executor),
 // then the C ABI below; rr_adjoint.hpp (the adjoints' host side), rr_kernels_metrics_adjoint.hpp (the adjoint of the skill
-// scores, device code) and rr_kernels_runoff_adjoint.hpp (the adjoint of the gridded-runoff inflow, device code) are included where
+// scores, device code), rr_kernels_runoff_adjoint.hpp (the adjoint of the gridded-runoff inflow, device code) and, last,
+// rr_kernels_metrics_missing.hpp (the skill scores and their adjoint over records with gaps, device code) are included where
 // their entry points are.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
@@ -1762,6 +1763,82 @@ int rr_runoff_adjoint_dev(int device, int64_t n_rivers, int64_t n_points, int64_
 #undef RR_RUNOFF_ADJ_WEIGHT
         HIPCHK(hipGetLastError());
     }
+    return RR_OK;
+}
+
+}  // extern "C"
+
+// ---- skill scores and their adjoint over records with gaps (rr_kernels_metrics_missing.hpp; DESIGN.md sections 9 and 12c) ----
+
+#include "rr_kernels_metrics_missing.hpp"      // here, last of all: every kernel above keeps its place in the code object
+
+extern "C" {
+
+int rr_metrics_update_missing_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                                  const void *y_pred, int pred_is_f32, int64_t pred_pitch, const int32_t *pred_columns, double *state,
+                                  void *work, int64_t work_bytes, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_update_missing_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    int64_t need = 0;
+    if (int rc = rr_metrics_work_bytes(n, rows, &need)) return rc;
+    if (n == 0 || rows == 0) return RR_OK;
+    if (!y_true || !y_pred || !state) return fail(RR_E_INVALID, "rr_metrics_update_missing_dev: null array");
+    if (true_pitch < n || pred_pitch < (pred_columns ? 1 : n))
+        return fail(RR_E_INVALID, "rr_metrics_update_missing_dev: row pitch shorter than the columns read");
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_metrics_update_missing_dev: work memory smaller than rr_metrics_work_bytes (" + std::to_string(need) + " bytes)");
+    int64_t splits, rows_per_split;
+    metrics_split(n, rows, splits, rows_per_split);
+    double *slab = static_cast<double *>(work);
+    const dim3 g((unsigned)((n + kBlock - 1) / kBlock), (unsigned)splits);
+#define RR_METRICS_MISSING_LAUNCH(TT_, TP_)                                                                                       \
+    hipLaunchKernelGGL((k_metrics_partial_missing<TT_, TP_>), g, dim3(kBlock), 0, (hipStream_t)stream, (const TT_ *)y_true,        \
+                       true_pitch, (const TP_ *)y_pred, pred_pitch, pred_columns, n, rows, rows_per_split, slab)
+    if (true_is_f32) { if (pred_is_f32) RR_METRICS_MISSING_LAUNCH(float, float); else RR_METRICS_MISSING_LAUNCH(float, double); }
+    else { if (pred_is_f32) RR_METRICS_MISSING_LAUNCH(double, float); else RR_METRICS_MISSING_LAUNCH(double, double); }
+#undef RR_METRICS_MISSING_LAUNCH
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_metrics_merge, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, slab, splits, n, state);
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+int rr_metrics_adjoint_missing_dev(int device, int64_t n, int64_t rows, const void *y_true, int true_is_f32, int64_t true_pitch,
+                                   const void *y_pred, int pred_is_f32, int64_t pred_pitch, const double *state, const double *grad_scores,
+                                   int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
+                                   void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_adjoint_missing_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    int64_t need = 0;
+    if (int rc = rr_metrics_adjoint_work_bytes(n, &need)) return rc;
+    if (rows < 0) return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: sizes out of range");
+    if (n == 0 || rows == 0) return RR_OK;
+    if (!y_true || !y_pred || !state || !grad_scores || !grad_pred) return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: null array");
+    const bool mapped = order || distinct_columns || segments;
+    if (mapped && !(order && distinct_columns && segments))
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: order, distinct_columns and segments come together or not at all");
+    if (mapped ? (n_distinct < 1 || n_distinct > n) : n_distinct != n)
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: n_distinct must be n without a column map and 1 .. n with one");
+    if (true_pitch < n || pred_pitch < (mapped ? 1 : n) || grad_pitch < (mapped ? 1 : n))
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: row pitch shorter than the columns read or written");
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_metrics_adjoint_missing_dev: work memory smaller than rr_metrics_adjoint_work_bytes (" + std::to_string(need) + " bytes)");
+    double *coef = static_cast<double *>(work);
+    hipLaunchKernelGGL(k_metrics_adjoint_coef, grid1(n), dim3(kBlock), 0, (hipStream_t)stream, state, grad_scores, n, coef);
+    HIPCHK(hipGetLastError());
+    int64_t splits, rows_per_split;
+    metrics_split(n_distinct, rows, splits, rows_per_split);      // the forward's row ranges
+    const dim3 g((unsigned)((n_distinct + kBlock - 1) / kBlock), (unsigned)splits);
+#define RR_METRICS_ADJ_MISSING_LAUNCH(TT_, TP_)                                                                                          \
+    hipLaunchKernelGGL((k_metrics_adjoint_rows_missing<TT_, TP_>), g, dim3(kBlock), 0, (hipStream_t)stream, (const TT_ *)y_true, true_pitch, \
+                       (const TP_ *)y_pred, pred_pitch, (const double *)coef, n, order, distinct_columns, segments, n_distinct, rows,       \
+                       rows_per_split, (TP_ *)grad_pred, grad_pitch)
+    if (true_is_f32) { if (pred_is_f32) RR_METRICS_ADJ_MISSING_LAUNCH(float, float); else RR_METRICS_ADJ_MISSING_LAUNCH(float, double); }
+    else { if (pred_is_f32) RR_METRICS_ADJ_MISSING_LAUNCH(double, float); else RR_METRICS_ADJ_MISSING_LAUNCH(double, double); }
+#undef RR_METRICS_ADJ_MISSING_LAUNCH
+    HIPCHK(hipGetLastError());
     return RR_OK;
 }
 

@@ -13,7 +13,8 @@ from ._lib import RRError, check, ptr
 
 __all__ = ['Plan', 'RRError', 'uh_convolve', 'uh_convolve_dev', 'uh_adjoint_work_bytes', 'uh_adjoint_dev', 'runoff_to_qlateral', 'DeviceBuffer', 'partition_forest', 'synchronize',
            'resample_cast_dev', 'copy_bandwidth', 'runoff_to_qlateral_dev', 'runoff_adjoint_work_bytes', 'runoff_adjoint_dev', 'rows_upload', 'rows_download', 'metrics_work_bytes',
-           'metrics_update_dev', 'metrics_finish_dev', 'metrics_adjoint_work_bytes', 'metrics_adjoint_dev', 'grid_overlap_area',
+           'metrics_update_dev', 'metrics_finish_dev', 'metrics_adjoint_work_bytes', 'metrics_adjoint_dev', 'metrics_update_missing_dev',
+           'metrics_adjoint_missing_dev', 'grid_overlap_area',
            'grid_overlap_area_dev']
 
 
@@ -730,6 +731,25 @@ def metrics_adjoint_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_i
                                             int(bool(pred_is_f32)), int(pred_pitch), ptr(state), ptr(grad_scores), int(n_distinct),
                                             ptr(order), ptr(distinct_columns), ptr(segments), ptr(grad_pred), int(grad_pitch), ptr(work),
                                             int(work_bytes), stream))
+
+
+def metrics_update_missing_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is_f32, pred_pitch, pred_columns, state, work,
+                               work_bytes, device: int = 0, stream=None) -> None:
+    """rr_metrics_update_missing_dev: metrics_update_dev that leaves out the pairs whose y_true is NaN; only enqueues."""
+    check(_lib.lib().rr_metrics_update_missing_dev(int(device), int(n), int(rows), ptr(y_true), int(bool(true_is_f32)), int(true_pitch),
+                                                   ptr(y_pred), int(bool(pred_is_f32)), int(pred_pitch), ptr(pred_columns), ptr(state),
+                                                   ptr(work), int(work_bytes), stream))
+
+
+def metrics_adjoint_missing_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is_f32, pred_pitch, state, grad_scores, n_distinct,
+                                order, distinct_columns, segments, grad_pred, grad_pitch, work, work_bytes, device: int = 0,
+                                stream=None) -> None:
+    """rr_metrics_adjoint_missing_dev: metrics_adjoint_dev for a state metrics_update_missing_dev left: an element whose y_true is NaN
+    gets exactly 0 from that column; only enqueues."""
+    check(_lib.lib().rr_metrics_adjoint_missing_dev(int(device), int(n), int(rows), ptr(y_true), int(bool(true_is_f32)), int(true_pitch),
+                                                    ptr(y_pred), int(bool(pred_is_f32)), int(pred_pitch), ptr(state), ptr(grad_scores),
+                                                    int(n_distinct), ptr(order), ptr(distinct_columns), ptr(segments), ptr(grad_pred),
+                                                    int(grad_pitch), ptr(work), int(work_bytes), stream))
 
 
 def grid_overlap_area(row_rings, ring_offsets, ring_weight, lon, lat, x_bounds, y_bounds, row_cells, pair_offsets,

@@ -48,6 +48,12 @@ section 12c): the same five values, bit for bit, and a backward pass that writes
     kge = rr.grad.scores(observed, Q, columns=gauges)['kge2012']      # observed[T, n_gauges] against Q[:, gauges], no gather copy
     (1 - kge).mean().backward()
 
+Gauge records have gaps; with skip_missing=True a NaN in `observed` is a missing observation, every gauge is scored over its own
+kept pairs, a skipped element gets the gradient 0, and 'count' (no graph) says how many pairs each gauge kept:
+
+    s = rr.grad.scores(observed, Q, columns=gauges, skip_missing=True)
+    (1 - s['kge2012'][s['count'] >= 2]).mean().backward()
+
 The router's chain starts one step before the catchment inflow when it is fed gridded runoff, and runoff_to_qlateral is that step with
 a gradient: the forward is rr_runoff_to_qlateral_dev, bit for bit what engine.runoff_to_qlateral computes
 (weights product, cumulative -> incremental, clip, NaN fill, area), the backward rr_runoff_adjoint_dev, which reaches the runoff field
@@ -856,10 +862,11 @@ class Scores(torch.autograd.Function):
     y_pred, a (T, m) or (T,) tensor.  Forward: rr_metrics_update_dev and rr_metrics_finish_dev, as rr.metrics.scores calls them.
     Backward: rr_metrics_adjoint_dev from the 9 x n state the forward left; beside it only the two inputs (saved tensors, read in
     place) and the sorted column map are kept.  cols is None or (columns, order, distinct columns, segment starts) as int32 host
-    arrays."""
+    arrays.  skip_missing: both passes through rr_metrics_update_missing_dev / rr_metrics_adjoint_missing_dev, and out[6, n] with the
+    kept pairs per column (row 0 of the state) as its last row, which `scores` returns detached."""
 
     @staticmethod
-    def forward(ctx, y_pred, y_true, cols):
+    def forward(ctx, y_pred, y_true, cols, skip_missing=False):
         t, p = y_true, metrics._Rows(y_pred.detach(), 'y_pred').tensor
         dev, where = p.device.index or 0, p.device
         T, n = (int(v) for v in t.shape)
@@ -870,10 +877,14 @@ class Scores(torch.autograd.Function):
         nbytes = engine.metrics_work_bytes(n, T)
         work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=where)
         n_distinct = n if cols is None else len(cols[2])
-        engine.metrics_update_dev(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p),
-                                  column_map_pointers(cols_dev, n, n_distinct)[0], state, work, nbytes, device=dev, stream=stream)
-        out = torch.empty((engine.METRICS_SCORES, n), dtype=torch.float64, device=where)
-        engine.metrics_finish_dev(n, state, out, device=dev, stream=stream)
+        update = engine.metrics_update_missing_dev if skip_missing else engine.metrics_update_dev
+        update(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p),
+               column_map_pointers(cols_dev, n, n_distinct)[0], state, work, nbytes, device=dev, stream=stream)
+        out = torch.empty((engine.METRICS_SCORES + (1 if skip_missing else 0), n), dtype=torch.float64, device=where)
+        engine.metrics_finish_dev(n, state, out, device=dev, stream=stream)      # rows 0 .. 4
+        if skip_missing:
+            out[engine.METRICS_SCORES] = state[0]
+        ctx.skip_missing = bool(skip_missing)
         ctx.save_for_backward(t, p, state, cols_dev)      # a change of the rows in place between the two passes is noticed
         ctx.n_distinct = n_distinct
         ctx.pred_shape = tuple(y_pred.shape)
@@ -884,22 +895,23 @@ class Scores(torch.autograd.Function):
     @torch.autograd.function.once_differentiable
     def backward(ctx, grad_out):
         if grad_out is None or not ctx.needs_input_grad[0]:
-            return None, None, None
+            return None, None, None, None
         t, p, state, cols_dev = ctx.saved_tensors
         dev, where, nd = p.device.index or 0, p.device, ctx.n_distinct
         T, n = (int(v) for v in t.shape)
         m = int(p.shape[1])
         f32 = torch.float32
-        g = grad_out.to(dtype=torch.float64, device=where).contiguous()
+        g = grad_out[:engine.METRICS_SCORES].to(dtype=torch.float64, device=where).contiguous()      # 'count' passes no gradient
         _, order, distinct, segments = column_map_pointers(cols_dev, n, nd)
         # unscored columns are zero and stay so: the kernel writes the scored ones only
         make = torch.empty if cols_dev is None else torch.zeros
         grad = make((T, m), dtype=p.dtype, device=where)
         nbytes = engine.metrics_adjoint_work_bytes(n)
         work = torch.empty(max(nbytes, 8), dtype=torch.uint8, device=where)
-        engine.metrics_adjoint_dev(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p), state, g, nd, order,
-                                   distinct, segments, grad, m, work, nbytes, device=dev, stream=torch.cuda.current_stream(dev).cuda_stream)
-        return grad.reshape(ctx.pred_shape), None, None
+        adjoint = engine.metrics_adjoint_missing_dev if ctx.skip_missing else engine.metrics_adjoint_dev
+        adjoint(n, T, t.data_ptr(), t.dtype == f32, _pitch(t), p.data_ptr(), p.dtype == f32, _pitch(p), state, g, nd, order,
+                distinct, segments, grad, m, work, nbytes, device=dev, stream=torch.cuda.current_stream(dev).cuda_stream)
+        return grad.reshape(ctx.pred_shape), None, None, None
 
 
 def _check_series(a, name):
@@ -928,7 +940,7 @@ def _sorted_columns(columns, n, m):
     return tuple(a.astype(np.int32) for a in (c, order, distinct, np.append(starts, n)))
 
 
-def scores(y_true, y_pred, columns=None) -> dict:
+def scores(y_true, y_pred, columns=None, skip_missing=False) -> dict:
     """rr.metrics.scores with autograd: {'me', 'mae', 'mse', 'pearson_r', 'kge2012'} -> (n,) float64 tensors on the GPU, the values
     rr.metrics.scores returns for the same tensors bit for bit, each carrying a graph to y_pred.
 
@@ -941,7 +953,13 @@ def scores(y_true, y_pred, columns=None) -> dict:
     nobody scores get 0, a column scored several times the sum of its shares.  A score whose incoming gradient is exactly 0 for a
     column adds nothing there, so a constant series may sit in an mse loss although its pearson_r and kge2012 are NaN; a NaN score
     with a non-zero gradient makes the column's gradient NaN.  No atomics: two backward passes give the same bits.  Every argument
-    is checked before the GPU is touched."""
+    is checked before the GPU is touched.
+
+    skip_missing=True: a NaN in y_true is a missing observation, as in rr.metrics.scores(..., skip_missing=True): column j's pair at
+    that row is left out of its sums, and the result has the key 'count' (the pairs kept per column, detached: no graph).  The
+    gradient at a kept element is the same closed form with the kept pairs' count and moments; at a skipped element column j adds
+    exactly 0.0, never NaN, and a column that keeps nothing adds zeros.  With repeats in columns= every share is masked by its own
+    y_true column.  A NaN score with a non-zero gradient makes the gradient NaN at the column's kept rows."""
     T, n = _check_series(y_true, 'y_true')
     Tp, m = _check_series(y_pred, 'y_pred')
     if y_true.requires_grad:
@@ -970,8 +988,11 @@ def scores(y_true, y_pred, columns=None) -> dict:
         raise ValueError(f'y_true is on {y_true.device}, y_pred on {y_pred.device}')
     if columns is not None and cols is None:
         cols = _sorted_columns(columns.detach().cpu(), n, m)
-    out = Scores.apply(y_pred, metrics._Rows(y_true, 'y_true').tensor, cols)
-    return {k: out[i] for i, k in enumerate(metrics.SCORES)}
+    out = Scores.apply(y_pred, metrics._Rows(y_true, 'y_true').tensor, cols, bool(skip_missing))
+    res = {k: out[i] for i, k in enumerate(metrics.SCORES)}
+    if skip_missing:
+        res['count'] = out[engine.METRICS_SCORES].detach()
+    return res
 
 
 class RunoffMap:

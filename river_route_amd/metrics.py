@@ -15,6 +15,10 @@ path run on each column of the float64 data (float32 data: widened to float64) t
 a column that is exactly constant has M2 == 0 on the device, so its pearson_r and kge2012 are nan, where numpy's
 mean-then-subtract can leave a tiny non-zero standard deviation (1.4e-17 for 35,040 copies of 0.1) and the reference's
 KGE then returns a finite number.
+
+Gauge records with gaps: every function, `scores` and `Accumulator` take skip_missing=False.  With True a NaN in y_true marks a
+missing observation and that pair is left out (1-D on the host: dropped before the reference's numpy calls; per column on the
+GPU: rr_metrics_update_missing_dev), each column scored over its own kept pairs, whose number `scores` returns as 'count'.
 """
 from __future__ import annotations
 
@@ -34,40 +38,66 @@ def _torch_tensor(a) -> bool:
     return t is not None and isinstance(a, t.Tensor)
 
 
+def _kept(y_true, y_pred):
+    """The pairs of two 1-D series whose y_true is not NaN (skip_missing=True on the host); without a NaN the inputs themselves,
+    so a gap-free series is scored by the very same numpy calls."""
+    t, p = np.asarray(y_true), np.asarray(y_pred)
+    if t.ndim != 1 or t.shape != p.shape:
+        raise ValueError(f'skip_missing needs two 1-D series of one length (got shapes {t.shape} and {p.shape})')
+    keep = ~np.isnan(t)
+    return (y_true, y_pred) if keep.all() else (t[keep], p[keep])
+
+
 def _batched(y_true, y_pred) -> bool:
     """Per-column scores on the GPU: a torch tensor, or a 2-D array."""
     return _torch_tensor(y_true) or _torch_tensor(y_pred) or np.ndim(y_true) == 2 or np.ndim(y_pred) == 2
 
 
-def mean_error(y_true, y_pred):
+def mean_error(y_true, y_pred, skip_missing=False):
     """Mean of y_true - y_pred (the reference's sign: positive when the simulation is low)."""
     if _batched(y_true, y_pred):
-        return scores(y_true, y_pred)['me']
+        return scores(y_true, y_pred, skip_missing=skip_missing)['me']
+    if skip_missing:
+        y_true, y_pred = _kept(y_true, y_pred)
+        if len(y_true) == 0:
+            return np.float64(np.nan)
     return np.mean(np.asarray(y_true) - np.asarray(y_pred))
 
 
-def mean_absolute_error(y_true, y_pred):
+def mean_absolute_error(y_true, y_pred, skip_missing=False):
     """Mean of |y_true - y_pred|."""
     if _batched(y_true, y_pred):
-        return scores(y_true, y_pred)['mae']
+        return scores(y_true, y_pred, skip_missing=skip_missing)['mae']
+    if skip_missing:
+        y_true, y_pred = _kept(y_true, y_pred)
+        if len(y_true) == 0:
+            return np.float64(np.nan)
     return np.mean(np.abs(np.asarray(y_true) - np.asarray(y_pred)))
 
 
-def mean_square_error(y_true, y_pred):
+def mean_square_error(y_true, y_pred, skip_missing=False):
     """Mean of (y_true - y_pred) ** 2."""
     if _batched(y_true, y_pred):
-        return scores(y_true, y_pred)['mse']
+        return scores(y_true, y_pred, skip_missing=skip_missing)['mse']
+    if skip_missing:
+        y_true, y_pred = _kept(y_true, y_pred)
+        if len(y_true) == 0:
+            return np.float64(np.nan)
     return np.mean((np.asarray(y_true) - np.asarray(y_pred)) ** 2)
 
 
-def pearson_r(y_true, y_pred):
+def pearson_r(y_true, y_pred, skip_missing=False):
     """Pearson correlation as np.corrcoef gives it: clipped to [-1, 1], nan when either series has zero variance."""
     if _batched(y_true, y_pred):
-        return scores(y_true, y_pred)['pearson_r']
+        return scores(y_true, y_pred, skip_missing=skip_missing)['pearson_r']
+    if skip_missing:
+        y_true, y_pred = _kept(y_true, y_pred)
+        if len(y_true) == 0:
+            return np.float64(np.nan)
     return np.corrcoef(y_true, y_pred)[0, 1]
 
 
-def kling_gupta_efficiency_2012(y_true, y_pred):
+def kling_gupta_efficiency_2012(y_true, y_pred, skip_missing=False):
     """Kling-Gupta efficiency as the reference computes it: 1 - sqrt((r - 1)^2 + (beta - 1)^2 + (gamma - 1)^2) with
     beta = mean_pred / mean_true and gamma = (mean_pred / std_pred) / (mean_true / std_true), standard deviations with
     ddof 0; nan when std_true, std_pred or mean_true is 0.
@@ -75,7 +105,11 @@ def kling_gupta_efficiency_2012(y_true, y_pred):
     Note: this gamma is the INVERSE of the coefficient-of-variation ratio of Kling et al. (2012), (std_pred / mean_pred) /
     (std_true / mean_true).  It is kept as the reference has it, so that scores agree with the reference's."""
     if _batched(y_true, y_pred):
-        return scores(y_true, y_pred)['kge2012']
+        return scores(y_true, y_pred, skip_missing=skip_missing)['kge2012']
+    if skip_missing:
+        y_true, y_pred = _kept(y_true, y_pred)
+        if len(y_true) == 0:
+            return np.float64(np.nan)
     r = pearson_r(y_true, y_pred)
     mean_true, mean_pred = np.mean(y_true), np.mean(y_pred)
     std_true, std_pred = np.std(y_true), np.std(y_pred)
@@ -92,14 +126,19 @@ mse = mean_square_error
 kge2012 = kling_gupta_efficiency_2012
 
 
-def scores(y_true, y_pred, columns=None) -> dict:
+def scores(y_true, y_pred, columns=None, skip_missing=False) -> dict:
     """All five scores per column from one read of (T, n) y_true and (T, m) y_pred: {'me', 'mae', 'mse', 'pearson_r',
     'kge2012'} -> (n,) arrays (numpy in: numpy out; torch in: device tensors out).  columns: optional int array of
     length n, column j of y_true is scored against column columns[j] of y_pred (repeats allowed; no gather copy is
-    made); without it m must equal n.  1-D inputs are scored as one column."""
+    made); without it m must equal n.  1-D inputs are scored as one column.
+
+    skip_missing=True: an element of y_true that is NaN (as stored) is a missing observation, and column j's pair at that row
+    is left out of all its sums; y_pred there is never looked at.  Every column is scored over its own kept pairs, and the
+    result has one more key, 'count': (n,) float64, the pairs kept per column (0: all five scores NaN; 1: pearson_r and
+    kge2012 NaN).  Inf is not missing, and a NaN of y_pred at a kept row still makes the column NaN."""
     t, p = _Rows(y_true, 'y_true'), _Rows(y_pred, 'y_pred')
     device = t.device if t.device is not None else (p.device if p.device is not None else 0)
-    acc = Accumulator(t.cols, columns=columns, device=device)
+    acc = Accumulator(t.cols, columns=columns, device=device, skip_missing=skip_missing)
     acc._update(t, p)
     return acc.result()
 
@@ -108,12 +147,15 @@ class Accumulator:
     """Per-column scores of series that arrive in row blocks: the rows of each input file of a run, or rows streamed
     from disk.  `update(true_rows, pred_rows)` merges (k, n) and (k, m) blocks into a per-column state kept on the GPU;
     `result()` returns the scores of all rows so far as `scores` does.  Splitting the rows differently changes results
-    by rounding only (within 1e-12 relative); the same blocks in the same order give bit-identical results."""
+    by rounding only (within 1e-12 relative); the same blocks in the same order give bit-identical results.
+    skip_missing (fixed at construction): every update leaves out the pairs whose true value is NaN, as `scores` describes,
+    and `result()` has the key 'count'; `rows` stays the number of rows seen, missing or not."""
 
-    def __init__(self, n: int, columns=None, device: int = 0):
+    def __init__(self, n: int, columns=None, device: int = 0, skip_missing: bool = False):
         from . import engine
         self._engine = engine
         self.n, self.device, self.rows = int(n), int(device), 0
+        self.skip_missing = bool(skip_missing)
         if self.n < 1:
             raise ValueError('Accumulator needs n >= 1 columns')
         self._columns, self._cols_dev = None, None
@@ -162,8 +204,9 @@ class Accumulator:
             if self._work is not None:
                 self._work.free()
             self._work = e.DeviceBuffer(need, self.device)
-        e.metrics_update_dev(self.n, t.rows, t.address, t.is_f32, t.pitch, p.address, p.is_f32, p.pitch, self._cols_dev, self._state,
-                             self._work, self._work.nbytes, device=self.device, stream=stream)
+        update = e.metrics_update_missing_dev if self.skip_missing else e.metrics_update_dev
+        update(self.n, t.rows, t.address, t.is_f32, t.pitch, p.address, p.is_f32, p.pitch, self._cols_dev, self._state,
+               self._work, self._work.nbytes, device=self.device, stream=stream)
         if t.uploaded is not None or p.uploaded is not None:
             e.synchronize(self.device)            # the uploaded copies are freed on return
         self.rows += t.rows
@@ -176,7 +219,7 @@ class Accumulator:
 
     def result(self) -> dict:
         """{'me', 'mae', 'mse', 'pearson_r', 'kge2012'} -> (n,) scores of every row so far: device tensors if any update
-        came as torch tensors, else numpy arrays."""
+        came as torch tensors, else numpy arrays.  With skip_missing also 'count', the pairs kept per column (row 0 of the state)."""
         e = self._engine
         if self._torch:
             import torch
@@ -184,6 +227,9 @@ class Accumulator:
             self._enter_stream(stream)
             out = torch.empty((len(SCORES), self.n), dtype=torch.float64, device=torch.device('cuda', self.device))
             e.metrics_finish_dev(self.n, self._state, out.data_ptr(), device=self.device, stream=stream)
+            if self.skip_missing:
+                # row 0 of the state, copied on the stream the finish was enqueued on
+                count = torch.as_tensor(_DeviceDoubles(self._state.address, self.n), device=out.device).clone()
         else:
             self._enter_stream(None)
             buf = e.DeviceBuffer(len(SCORES) * self.n * 8, self.device)
@@ -191,7 +237,20 @@ class Accumulator:
             e.synchronize(self.device)
             out = buf.download(np.float64, (len(SCORES), self.n))
             buf.free()
-        return {k: out[i] for i, k in enumerate(SCORES)}
+            if self.skip_missing:
+                count = self._state.download(np.float64, (self.n,))      # row 0 of the state
+        res = {k: out[i] for i, k in enumerate(SCORES)}
+        if self.skip_missing:
+            res['count'] = count
+        return res
+
+
+class _DeviceDoubles:
+    """`count` float64 values at a device address, for torch.as_tensor to look at in place (__cuda_array_interface__)."""
+
+    def __init__(self, address: int, count: int):
+        self.__cuda_array_interface__ = {'shape': (int(count),), 'typestr': '<f8', 'data': (int(address), False), 'strides': None,
+                                         'version': 2}
 
 
 class _Rows:
