@@ -661,6 +661,31 @@ int rr_metrics_adjoint_missing_dev(int device, int64_t n, int64_t rows, const vo
                                    int64_t n_distinct, const int32_t *order, const int32_t *distinct_columns, const int32_t *segments,
                                    void *grad_pred, int64_t grad_pitch, void *work, int64_t work_bytes, void *stream);
 
+/* ---- skill scores of the members of an ensemble in one launch ----
+ * rr_metrics_update_members_dev is rr_metrics_update_dev (skip_missing != 0: rr_metrics_update_missing_dev) for `members` blocks of
+ * rows at once: member m's element (r, c) of y_pred is at y_pred[m * pred_member_pitch + r * pred_pitch + c], its observation at
+ * y_true[m * true_member_pitch + r * true_pitch + c]; true_member_pitch == 0: one observation block that all members share.  All
+ * pitches are in elements and every member offset is formed in 64 bits, so the members may lie more than 2^31 elements apart.
+ * pred_columns[n] (may be NULL) is one map for all members.
+ * `state` is RR_METRICS_STATE x (members * n) doubles, field-major over the flattened index m * n + j (state[k * members * n +
+ * m * n + j]), zero-filled by the caller before the first update.  It is finished by rr_metrics_finish_dev(device, members * n, state,
+ * out, stream), whose out[5 * members * n] then reads as (5, members, n); row 0 of the state is the pairs kept, (members, n).
+ * The rows are cut by rr_metrics_update_dev's rule with members * ceil(n / 256) workgroups per row range in place of ceil(n / 256):
+ * a function of (n, members, rows) only (same inputs and the same sequence of updates: bit-identical results), and with members == 1
+ * the cut, and so every bit of the state, is that of rr_metrics_update_dev / rr_metrics_update_missing_dev (the member pitches are
+ * then not looked at).  Wherever members * ceil(n / 256) * ceil(rows / 32) <= 2048, both calls cut the rows into the same 32-row
+ * ranges and member m's columns of the state carry the bits of a single call on member m's rows.  Work memory:
+ * rr_metrics_members_work_bytes = splits x RR_METRICS_STATE x members * n doubles (0 when n or rows is 0), folded in split order.
+ * Enqueue only, allocates nothing, no atomics; pred_columns is not range-checked on the device.
+ * RR_E_INVALID: what rr_metrics_update_dev refuses; members < 1; members * n > 2^31 - 1; with members > 1, pred_member_pitch <
+ * (rows - 1) * pred_pitch + the columns read (n, or 1 with pred_columns), or a true_member_pitch other than 0 below
+ * (rows - 1) * true_pitch + n.  A refused call leaves `state` as it was. */
+int rr_metrics_members_work_bytes(int64_t n, int64_t members, int64_t rows, int64_t *bytes);
+int rr_metrics_update_members_dev(int device, int64_t n, int64_t members, int64_t rows, const void *y_true, int true_is_f32,
+                                  int64_t true_pitch, int64_t true_member_pitch, const void *y_pred, int pred_is_f32, int64_t pred_pitch,
+                                  int64_t pred_member_pitch, const int32_t *pred_columns, int skip_missing, double *state, void *work,
+                                  int64_t work_bytes, void *stream);
+
 /* ---- adjoint of gridded runoff -> catchment inflow (rr.grad.runoff_to_qlateral) ----
  * The gradient of a scalar loss L through one rr_runoff_to_qlateral_dev call with respect to the runoff block and to the weights.
  * n_rivers, n_points, T, the CSR arrays, runoff with its type and strides, area and flags are those of the forward call;

@@ -163,6 +163,9 @@ _SIGNATURES = {
     'rr_metrics_update_missing_dev': (C.c_int, [C.c_int, _i64, _i64, _vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _vp, _i64, _vp]),
     'rr_metrics_adjoint_missing_dev': (C.c_int, [C.c_int, _i64, _i64, _vp, C.c_int, _i64, _vp, C.c_int, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp,
                                                  _i64, _vp, _i64, _vp]),
+    'rr_metrics_members_work_bytes': (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64)]),
+    'rr_metrics_update_members_dev': (C.c_int, [C.c_int, _i64, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _vp,
+                                                _vp, _i64, _vp]),
     'rr_runoff_adjoint_work_bytes': (C.c_int, [_i64, _i64, _i64, C.POINTER(_i64)]),
     'rr_runoff_adjoint_dev': (C.c_int, [C.c_int, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, C.c_int, _i64, _i64, _vp, C.c_int, _vp, _vp, _i64,
                                         _vp, _vp, _i64, _vp]),

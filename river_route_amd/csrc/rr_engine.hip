@@ -16,8 +16,9 @@
 // rr_kernels_uh.hpp, rr_kernels_rec.hpp, rr_kernels_runoff.hpp, rr_kernels_direct.hpp, rr_kernels_metrics.hpp,
 // rr_kernels_overlap.hpp, rr_kernels_adjoint.hpp, rr_kernels_adjoint_unit.hpp (device code), rr_exec.hpp (plan object, executor),
 // then the C ABI below; rr_adjoint.hpp (the adjoints' host side), rr_kernels_metrics_adjoint.hpp (the adjoint of the skill
-// scores, device code), rr_kernels_runoff_adjoint.hpp (the adjoint of the gridded-runoff inflow, device code) and, last,
-// rr_kernels_metrics_missing.hpp (the skill scores and their adjoint over records with gaps, device code) are included where
+// scores, device code), rr_kernels_runoff_adjoint.hpp (the adjoint of the gridded-runoff inflow, device code),
+// rr_kernels_metrics_missing.hpp (the skill scores and their adjoint over records with gaps, device code) and, last,
+// rr_kernels_metrics_members.hpp (the skill scores of an ensemble's members in one launch, device code) are included where
 // their entry points are.
 #include "rr_common.hpp"
 #include "rr_kernels_tick.hpp"
@@ -1838,6 +1839,72 @@ int rr_metrics_adjoint_missing_dev(int device, int64_t n, int64_t rows, const vo
     if (true_is_f32) { if (pred_is_f32) RR_METRICS_ADJ_MISSING_LAUNCH(float, float); else RR_METRICS_ADJ_MISSING_LAUNCH(float, double); }
     else { if (pred_is_f32) RR_METRICS_ADJ_MISSING_LAUNCH(double, float); else RR_METRICS_ADJ_MISSING_LAUNCH(double, double); }
 #undef RR_METRICS_ADJ_MISSING_LAUNCH
+    HIPCHK(hipGetLastError());
+    return RR_OK;
+}
+
+}  // extern "C"
+
+// ---- skill scores of the members of an ensemble in one launch (rr_kernels_metrics_members.hpp) ----
+
+#include "rr_kernels_metrics_members.hpp"      // here, last of all: every kernel above keeps its place in the code object
+
+extern "C" {
+
+int rr_metrics_members_work_bytes(int64_t n, int64_t members, int64_t rows, int64_t *bytes)
+{
+    if (!bytes) return fail(RR_E_INVALID, "rr_metrics_members_work_bytes: null out");
+    if (n < 0 || rows < 0 || members < 1 || n > 0x7FFFFFFFLL || (n > 0 && members > 0x7FFFFFFFLL / n))
+        return fail(RR_E_INVALID, "rr_metrics_members_work_bytes: sizes out of range (members >= 1, members * n <= 2^31 - 1)");
+    *bytes = 0;
+    if (n == 0 || rows == 0) return RR_OK;
+    int64_t splits, rows_per_split;
+    metrics_split(n, rows, splits, rows_per_split, members);
+    *bytes = splits * RR_METRICS_STATE * members * n * (int64_t)sizeof(double);
+    return RR_OK;
+}
+
+int rr_metrics_update_members_dev(int device, int64_t n, int64_t members, int64_t rows, const void *y_true, int true_is_f32,
+                                  int64_t true_pitch, int64_t true_member_pitch, const void *y_pred, int pred_is_f32, int64_t pred_pitch,
+                                  int64_t pred_member_pitch, const int32_t *pred_columns, int skip_missing, double *state, void *work,
+                                  int64_t work_bytes, void *stream)
+{
+    if (device < 0 || device >= rr_device_count()) return fail(RR_E_NO_DEVICE, "rr_metrics_update_members_dev: no such HIP device");
+    HIPCHK(hipSetDevice(device));
+    int64_t need = 0;
+    if (int rc = rr_metrics_members_work_bytes(n, members, rows, &need)) return rc;
+    if (n == 0 || rows == 0) return RR_OK;
+    if (!y_true || !y_pred || !state) return fail(RR_E_INVALID, "rr_metrics_update_members_dev: null array");
+    const int64_t pred_width = pred_columns ? 1 : n;
+    if (true_pitch < n || pred_pitch < pred_width)
+        return fail(RR_E_INVALID, "rr_metrics_update_members_dev: row pitch shorter than the columns read");
+    if (members > 1) {      // (one member: its pitches are never used)
+        // no real pitch is this long; refusing it keeps the products below in range
+        if (true_pitch > (INT64_MAX >> 1) / rows || pred_pitch > (INT64_MAX >> 1) / rows)
+            return fail(RR_E_INVALID, "rr_metrics_update_members_dev: row pitch out of range");
+        if (pred_member_pitch < (rows - 1) * pred_pitch + pred_width ||
+            (true_member_pitch != 0 && true_member_pitch < (rows - 1) * true_pitch + n))
+            return fail(RR_E_INVALID, "rr_metrics_update_members_dev: member pitch shorter than the rows one member spans");
+    }
+    if (!work || work_bytes < need)
+        return fail(RR_E_INVALID, "rr_metrics_update_members_dev: work memory smaller than rr_metrics_members_work_bytes (" + std::to_string(need) + " bytes)");
+    int64_t splits, rows_per_split;
+    metrics_split(n, rows, splits, rows_per_split, members);
+    double *slab = static_cast<double *>(work);
+    const int64_t col_blocks = (n + kBlock - 1) / kBlock, total = members * n;
+    const dim3 g((unsigned)(members * col_blocks), (unsigned)splits);
+#define RR_METRICS_MEMBERS_LAUNCH(MISSING_, TT_, TP_)                                                                                     \
+    hipLaunchKernelGGL((k_metrics_partial_members<MISSING_, TT_, TP_>), g, dim3(kBlock), 0, (hipStream_t)stream, (const TT_ *)y_true,      \
+                       true_pitch, true_member_pitch, (const TP_ *)y_pred, pred_pitch, pred_member_pitch, pred_columns, n, col_blocks,    \
+                       members, rows, rows_per_split, slab)
+#define RR_METRICS_MEMBERS_TYPES(MISSING_)                                                                                                \
+    if (true_is_f32) { if (pred_is_f32) RR_METRICS_MEMBERS_LAUNCH(MISSING_, float, float); else RR_METRICS_MEMBERS_LAUNCH(MISSING_, float, double); } \
+    else { if (pred_is_f32) RR_METRICS_MEMBERS_LAUNCH(MISSING_, double, float); else RR_METRICS_MEMBERS_LAUNCH(MISSING_, double, double); }
+    if (skip_missing) { RR_METRICS_MEMBERS_TYPES(true) } else { RR_METRICS_MEMBERS_TYPES(false) }
+#undef RR_METRICS_MEMBERS_TYPES
+#undef RR_METRICS_MEMBERS_LAUNCH
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_metrics_merge, grid1(total), dim3(kBlock), 0, (hipStream_t)stream, slab, splits, total, state);
     HIPCHK(hipGetLastError());
     return RR_OK;
 }

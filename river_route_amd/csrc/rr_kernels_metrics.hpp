@@ -173,9 +173,10 @@ __global__ __launch_bounds__(kBlock) void k_metrics_finish(const double *__restr
 
 // How an update of `rows` rows of n columns is cut: splits x rows_per_split, rows_per_split a whole number of chunks.
 // A function of (n, rows) only, so rr_metrics_work_bytes and the update agree and a repeated update repeats its sums.
-inline void metrics_split(int64_t n, int64_t rows, int64_t &splits, int64_t &rows_per_split)
+// members > 1 (rr_metrics_update_members_dev): one row range takes members x ceil(n / 256) workgroups, a function of (n, members, rows).
+inline void metrics_split(int64_t n, int64_t rows, int64_t &splits, int64_t &rows_per_split, int64_t members = 1)
 {
-    const int64_t col_blocks = (n + kBlock - 1) / kBlock;
+    const int64_t col_blocks = members * ((n + kBlock - 1) / kBlock);
     const int64_t chunks = (rows + kMetricsChunk - 1) / kMetricsChunk;
     const int64_t want = std::max<int64_t>(1, (kMetricsTargetBlocks + col_blocks - 1) / col_blocks);
     splits = std::max<int64_t>(1, std::min(want, chunks));

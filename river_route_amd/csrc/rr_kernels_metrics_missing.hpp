@@ -1,7 +1,8 @@
 // rr_kernels_metrics_missing.hpp -- the skill scores of rr_kernels_metrics.hpp and their gradient (rr_kernels_metrics_adjoint.hpp)
 // over gauge records with gaps: element (r, j) is missing when y_true[r, j] is NaN, and the pair (y_true[r, j], y_pred[r, col[j]])
 // is then left out of column j's sums and gets no gradient (DESIGN.md sections 9 and 12c, "Missing observations").
-// Part of the one translation unit rr_engine.hip builds (included from there, LAST; not a stand-alone header).
+// Part of the one translation unit rr_engine.hip builds (included from there, after every kernel but those of
+// rr_kernels_metrics_members.hpp; not a stand-alone header).
 //
 // The two row loops of k_metrics_partial and k_metrics_adjoint_rows are restated here, not shared through a template parameter:
 // kernels lie in the code object in the order they are first named and the routing kernels' speed depends on their place, so the

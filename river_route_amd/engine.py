@@ -384,22 +384,33 @@ class Plan:
                                                      int(lateral_member_pitch), ptr(discharge), int(bool(discharge_is_f32)), int(discharge_member_pitch),
                                                      int(factor), int(T), int(num_substeps), stream))
 
-    def _route_member_groups(self, q_t, qlateral, M, discharge, num_substeps, factor, route_dev, per_group=None) -> np.ndarray:
+    def _route_member_groups(self, q_t, qlateral, M, discharge, num_substeps, factor, route_dev, per_group=None, sink=None) -> np.ndarray:
         """The host-array driver behind rapid_route_ensemble and rapid_route_members: M members' rows (M, T, n) -- or one (T, n) forcing that
         all members share, uploaded once and passed with member pitch 0 -- go to the device in groups of the size the reservation reports
         (members_max), each group routed by `route_dev` (rapid_route_ensemble_dev's signature).  `per_group(g0, m)` is called before each
         group with its range, and once before the first reservation with (0, 0): rapid_route_members puts the group's coefficient sets
-        on the plan there.  Returns the (M, n) final states."""
+        on the plan there.  Returns the (M, n) final states.
+        Each group's (m, rows, n) discharge block is downloaded into `discharge`; with a `sink` it stays on the device instead: `discharge`
+        is then the rows' dtype (float32 or float64), no host array, and `sink(g0, m, d_out)` is called after each group is enqueued, on the
+        stream it was enqueued on, with the device buffer that holds its block (reused by the next group)."""
         ql = np.asarray(qlateral)
         if ql.dtype != np.float32:
             ql = np.asarray(ql, dtype=np.float64)
         shared, (T, n) = ql.ndim == 2, ql.shape[-2:]
         q0 = np.array(np.broadcast_to(np.asarray(q_t, dtype=np.float64), (M, n)), order='C')      # (a copy: returned as the final states)
-        f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
-        rows = T // int(factor) if f32_out else T
-        if not (isinstance(discharge, np.ndarray) and discharge.dtype in (np.float32, np.float64) and discharge.flags['C_CONTIGUOUS']
-                and discharge.flags['WRITEABLE'] and discharge.shape == (M, rows, n) and (f32_out or int(factor) == 1)):
-            raise ValueError(f'discharge must be a writeable C-contiguous float64 ({M}, {T}, {n}) array, or float32 ({M}, T / factor, {n})')
+        if sink is not None:
+            out_dtype = np.dtype(discharge)
+            f32_out = out_dtype == np.float32
+            rows = T // int(factor) if f32_out else T
+            if out_dtype not in (np.float32, np.float64) or not (f32_out or int(factor) == 1):
+                raise ValueError('the rows are float64 (factor 1) or float32 (each the mean of `factor` routed rows)')
+        else:
+            f32_out = isinstance(discharge, np.ndarray) and discharge.dtype == np.float32
+            rows = T // int(factor) if f32_out else T
+            if not (isinstance(discharge, np.ndarray) and discharge.dtype in (np.float32, np.float64) and discharge.flags['C_CONTIGUOUS']
+                    and discharge.flags['WRITEABLE'] and discharge.shape == (M, rows, n) and (f32_out or int(factor) == 1)):
+                raise ValueError(f'discharge must be a writeable C-contiguous float64 ({M}, {T}, {n}) array, or float32 ({M}, T / factor, {n})')
+            out_dtype = discharge.dtype
         f32_in = ql.dtype == np.float32
         nsub = int(num_substeps)
         if M == 0 or T == 0 or n == 0:
@@ -410,7 +421,7 @@ class Plan:
         if group < 1:
             raise RRError(_lib.RR_E_UNSUPPORTED, 'the record ring of one member does not fit the card at this shape')
         # members_max budgets the record rings only: the group's rows must fit beside them, so a group the device refuses is halved
-        lat_each, out_each = T * n * ql.itemsize, rows * n * discharge.itemsize
+        lat_each, out_each = T * n * ql.itemsize, rows * n * out_dtype.itemsize
         while True:
             bufs = []
             try:
@@ -436,7 +447,10 @@ class Plan:
                     d_ql.upload(np.ascontiguousarray(ql[g0:g0 + m]))
                 d_q.upload(q0[g0:g0 + m])
                 route_dev(m, d_q, n, d_ql, f32_in, 0 if shared else T * n, d_out, f32_out, rows * n, int(factor), T, nsub)
-                discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
+                if sink is not None:
+                    sink(g0, m, d_out)
+                else:
+                    discharge[g0:g0 + m] = d_out.download(discharge.dtype, (m, rows, n))
                 q0[g0:g0 + m] = d_q.download(np.float64, (m, n))
         finally:
             for b in (d_ql, d_out, d_q):
@@ -491,6 +505,12 @@ class Plan:
         all members -- or (M, T, n), float64 or float32; q_t (n,) or (M, n); discharge (M, T, n) float64, or (M, T / factor, n) float32 (each
         row the mean of `factor` routed rows).  Returns the (M, n) final states.  Where the reservation (members_max) or the device's memory
         does not take all members at once they are routed in groups, each group's coefficient sets set again from the arrays the plan keeps."""
+        ql, M, q_in, sets_on_plan = self._members_inputs(q_t, qlateral, factor)
+        return self._route_member_groups(q_in, ql, M, discharge, num_substeps, factor, self.rapid_route_members_dev, sets_on_plan)
+
+    def _members_inputs(self, q_t, qlateral, factor):
+        """The checks rapid_route_members and rapid_route_members_scores share, before any device work: (qlateral as an array, M, q_t as
+        float64, the per-group hook that keeps the group's coefficient sets on the plan)."""
         ql = np.asarray(qlateral)
         if ql.ndim not in (2, 3) or ql.shape[-1] != self.n:
             raise ValueError(f'qlateral must have shape (T, {self.n}) or (M, T, {self.n})')
@@ -513,7 +533,63 @@ class Plan:
                     self._upload_member_coeffs(0, M)
             elif on != (g0, m) and not (g0 == 0 and on == (0, M)):
                 self._upload_member_coeffs(g0, m)
-        return self._route_member_groups(q_in, ql, M, discharge, num_substeps, factor, self.rapid_route_members_dev, sets_on_plan)
+        return ql, M, q_in, sets_on_plan
+
+    def rapid_route_members_scores(self, q_t, qlateral, observed, gauges, num_substeps: int, factor: int = 1, skip_missing: bool = False,
+                                   skip_rows: int = 0, dtype=np.float32):
+        """Route the M members of set_member_coeffs as rapid_route_members does and score each at its gauges without the discharge
+        leaving the device: returns (scores, q_final), scores {'me', 'mae', 'mse', 'pearson_r', 'kge2012'[, 'count']} -> (M, G) float64
+        (rr.metrics.scores_members' keys) and q_final the (M, n) final states.  q_t and qlateral are rapid_route_members'.  The scored
+        rows are the rows rapid_route_members would write: dtype float32 -- (M, T // factor, n), each the mean of `factor` routed rows
+        -- or float64 -- (M, T, n), factor 1.  observed: (rows, G) float32 or float64, uploaded once; gauges: (G,) reach indices in
+        params order, repeats allowed; skip_missing: a NaN in `observed` is a gap (rr.metrics.scores); skip_rows: the first output rows
+        (spin-up) are left out of the scores.  Each group's (m, rows, n) block is scored by an rr.metrics.MemberAccumulator on the
+        stream it was routed on; only the scores and the final states come back.  Member m's scores are the bits of
+        rr.metrics.scores(observed[skip_rows:], out[m][skip_rows:], columns=gauges) on rapid_route_members' rows wherever
+        m_group x ceil(G / 256) x ceil(rows / 32) <= 2048."""
+        from . import metrics
+        ql, M, q_in, sets_on_plan = self._members_inputs(q_t, qlateral, factor)
+        T, n = ql.shape[-2:]
+        out_dtype = np.dtype(dtype)
+        if out_dtype not in (np.float32, np.float64):
+            raise ValueError('dtype must be float32 or float64')
+        if out_dtype == np.float64 and int(factor) != 1:
+            raise ValueError('float64 rows are never averaged: factor must be 1 (or pass dtype=float32)')
+        rows, skip = (T // int(factor) if out_dtype == np.float32 else T), int(skip_rows)
+        cols = np.asarray(gauges)
+        if cols.ndim != 1 or cols.size < 1 or not np.issubdtype(cols.dtype, np.integer):
+            raise ValueError('gauges must be a 1-D integer array of at least one reach index')
+        if cols.min() < 0 or cols.max() >= n:
+            raise ValueError(f'gauges holds a reach index outside 0 .. {n - 1}')
+        G = cols.shape[0]
+        obs = np.asarray(observed)
+        if obs.dtype not in (np.float32, np.float64):
+            obs = obs.astype(np.float64)
+        if obs.shape != (rows, G):
+            raise ValueError(f'observed must have shape ({rows}, {G}): one row per output row, one column per gauge; got {obs.shape}')
+        if not 0 <= skip < rows:
+            raise ValueError(f'skip_rows must leave at least one of the {rows} rows (0 <= skip_rows < rows)')
+        obs = np.ascontiguousarray(obs)
+        keys = metrics.SCORES + (('count',) if skip_missing else ())
+        scores = {k: np.empty((M, G)) for k in keys}
+        d_obs = []
+
+        def score_group(g0, m, d_out):
+            if not d_obs:
+                d_obs.append(DeviceBuffer(obs.nbytes, self.device).upload(obs))
+            acc = metrics.MemberAccumulator(G, m, columns=cols, device=self.device, skip_missing=skip_missing)
+            acc._enter_stream(None)
+            acc._launch(rows - skip, d_obs[0].address + skip * G * obs.itemsize, obs.dtype == np.float32, G, 0,
+                        d_out.address + skip * n * out_dtype.itemsize, out_dtype == np.float32, n, rows * n, None)
+            for k, v in acc.result().items():
+                scores[k][g0:g0 + m] = v
+        try:
+            q_final = self._route_member_groups(q_in, ql, M, out_dtype, num_substeps, factor, self.rapid_route_members_dev, sets_on_plan,
+                                                sink=score_group)
+        finally:
+            for b in d_obs:
+                b.free()
+        return scores, q_final
 
     def muskingum_route_f32_dev(self, q_t, discharge32, num_output_steps, num_routing_per_output, stream=None) -> None:
         self.reserve(MODE_MUSKINGUM, num_output_steps, num_routing_per_output, f32_out=True)
@@ -739,6 +815,23 @@ def metrics_update_missing_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred,
     check(_lib.lib().rr_metrics_update_missing_dev(int(device), int(n), int(rows), ptr(y_true), int(bool(true_is_f32)), int(true_pitch),
                                                    ptr(y_pred), int(bool(pred_is_f32)), int(pred_pitch), ptr(pred_columns), ptr(state),
                                                    ptr(work), int(work_bytes), stream))
+
+
+def metrics_members_work_bytes(n: int, members: int, rows: int) -> int:
+    """rr_metrics_members_work_bytes: device work memory one rr_metrics_update_members_dev of `rows` rows of `members` x n columns needs."""
+    out = C.c_int64(0)
+    check(_lib.lib().rr_metrics_members_work_bytes(int(n), int(members), int(rows), C.byref(out)))
+    return int(out.value)
+
+
+def metrics_update_members_dev(n, members, rows, y_true, true_is_f32, true_pitch, true_member_pitch, y_pred, pred_is_f32, pred_pitch,
+                               pred_member_pitch, pred_columns, skip_missing, state, work, work_bytes, device: int = 0, stream=None) -> None:
+    """rr_metrics_update_members_dev: merge `rows` device rows of each of `members` members into the [9][members * n] float64 score state
+    (true_member_pitch 0: one observation block for all members); only enqueues."""
+    check(_lib.lib().rr_metrics_update_members_dev(int(device), int(n), int(members), int(rows), ptr(y_true), int(bool(true_is_f32)),
+                                                   int(true_pitch), int(true_member_pitch), ptr(y_pred), int(bool(pred_is_f32)),
+                                                   int(pred_pitch), int(pred_member_pitch), ptr(pred_columns), int(bool(skip_missing)),
+                                                   ptr(state), ptr(work), int(work_bytes), stream))
 
 
 def metrics_adjoint_missing_dev(n, rows, y_true, true_is_f32, true_pitch, y_pred, pred_is_f32, pred_pitch, state, grad_scores, n_distinct,

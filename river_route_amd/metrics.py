@@ -19,6 +19,11 @@ KGE then returns a finite number.
 Gauge records with gaps: every function, `scores` and `Accumulator` take skip_missing=False.  With True a NaN in y_true marks a
 missing observation and that pair is left out (1-D on the host: dropped before the reference's numpy calls; per column on the
 GPU: rr_metrics_update_missing_dev), each column scored over its own kept pairs, whose number `scores` returns as 'count'.
+
+Ensembles: `scores_members` and `MemberAccumulator` score the (members, T, m) rows of a generation of members against one shared
+(T, n) observation block, or one per member, in one launch per update (rr_metrics_update_members_dev): member m's scores are those
+`scores` gives for member m alone.  Plan.rapid_route_members_scores routes and scores a parameter ensemble without the discharge
+leaving the device.
 """
 from __future__ import annotations
 
@@ -27,7 +32,7 @@ import sys
 import numpy as np
 
 __all__ = ['mean_error', 'mean_absolute_error', 'mean_square_error', 'pearson_r', 'kling_gupta_efficiency_2012',
-           'me', 'mae', 'mse', 'kge2012', 'scores', 'Accumulator', 'SCORES']
+           'me', 'mae', 'mse', 'kge2012', 'scores', 'Accumulator', 'scores_members', 'MemberAccumulator', 'SCORES']
 
 SCORES = ('me', 'mae', 'mse', 'pearson_r', 'kge2012')       # the rows of rr_metrics_finish_dev's out[5][n]
 _UNUSED = object()      # Accumulator._stream before the first launch
@@ -299,3 +304,187 @@ class _Rows:
     @property
     def address(self) -> int:
         return int(self.tensor.data_ptr()) if self.tensor is not None else int(self.uploaded.address)
+
+
+def scores_members(y_true, y_pred, columns=None, skip_missing=False) -> dict:
+    """`scores` for every member of an ensemble from one read: y_pred is (members, T, m); y_true is (T, n), one observation block
+    that all members are scored against, or (members, T, n).  Returns {'me', 'mae', 'mse', 'pearson_r', 'kge2012'[, 'count']} ->
+    (members, n) arrays (numpy in: numpy out; torch in: device tensors out), row m what `scores` gives for member m alone -- bit
+    for bit wherever members x ceil(n / 256) x ceil(T / 32) <= 2048 (both then cut the rows alike), within 1e-12 relative otherwise.
+    columns (one map for all members) and skip_missing are those of `scores`."""
+    t, p = _MemberRows(y_true, 'y_true', shared_ok=True), _MemberRows(y_pred, 'y_pred')
+    columns = _member_columns(columns, t.cols)
+    _check_member_rows(t.cols, p.members, columns, None, t, p)
+    device = t.device if t.device is not None else (p.device if p.device is not None else 0)
+    acc = MemberAccumulator(t.cols, p.members, columns=columns, device=device, skip_missing=skip_missing)
+    acc._update(t, p)
+    return acc.result()
+
+
+def _member_columns(columns, n: int):
+    """columns= as an int32 array of length n (None stays None), checked on the host."""
+    if columns is None:
+        return None
+    cols = np.asarray(columns.detach().cpu() if _torch_tensor(columns) else columns)
+    if cols.shape != (n,) or not np.issubdtype(cols.dtype, np.integer):
+        raise ValueError(f'columns must be a 1-D integer array of length {n}')
+    if cols.size and (cols.min() < 0 or cols.max() > np.iinfo(np.int32).max):
+        raise ValueError('columns holds a negative or too large column index')
+    return cols.astype(np.int32)
+
+
+def _check_member_rows(n, members, columns, device, t: '_MemberRows', p: '_MemberRows') -> None:
+    """Every shape rule of one members update, on the host (device None: any)."""
+    if p.members != members:
+        raise ValueError(f'predicted rows have {p.members} members, expected {members}')
+    if t.members is not None and t.members != members:
+        raise ValueError(f'true rows have {t.members} members, predicted rows {members} (or pass one 2-D block for all)')
+    if t.cols != n:
+        raise ValueError(f'true rows have {t.cols} columns, expected {n}')
+    if t.rows != p.rows:
+        raise ValueError(f'true rows ({t.rows}) and predicted rows ({p.rows}) differ in number')
+    if columns is None and p.cols != n:
+        raise ValueError(f'predicted rows have {p.cols} columns, expected {n} (or pass columns=)')
+    if columns is not None and columns.size and columns.max() >= p.cols:
+        raise ValueError(f'columns refers to column {int(columns.max())} of predicted rows with {p.cols} columns')
+    for r in (t, p):
+        if r.device is not None and device is not None and r.device != device:
+            raise ValueError(f'rows on device {r.device}, accumulator on device {device}')
+    if t.device is not None and p.device is not None and t.device != p.device:
+        raise ValueError(f'true rows on device {t.device}, predicted rows on device {p.device}')
+
+
+class MemberAccumulator:
+    """`Accumulator` for the members of an ensemble: `update(true_rows, pred_rows)` merges a (members, k, m) block of predicted rows
+    and its observations -- (k, n), shared by all members, or (members, k, n) -- into a per-member, per-column state kept on the GPU,
+    one launch for all members; `result()` returns the scores of all rows so far, each (members, n).  numpy / torch in and out,
+    streams, the reuse of the work slab, row blocks (1e-12 relative against one pass; the same blocks give the same bits) and
+    skip_missing are `Accumulator`'s.  Torch tensors are read in place when their columns are adjacent and neither their rows nor
+    their members overlap (any row and member stride from there up); other views are copied first."""
+
+    def __init__(self, n: int, members: int, columns=None, device: int = 0, skip_missing: bool = False):
+        from . import engine
+        self._engine = engine
+        self.n, self.members, self.device, self.rows = int(n), int(members), int(device), 0
+        self.skip_missing = bool(skip_missing)
+        if self.n < 1 or self.members < 1:
+            raise ValueError('MemberAccumulator needs n >= 1 columns and members >= 1')
+        if self.n * self.members > np.iinfo(np.int32).max:
+            raise ValueError('MemberAccumulator: members * n must stay below 2^31')
+        self._columns, self._cols_dev = _member_columns(columns, self.n), None
+        if self._columns is not None:
+            self._cols_dev = engine.DeviceBuffer(self._columns.nbytes, self.device).upload(self._columns)
+        self._state = engine.DeviceBuffer(engine.METRICS_STATE * self.members * self.n * 8, self.device)
+        self._state.upload(np.zeros(engine.METRICS_STATE * self.members * self.n))
+        self._work, self._stream, self._torch = None, _UNUSED, False
+
+    def update(self, true_rows, pred_rows) -> 'MemberAccumulator':
+        self._update(_MemberRows(true_rows, 'true_rows', shared_ok=True), _MemberRows(pred_rows, 'pred_rows'))
+        return self
+
+    def _update(self, t: '_MemberRows', p: '_MemberRows') -> None:
+        _check_member_rows(self.n, self.members, self._columns, self.device, t, p)
+        if t.rows == 0:
+            return
+        stream = None
+        if t.tensor is not None or p.tensor is not None:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._torch = True
+        self._enter_stream(stream)
+        t.to_device(self.device)
+        p.to_device(self.device)
+        self._launch(t.rows, t.address, t.is_f32, t.pitch, t.member_pitch, p.address, p.is_f32, p.pitch, p.member_pitch, stream)
+        if t.uploaded is not None or p.uploaded is not None:
+            self._engine.synchronize(self.device)            # the uploaded copies are freed on return
+
+    def _launch(self, rows, y_true, true_is_f32, true_pitch, true_member_pitch, y_pred, pred_is_f32, pred_pitch, pred_member_pitch, stream) -> None:
+        """One rr_metrics_update_members_dev of device rows at raw addresses, on `stream` (entered by the caller)."""
+        e = self._engine
+        need = e.metrics_members_work_bytes(self.n, self.members, rows)
+        if self._work is None or self._work.nbytes < need:
+            if self._work is not None:
+                self._work.free()
+            self._work = e.DeviceBuffer(need, self.device)
+        e.metrics_update_members_dev(self.n, self.members, rows, y_true, true_is_f32, true_pitch, true_member_pitch, y_pred, pred_is_f32,
+                                     pred_pitch, pred_member_pitch, self._cols_dev, self.skip_missing, self._state, self._work,
+                                     self._work.nbytes, device=self.device, stream=stream)
+        self.rows += rows
+
+    _enter_stream = Accumulator._enter_stream
+
+    def result(self) -> dict:
+        """{'me', 'mae', 'mse', 'pearson_r', 'kge2012'} -> (members, n) scores of every row so far: device tensors if any update came
+        as torch tensors, else numpy arrays.  With skip_missing also 'count', the pairs kept per member and column."""
+        e, total, shape = self._engine, self.members * self.n, (self.members, self.n)
+        if self._torch:
+            import torch
+            stream = torch.cuda.current_stream(self.device).cuda_stream
+            self._enter_stream(stream)
+            out = torch.empty((len(SCORES),) + shape, dtype=torch.float64, device=torch.device('cuda', self.device))
+            e.metrics_finish_dev(total, self._state, out.data_ptr(), device=self.device, stream=stream)
+            if self.skip_missing:
+                # row 0 of the state, copied on the stream the finish was enqueued on
+                count = torch.as_tensor(_DeviceDoubles(self._state.address, total), device=out.device).clone().reshape(shape)
+        else:
+            self._enter_stream(None)
+            buf = e.DeviceBuffer(len(SCORES) * total * 8, self.device)
+            e.metrics_finish_dev(total, self._state, buf, device=self.device)
+            e.synchronize(self.device)
+            out = buf.download(np.float64, (len(SCORES),) + shape)
+            buf.free()
+            if self.skip_missing:
+                count = self._state.download(np.float64, shape)      # row 0 of the state
+        res = {k: out[i] for i, k in enumerate(SCORES)}
+        if self.skip_missing:
+            res['count'] = count
+        return res
+
+
+class _MemberRows:
+    """One input of a members update: (members, rows, cols) float32/float64 in device memory, rows `pitch` and members `member_pitch`
+    elements apart -- or, where shared_ok, one (rows, cols) block for all members (members None, member_pitch 0).  numpy arrays are
+    uploaded by to_device; torch tensors on the GPU are used in place where the kernel's addressing reads them as they are."""
+
+    def __init__(self, a, name: str, shared_ok: bool = False):
+        self.tensor, self.uploaded, self.device = None, None, None
+        dims = '2-D (time, column) or 3-D (member, time, column)' if shared_ok else '3-D (member, time, column)'
+        if _torch_tensor(a):
+            import torch
+            if a.device.type != 'cuda':
+                raise ValueError(f'{name}: torch tensor must be on the GPU (got {a.device})')
+            if a.dim() != 3 and not (shared_ok and a.dim() == 2):
+                raise ValueError(f'{name} must be {dims}')
+            if a.dtype not in (torch.float32, torch.float64):
+                a = a.to(torch.float64)
+            lead = a.dim() - 2
+            self.members = int(a.shape[0]) if lead else None
+            self.rows, self.cols = int(a.shape[lead]), int(a.shape[lead + 1])
+            # the kernel reads element (m, r, c) at m * member_pitch + r * pitch + c: columns that are not adjacent, rows that share
+            # elements and members that share elements (broadcast or overlapping views) are copied into whole blocks first
+            pitch = int(a.stride(lead)) if self.rows > 1 else self.cols
+            span = (self.rows - 1) * pitch + self.cols
+            if ((self.cols > 1 and a.stride(lead + 1) != 1) or pitch < self.cols
+                    or (lead and self.members > 1 and a.stride(0) < span)):
+                a = a.contiguous()
+                pitch = self.cols
+                span = self.rows * self.cols
+            self.tensor, self.device = a, a.device.index or 0
+            self.is_f32 = a.dtype == torch.float32
+            self.pitch = pitch
+            self.member_pitch = 0 if not lead else (int(a.stride(0)) if self.members > 1 else span)
+        else:
+            a = np.asarray(a)
+            if a.ndim != 3 and not (shared_ok and a.ndim == 2):
+                raise ValueError(f'{name} must be {dims}')
+            if a.dtype not in (np.float32, np.float64):
+                a = a.astype(np.float64)
+            self.host = np.ascontiguousarray(a)
+            self.members = int(a.shape[0]) if a.ndim == 3 else None
+            self.rows, self.cols = int(a.shape[-2]), int(a.shape[-1])
+            self.is_f32 = a.dtype == np.float32
+            self.pitch = self.cols
+            self.member_pitch = self.rows * self.cols if a.ndim == 3 else 0
+
+    to_device = _Rows.to_device
+    address = _Rows.address
