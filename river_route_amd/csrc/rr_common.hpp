@@ -89,6 +89,19 @@ __device__ __forceinline__ float f32_from_file(float raw, uint32_t sel)
 }
 __device__ __forceinline__ float f32_to_file(float v, uint32_t sel) { return f32_from_file(v, sel); }
 
+// A global load / store with a compile-time cache hint: NT = non-temporal (the `nt` bit: the line is marked for early eviction), else
+// the default policy.  The per-stream policies are kRecStreams (rr_kernels_rec.hpp) and kTileStreams (rr_kernels_tile.hpp).
+template <bool NT, typename T> __device__ __forceinline__ T stream_load(const T *p)
+{
+    if constexpr (NT) return __builtin_nontemporal_load(p);
+    else return *p;
+}
+template <bool NT, typename T> __device__ __forceinline__ void stream_store(T *p, T v)
+{
+    if constexpr (NT) __builtin_nontemporal_store(v, p);
+    else *p = v;
+}
+
 inline dim3 grid1(int64_t n) { return dim3((unsigned)((n + kBlock - 1) / kBlock)); }
 
 // Workgroups are handed to the eight XCDs in turn (blockIdx % 8 labels the workgroups that share an XCD and its L2, cdna

@@ -46,17 +46,7 @@ struct RecStreamPolicy {
     bool out_rows;      // k_rec_out: params-order rows (float64 or float32 means), stored
 };
 constexpr RecStreamPolicy kRecStreamsDefault{false, false, false, false};
-constexpr RecStreamPolicy kRecStreams{false, true, true, false};
-template <bool NT, typename T> __device__ __forceinline__ T stream_load(const T *p)
-{
-    if constexpr (NT) return __builtin_nontemporal_load(p);
-    else return *p;
-}
-template <bool NT, typename T> __device__ __forceinline__ void stream_store(T *p, T v)
-{
-    if constexpr (NT) __builtin_nontemporal_store(v, p);
-    else *p = v;
-}
+constexpr RecStreamPolicy kRecStreams{false, true, true, false};      // (stream_load / stream_store: rr_common.hpp)
 
 struct RecPermArgs {
     double *rec;

@@ -85,19 +85,50 @@ __device__ __forceinline__ void store_f64(__amdgpu_buffer_rsrc_t r, uint32_t byt
     __builtin_memcpy(&bits, &v, sizeof bits);
     __builtin_amdgcn_raw_buffer_store_b64(bits, r, (int)byte_off, 0, 0);
 }
-__device__ __forceinline__ void store_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, double2 v)
+// NT: the access carries the `nt` bit (the last argument of the raw-buffer intrinsics: 2 = nt; 1 would be sc0, 16 sc1) -- see kTileStreams.
+constexpr int kAuxDefault = 0, kAuxNt = 2;
+template <bool NT = false> __device__ __forceinline__ void store_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, double2 v)
 {
     u32x4 bits;
     __builtin_memcpy(&bits, &v, sizeof bits);
-    __builtin_amdgcn_raw_buffer_store_b128(bits, r, (int)byte_off, 0, 0);
+    __builtin_amdgcn_raw_buffer_store_b128(bits, r, (int)byte_off, 0, NT ? kAuxNt : kAuxDefault);
 }
-__device__ __forceinline__ void load_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, double &x, double &y)
+template <bool NT = false> __device__ __forceinline__ u32x4 load_b128(__amdgpu_buffer_rsrc_t r, uint32_t byte_off)
 {
-    const u32x4 bits = __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, 0);   // one 16-byte request per lane
+    return __builtin_amdgcn_raw_buffer_load_b128(r, (int)byte_off, 0, NT ? kAuxNt : kAuxDefault);   // one 16-byte request per lane
+}
+template <bool NT = false> __device__ __forceinline__ void load_f64x2(__amdgpu_buffer_rsrc_t r, uint32_t byte_off, double &x, double &y)
+{
+    const u32x4 bits = load_b128<NT>(r, byte_off);
     double2 v;
     __builtin_memcpy(&v, &bits, sizeof v);
     x = v.x; y = v.y;
 }
+
+// Cache policy of k_tile's access streams, one hint per stream, as kRecStreams is for the record passes (rr_kernels_rec.hpp):
+// true = non-temporal (the `nt` bit of the buffer / global instruction: the line is marked for early eviction), false = the default
+// policy.  A hint changes the instruction's cache bits only: no load or store is added, removed, reordered or put behind a branch,
+// the explicit wait in front of the first receive() and the register figures stay (profiles/r09_tile_stream_ab.txt: the assembly
+// of every form against the parent's).
+// Two kinds of access have no entry and keep the default policy.  The copy of a record into the slot of the GHOST that mirrors the
+// reach (the second store of store_record; with sub-steps the 8-byte store per tick) is read by another tile one launch later: it
+// should still be in a cache then.  The position, coefficient and TileMeta tables are read again by every launch, and by every
+// member of an ensemble.  The export series (a.exports) is left alone.
+// Measured at 1M reaches, each hint alone and together (profiles/r09_tile_stream_ab.txt), k_tile per year against
+// the parent's 94.2 ms / the year against 262.3 ms, eight builds alternating:
+//   rec_loads   k_tile 97.1 ms, the year +1.2 ms: alone it costs;
+//   rec_stores  k_tile 92.1 ms, the year -2.3 ms;
+//   state       k_tile 93.0 ms, the year -1.9 ms: inside the spread;
+//   rec_loads + rec_stores  k_tile 83.2 ms, the year -13.4 ms (a second session: 93.5 -> 82.8 ms, the year 256.4 -> 248.3, bar 7.5): kept.
+//   All three: k_tile 83.7 ms, the year -13.5 ms: the state's hint adds nothing, the state keeps the default.  rec_loads + state 95.6 ms,
+//   rec_stores + state 91.4 ms.  The counters do not move (310.6 GB read, 160.6 GB written a year): the same bytes at 5.70 instead of
+//   5.04 TB/s.  No other line is slower (rapid_f32, unit, 100k reaches, the skeleton's launches, a 4,096-row sink), so no form is exempt.
+struct TileStreamPolicy {
+    bool rec_loads;     // the record loads of issue_load / issue_load_plain: k_tile uses a record's line once
+    bool rec_stores;    // the first store of store_record, the line a tile owns: next read by k_rec_out, several launches on
+    bool state;         // sq, ss, si, sqch: loaded in load_state, stored at the end of a task, next used one launch later
+};
+constexpr TileStreamPolicy kTileStreams{true, true, false};
 
 // The tick loops are fully unrolled (the record slots are registers), so anything derived from a per-position constant
 // is "loop invariant" and hipcc keeps every such derivative in a VGPR for the whole task.  fresh() hands the constant
@@ -193,7 +224,7 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
     auto issue_load = [&](__amdgpu_buffer_rsrc_t src, int32_t b0, int32_t b1, int j, bool real) {
         const int32_t t = fresh(tid), ln = t & 63;      // addresses are rebuilt at every use, not kept in registers across the task
         const int32_t pos = min(b0 + (t - ln) + 8 * j + (ln >> 3), b1 - 1);
-        load_f64x2(src, real ? (uint32_t)pos * kPosBytes + (uint32_t)((ln & 7) * 16) : kDropAccess, N[2 * j], N[2 * j + 1]);
+        load_f64x2<kTileStreams.rec_loads>(src, real ? (uint32_t)pos * kPosBytes + (uint32_t)((ln & 7) * 16) : kDropAccess, N[2 * j], N[2 * j + 1]);
     };
     auto receive = [&]() {
         const int32_t tl = fresh(tid), lane = tl & 63;
@@ -227,11 +258,11 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
             const int32_t first_up = pm.y - t.b0;
             s.lg = pm.x; s.up = first_up | (int32_t)((cc & 0xFFFFu) << 16);
             s.xp = pm.z;
-            if (UNIT) { s.uh = first_up + (int32_t)(cc >> 16); s.qch = a.sqch[p]; }
-            if (SUB) s.isum = a.si[ENS ? p + member_pos0(a) : p];
-            s.s_prev = a.ss[ENS ? p + member_pos0(a) : p];
+            if (UNIT) { s.uh = first_up + (int32_t)(cc >> 16); s.qch = stream_load<kTileStreams.state>(a.sqch + p); }
+            if (SUB) s.isum = stream_load<kTileStreams.state>(a.si + (ENS ? p + member_pos0(a) : p));
+            s.s_prev = stream_load<kTileStreams.state>(a.ss + (ENS ? p + member_pos0(a) : p));
             const double *coef = MCOEF ? a.coef + 3 * (int64_t)member_pos0(a) : a.coef;      // (uniform: scalar registers)
-            s.q = a.sq[ENS ? p + member_pos0(a) : p]; s.c1 = coef[3 * (int64_t)p]; s.c2 = coef[3 * (int64_t)p + 1]; s.c3 = coef[3 * (int64_t)p + 2];
+            s.q = stream_load<kTileStreams.state>(a.sq + (ENS ? p + member_pos0(a) : p)); s.c1 = coef[3 * (int64_t)p]; s.c2 = coef[3 * (int64_t)p + 1]; s.c3 = coef[3 * (int64_t)p + 2];
         }
     };
     // The first tile: state and coefficients are requested BEFORE the record: memory operations retire in order, so the
@@ -300,7 +331,7 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
                     const double2 *theirs = reinterpret_cast<const double2 *>(stage + pm * kStageStrideOut);
                     const double2 v = theirs[piece];
                     const bool skip = reinterpret_cast<const int32_t *>(theirs + 8)[0] != 0;
-                    store_f64x2(dst, skip ? kDropAccess : first + (uint32_t)pm * kPosBytes + (uint32_t)piece * 16u, v);
+                    store_f64x2<kTileStreams.rec_stores>(dst, skip ? kDropAccess : first + (uint32_t)pm * kPosBytes + (uint32_t)piece * 16u, v);
                     if (!SUB) {     // the same line into the record of the ghost that mirrors the reach (always issued, see store_f64)
                         const int32_t gx = reinterpret_cast<const int32_t *>(theirs + 8)[1];
                         store_f64x2(dst, gx < 0 ? kDropAccess : (uint32_t)gx * kPosBytes + (uint32_t)piece * 16u, v);
@@ -392,7 +423,7 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
         auto issue_load_plain = [&](__amdgpu_buffer_rsrc_t src, uint32_t voff, int j) {
             // the piece's offset is part of the per-lane offset (a compile-time constant per unrolled load, folded into the
             // instruction's immediate where it fits): the range check of a raw buffer covers that sum, not a scalar offset
-            const u32x4 bits = __builtin_amdgcn_raw_buffer_load_b128(src, (int)(voff + (uint32_t)j * 8u * kPosBytes), 0, 0);
+            const u32x4 bits = load_b128<kTileStreams.rec_loads>(src, voff + (uint32_t)j * 8u * kPosBytes);
             double2 v;
             __builtin_memcpy(&v, &bits, sizeof v);
             N[2 * j] = v.x; N[2 * j + 1] = v.y;
@@ -496,9 +527,11 @@ __global__ __launch_bounds__(TH, 4) void k_tile(const TileArgs a)      // 16 wav
         if ((LEAN ? the_lg() : lg) >= 0) {
             const int32_t p = b0 + tid;
             const double *aux = lds + 2 * THP + (TH / 64) * (kStageLanes * kStageStrideOut);
-            a.sq[ENS ? p + member_pos0(a) : p] = lds[(size_t)((tau_begin + K - 1) & 1) * THP + tid]; a.ss[ENS ? p + member_pos0(a) : p] = (LEAN && UNIT) ? aux[4 * TH + tid] : s_prev;
-            if (UNIT) a.sqch[p] = (LEAN && UNIT) ? aux[3 * TH + tid] : qch;
-            if (SUB) a.si[ENS ? p + member_pos0(a) : p] = isum;
+            constexpr bool kNt = kTileStreams.state;
+            stream_store<kNt>(a.sq + (ENS ? p + member_pos0(a) : p), lds[(size_t)((tau_begin + K - 1) & 1) * THP + tid]);
+            stream_store<kNt>(a.ss + (ENS ? p + member_pos0(a) : p), (LEAN && UNIT) ? aux[4 * TH + tid] : s_prev);
+            if (UNIT) stream_store<kNt>(a.sqch + p, (LEAN && UNIT) ? aux[3 * TH + tid] : qch);
+            if (SUB) stream_store<kNt>(a.si + (ENS ? p + member_pos0(a) : p), isum);
         }
         if (LEAN && has_next) load_state(nxt, st);
         if (!has_next) break;
