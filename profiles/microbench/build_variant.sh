@@ -6,5 +6,6 @@ set -e
 name=$1; shift
 mkdir -p gpurun_variants
 /opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -pthread -Wno-unused-result "$@" \
+    river_route_amd/csrc/rr_scores.hip \
     river_route_amd/csrc/rr_plan.cpp river_route_amd/csrc/rr_engine.hip -o gpurun_variants/librr_$name.so
 echo built gpurun_variants/librr_$name.so "$@"

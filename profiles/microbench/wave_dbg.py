@@ -1,6 +1,7 @@
 """Per-tile phase breakdown of one k_tile launch from the timestamps a -DRR_WAVE_TRACE build writes (development aid).
 
     hipcc --offload-arch=gfx950 -O3 -std=c++17 -fPIC -shared -DRR_WAVE_TRACE river_route_amd/csrc/rr_plan.cpp \
+        river_route_amd/csrc/rr_scores.hip \
         river_route_amd/csrc/rr_engine.hip -o /tmp/librr_trace.so
     RR_LIB_PATH=/tmp/librr_trace.so RR_WAVE_TRACE_DIAG=300 RR_WAVE_TRACE_FILE=/tmp/t.txt python bench.py --steps 1 --warmup 0 --no-cpu-baseline
     python profiles/microbench/wave_dbg.py /tmp/t.txt

@@ -14,7 +14,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('RR_LIB_PATH') or os.path.join(_HERE, 'librr_hip.so')      # RR_LIB_PATH: a development build
 CSRC = os.path.join(_HERE, 'csrc')
-SOURCES = ('rr_plan.cpp', 'rr_engine.hip')
+SOURCES = ('rr_plan.cpp', 'rr_engine.hip', 'rr_scores.hip')
 
 RR_OK = 0
 RR_E_INVALID, RR_E_NOT_TOPOLOGICAL, RR_E_HIP, RR_E_NO_DEVICE, RR_E_STATE, RR_E_ALLOC, RR_E_UNSUPPORTED = \
@@ -41,8 +41,10 @@ def sanitizer_runtime() -> str | None:
 
 def build(force: bool = False, verbose: bool = False, sanitize: bool = False) -> str:
     """Compile librr_hip.so for gfx950 with hipcc (cross-compiles without a GPU). Returns the path.
-    sanitize: the HOST code (network analysis, tile / direct planners, partitioner, executor: rr_plan.cpp and the host half of
-    rr_engine.hip) under AddressSanitizer + UndefinedBehaviorSanitizer into librr_hip_asan.so -- device code is compiled as usual
+    One hipcc command over SOURCES: rr_plan.cpp (host only) and the two device translation units, rr_engine.hip (routing) and
+    rr_scores.hip (skill scores, overlap areas), each with a code object of its own (no -fgpu-rdc).
+    sanitize: the HOST code (network analysis, tile / direct planners, partitioner, executor: rr_plan.cpp and the host halves of
+    the two .hip files) under AddressSanitizer + UndefinedBehaviorSanitizer into librr_hip_asan.so -- device code is compiled as usual
     (-fno-gpu-sanitize: no GPU sanitizer on this pool).  tests/test_sanitize.py runs the host-only planner tests against it."""
     srcs = [os.path.join(CSRC, s) for s in SOURCES]
     deps = srcs + [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC)) if f.endswith('.hpp')] + [os.path.join(os.path.dirname(_HERE), 'include', 'rr_hip.h')]

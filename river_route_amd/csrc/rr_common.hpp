@@ -1,5 +1,5 @@
 // rr_common.hpp -- includes, error helper, constants and index helpers shared by the kernels and the executor.
-// Part of the one translation unit rr_engine.hip builds (included from there first).
+// Included first by both device translation units, rr_engine.hip and rr_scores.hip.
 #pragma once
 
 #include <hip/hip_runtime.h>
@@ -22,11 +22,14 @@
 
 #define RR_VERSION_NUM 230
 
+// The one error string of the library, per thread (rr_last_error): set `msg`, return `code`.  Defined once, in rr_engine.hip
+// beside rr_last_error; external but not part of the C ABI, as rr::dev_mem_alloc (rr_devbuf.hpp).
+namespace rr {
+int fail(int code, const std::string &msg);
+}
+using rr::fail;
+
 namespace {
-
-thread_local std::string g_err;
-
-int fail(int code, const std::string &msg) { g_err = msg; return code; }
 
 #define HIPCHK(expr)                                                                                   \
     do {                                                                                               \

@@ -1,5 +1,5 @@
 // rr_kernels_metrics.hpp -- per-column skill scores (river_route/metrics.py) of (time, reach) rows already on the device.
-// Part of the one translation unit rr_engine.hip builds (included from there, in order; not a stand-alone header).
+// Part of the translation unit rr_scores.hip builds (included from there, after rr_common.hpp; not a stand-alone header).
 #pragma once
 
 namespace {
@@ -57,26 +57,61 @@ __device__ __forceinline__ void mstat_merge(MStat &a, const MStat &b)
     a.sd2 += b.sd2;
 }
 
-// Partial states of one launch: workgroup (x, y) takes columns [256 x, 256 x + 256) over rows [y R, y R + R) and writes
-// its state to slab[y][field][n].  Lane j reads y_true[r, j] and y_pred[r, col[j]]: along a row, so the true rows (and
-// the predicted rows without a column map) are read coalesced.  Every element is widened to double on load.
-template <typename TT, typename TP>
-__global__ __launch_bounds__(kBlock) void k_metrics_partial(const TT *__restrict__ yt, int64_t tpitch, const TP *__restrict__ yp,
-                                                            int64_t ppitch, const int32_t *__restrict__ cols, int64_t n, int64_t rows,
-                                                            int64_t rows_per_split, double *__restrict__ slab)
+// The shifted sums of one chunk -> its state: cnt pairs, (mean, M2, C) with one divide (inv = 1 / cnt, or 0 for no pair: the
+// all-zero empty state).  Rounding can leave an M2 a hair below zero (NaN stays NaN).
+__device__ __forceinline__ MStat mstat_of_chunk(double cnt, double inv, double kt, double kp, double st, double sp, double stt, double spp,
+                                                double stp, double sd, double sad, double sd2)
 {
-    const int64_t j = (int64_t)blockIdx.x * kBlock + threadIdx.x;
-    if (j >= n) return;
-    const int64_t r0 = (int64_t)blockIdx.y * rows_per_split, r1 = min(rows, r0 + rows_per_split);
-    const TT *pt = yt + r0 * tpitch + j;
-    const TP *pp = yp + r0 * ppitch + (cols ? (int64_t)cols[j] : j);
+    MStat b;
+    b.cnt = cnt;
+    b.mt = kt + st * inv;
+    b.mp = kp + sp * inv;
+    b.m2t = fma(-st * inv, st, stt);
+    b.m2p = fma(-sp * inv, sp, spp);
+    b.c = fma(-st * inv, sp, stp);
+    if (b.m2t < 0.0) b.m2t = 0.0;
+    if (b.m2p < 0.0) b.m2p = 0.0;
+    b.sd = sd;
+    b.sad = sad;
+    b.sd2 = sd2;
+    return b;
+}
+
+// The state of rows [r0, r1) of one lane's column, pt and pp at its elements of row r0: the one row loop of the scores.  Every
+// element is widened to double on load.  The chunk's first row is the pivot of its shifted sums.
+// MISSING (gauge records with gaps, DESIGN.md section 9 "Missing observations"): element (r, j) is missing when y_true[r, j] is NaN,
+// and the pair is then left out of the column's sums.  Every load is issued whether the pair is kept or not (the bytes moved are the
+// unmasked loop's) and the validity flag drives selects, never a branch: the lanes of a wave have different gaps.  A skipped pair
+// adds 0 to every shifted sum and to the count, and its y_pred is never looked at.  The pivot is the chunk's first KEPT pair: any
+// kept value would do, the first makes a gap-free column repeat the unmasked sums operation by operation, and a NaN is never a
+// pivot.  A chunk that keeps nothing gives the all-zero empty state, which mstat_merge skips.
+template <bool MISSING, typename TT, typename TP>
+__device__ __forceinline__ MStat mstat_rows(const TT *__restrict__ pt, int64_t tpitch, const TP *__restrict__ pp, int64_t ppitch, int64_t r0,
+                                            int64_t r1)
+{
     MStat s = {0, 0, 0, 0, 0, 0, 0, 0, 0};
     for (int64_t r = r0; r < r1; r += kMetricsChunk) {
         const int m = (int)min((int64_t)kMetricsChunk, r1 - r);
-        const double kt = (double)pt[0], kp = (double)pp[0];
+        double kt = 0, kp = 0;      // the pivot: the first row (MISSING: the first kept pair, once `kept` is not 0)
+        int kept = 0;
+        if constexpr (!MISSING) {
+            kt = (double)pt[0];
+            kp = (double)pp[0];
+        }
         double st = 0, sp = 0, stt = 0, spp = 0, stp = 0, sd = 0, sad = 0, sd2 = 0;
-        auto body = [&](double t, double p) {
-            const double a = t - kt, b = p - kp, d = t - p;
+        auto body = [&](TT xt, TP xp) {
+            const double t = (double)xt, p = (double)xp;
+            double a, b, d;
+            if constexpr (MISSING) {
+                const bool ok = xt == xt;      // the element as stored; inf is kept
+                const bool first = ok && kept == 0;
+                kt = first ? t : kt;
+                kp = first ? p : kp;
+                kept += ok ? 1 : 0;
+                a = ok ? t - kt : 0.0, b = ok ? p - kp : 0.0, d = ok ? t - p : 0.0;
+            } else {
+                a = t - kt, b = p - kp, d = t - p;
+            }
             st += a;
             sp += b;
             stt = fma(a, a, stt);
@@ -97,30 +132,43 @@ __global__ __launch_bounds__(kBlock) void k_metrics_partial(const TT *__restrict
                     xp[i] = pp[(i0 + i) * ppitch];
                 }
 #pragma unroll
-                for (int i = 0; i < kMetricsBatch; ++i) body((double)xt[i], (double)xp[i]);
+                for (int i = 0; i < kMetricsBatch; ++i) body(xt[i], xp[i]);
             }
         } else {
-            for (int i = 0; i < m; ++i) body((double)pt[i * tpitch], (double)pp[i * ppitch]);
+            for (int i = 0; i < m; ++i) body(pt[i * tpitch], pp[i * ppitch]);
         }
         pt += m * tpitch;
         pp += m * ppitch;
-        // shifted sums -> (mean, M2, C) of the chunk; rounding can leave an M2 a hair below zero (NaN stays NaN)
-        const double inv = m == kMetricsChunk ? 1.0 / kMetricsChunk : 1.0 / m;
-        MStat b;
-        b.cnt = m;
-        b.mt = kt + st * inv;
-        b.mp = kp + sp * inv;
-        b.m2t = fma(-st * inv, st, stt);
-        b.m2p = fma(-sp * inv, sp, spp);
-        b.c = fma(-st * inv, sp, stp);
-        if (b.m2t < 0.0) b.m2t = 0.0;
-        if (b.m2p < 0.0) b.m2p = 0.0;
-        b.sd = sd;
-        b.sad = sad;
-        b.sd2 = sd2;
-        mstat_merge(s, b);
+        if constexpr (MISSING)
+            mstat_merge(s, mstat_of_chunk(kept, kept > 0 ? 1.0 / kept : 0.0, kt, kp, st, sp, stt, spp, stp, sd, sad, sd2));
+        else
+            mstat_merge(s, mstat_of_chunk(m, m == kMetricsChunk ? 1.0 / kMetricsChunk : 1.0 / m, kt, kp, st, sp, stt, spp, stp, sd, sad, sd2));
     }
-    mstat_store(s, slab + (int64_t)blockIdx.y * RR_METRICS_STATE * n, n, j);
+    return s;
+}
+
+// Partial states of one launch, for the members of an ensemble (one member: a single series).  Workgroup x
+// takes columns [256 cb, 256 cb + 256) of member m, x = m * col_blocks + cb, over rows [y R, y R + R), and writes its states to
+// slab[y][field][m * n + j].  Member m's rows of y_pred lie m * pmpitch elements after member 0's, its observations m * tmpitch
+// after member 0's (pitch 0: one observation block for all members, which comes from L2 / MALL after the first member has read it).
+// A workgroup never spans two members, so the member and both member offsets (formed in 64 bits) are uniform over it; the column map
+// is one for all members.  Lane j reads y_true[r, j] and y_pred[r, col[j]]: along a row, so the true rows (and the predicted rows
+// without a column map) are read coalesced.  The state is the single-series state over the flattened index f = m * n + j, so
+// k_metrics_merge and k_metrics_finish work on it with members * n as their column count.
+template <bool MISSING, typename TT, typename TP>
+__global__ __launch_bounds__(kBlock) void k_metrics_partial(const TT *__restrict__ yt, int64_t tpitch, int64_t tmpitch,
+                                                            const TP *__restrict__ yp, int64_t ppitch, int64_t pmpitch,
+                                                            const int32_t *__restrict__ cols, int64_t n, int64_t col_blocks, int64_t members,
+                                                            int64_t rows, int64_t rows_per_split, double *__restrict__ slab)
+{
+    const int64_t m = (int64_t)blockIdx.x / col_blocks, cb = (int64_t)blockIdx.x - m * col_blocks;
+    const int64_t j = cb * kBlock + threadIdx.x;
+    if (j >= n) return;
+    const int64_t r0 = (int64_t)blockIdx.y * rows_per_split, r1 = min(rows, r0 + rows_per_split);
+    const TT *pt = yt + m * tmpitch + r0 * tpitch + j;
+    const TP *pp = yp + m * pmpitch + r0 * ppitch + (cols ? (int64_t)cols[j] : j);
+    const MStat s = mstat_rows<MISSING>(pt, tpitch, pp, ppitch, r0, r1);
+    mstat_store(s, slab + ((int64_t)blockIdx.y * RR_METRICS_STATE * members + m) * n, members * n, j);
 }
 
 // state[j] <- state[j] merged with the slab's partial states, folded in split order: the result depends on the inputs
@@ -173,7 +221,7 @@ __global__ __launch_bounds__(kBlock) void k_metrics_finish(const double *__restr
 
 // How an update of `rows` rows of n columns is cut: splits x rows_per_split, rows_per_split a whole number of chunks.
 // A function of (n, rows) only, so rr_metrics_work_bytes and the update agree and a repeated update repeats its sums.
-// members > 1 (rr_metrics_update_members_dev): one row range takes members x ceil(n / 256) workgroups, a function of (n, members, rows).
+// members > 1: one row range takes members x ceil(n / 256) workgroups, a function of (n, members, rows).
 inline void metrics_split(int64_t n, int64_t rows, int64_t &splits, int64_t &rows_per_split, int64_t members = 1)
 {
     const int64_t col_blocks = members * ((n + kBlock - 1) / kBlock);

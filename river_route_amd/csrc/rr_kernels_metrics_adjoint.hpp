@@ -1,6 +1,6 @@
 // rr_kernels_metrics_adjoint.hpp -- the gradient of a loss through the per-column skill scores of rr_kernels_metrics.hpp
 // (river_route/metrics.py) with respect to the simulated rows.
-// Part of the one translation unit rr_engine.hip builds (included from there, in order; not a stand-alone header).
+// Part of the translation unit rr_scores.hip builds (included from there, after rr_kernels_metrics.hpp; not a stand-alone header).
 #pragma once
 
 namespace {
@@ -22,12 +22,17 @@ __device__ __forceinline__ MAdjCoef madj_load(const double *__restrict__ c, int6
 }
 
 // One element's share: the centred form (an uncentred one cancels for series with a large offset); sign(0) = 0.
+// MISSING: exactly 0 where the observation is missing (NaN), whatever the column's constants are (NaN among them), hence a select
+// and not a multiply by the flag.
+template <bool MISSING>
 __device__ __forceinline__ double madj_term(const MAdjCoef &k, double t, double p)
 {
     const double d = t - p;
     double v = fma(k.B, t - k.mt, k.A);
     v = fma(k.P, p - k.mp, v);
-    return v + (d > 0.0 ? k.S : (d < 0.0 ? -k.S : 0.0));
+    v = v + (d > 0.0 ? k.S : (d < 0.0 ? -k.S : 0.0));
+    if constexpr (MISSING) return t == t ? v : 0.0;
+    else return v;
 }
 
 // State and the gradient of the five scores (g[5][n], the rows of k_metrics_finish's out) -> coef[6][n].  Every divide and square
@@ -95,7 +100,9 @@ __global__ __launch_bounds__(kBlock) void k_metrics_adjoint_coef(const double *_
 // atomics, and columns of y_pred nobody scores are never written.  The first share's constants stay in registers; those of a
 // repeated column are reloaded per batch of rows.  Per element: two loads, two subtractions (the centring), two FMAs, a sign select
 // with its add, and one store of y_pred's type; no divide.
-template <typename TT, typename TP>
+// MISSING (rr_kernels_metrics.hpp: mstat_rows): each share is masked by its own y_true element.  Every owned element is stored, a
+// skipped one as 0, so without a column map the caller's grad needs no zero fill.
+template <bool MISSING, typename TT, typename TP>
 __global__ __launch_bounds__(kBlock) void k_metrics_adjoint_rows(const TT *__restrict__ yt, int64_t tpitch, const TP *__restrict__ yp,
                                                                  int64_t ppitch, const double *__restrict__ coef, int64_t n,
                                                                  const int32_t *__restrict__ order, const int32_t *__restrict__ ucols,
@@ -123,13 +130,13 @@ __global__ __launch_bounds__(kBlock) void k_metrics_adjoint_rows(const TT *__res
         }
         double v[kMetricsAdjBatch];
 #pragma unroll
-        for (int i = 0; i < kMetricsAdjBatch; ++i) v[i] = madj_term(k0, (double)xt[i], (double)xp[i]);
+        for (int i = 0; i < kMetricsAdjBatch; ++i) v[i] = madj_term<MISSING>(k0, (double)xt[i], (double)xp[i]);
         for (int64_t s = s0 + 1; s < s1; ++s) {      // a column of y_pred scored more than once
             const int64_t j = order[s];
             const MAdjCoef k = madj_load(coef, n, j);
             const TT *qt = yt + r * tpitch + j;
 #pragma unroll
-            for (int i = 0; i < kMetricsAdjBatch; ++i) v[i] += madj_term(k, (double)qt[i * tpitch], (double)xp[i]);
+            for (int i = 0; i < kMetricsAdjBatch; ++i) v[i] += madj_term<MISSING>(k, (double)qt[i * tpitch], (double)xp[i]);
         }
 #pragma unroll
         for (int i = 0; i < kMetricsAdjBatch; ++i) pg[i * gpitch] = (TP)v[i];
@@ -139,10 +146,10 @@ __global__ __launch_bounds__(kBlock) void k_metrics_adjoint_rows(const TT *__res
     }
     for (; r < r1; ++r) {
         const double p = (double)pp[0];
-        double v = madj_term(k0, (double)pt[0], p);
+        double v = madj_term<MISSING>(k0, (double)pt[0], p);
         for (int64_t s = s0 + 1; s < s1; ++s) {
             const int64_t j = order[s];
-            v += madj_term(madj_load(coef, n, j), (double)yt[r * tpitch + j], p);
+            v += madj_term<MISSING>(madj_load(coef, n, j), (double)yt[r * tpitch + j], p);
         }
         pg[0] = (TP)v;
         pt += tpitch;

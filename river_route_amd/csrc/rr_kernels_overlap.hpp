@@ -1,6 +1,6 @@
 // rr_kernels_overlap.hpp -- area of catchment polygons clipped to the cells of a regular grid (river_route/runoff.py:70-116:
 // gpd.overlay of the grid's Voronoi cells with the catchments, then .to_crs({'proj': 'cea'}).area).
-// Part of the one translation unit rr_engine.hip builds (included from there, in order; not a stand-alone header).
+// Part of the translation unit rr_scores.hip builds (included from there, after rr_common.hpp; not a stand-alone header).
 #pragma once
 
 namespace {

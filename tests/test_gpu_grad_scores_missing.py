@@ -1,5 +1,5 @@
 """rr.grad.scores(..., skip_missing=True) on the GPU (rr_metrics_update_missing_dev forward, rr_metrics_adjoint_missing_dev backward:
-k_metrics_adjoint_coef as it is, then k_metrics_adjoint_rows_missing): the forward is rr.metrics.scores(..., skip_missing=True)
+k_metrics_adjoint_coef as it is, then k_metrics_adjoint_rows<MISSING>): the forward is rr.metrics.scores(..., skip_missing=True)
 bit for bit, 'count' included; dL/dy_pred agrees with torch autograd on the CPU through the masked float64 restatement
 (missing_helpers.dense_scores_missing: torch.where on the mask, N = mask.sum(0)) within the assert_grad of
 tests/test_gpu_grad_scores.py, and is exactly 0.0 at every skipped element.  Every shape carries the gap pattern of

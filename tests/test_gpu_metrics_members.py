@@ -1,4 +1,4 @@
-"""Scores of an ensemble's members on the GPU (k_metrics_partial_members through rr_metrics_update_members_dev, rr.metrics.scores_members,
+"""Scores of an ensemble's members on the GPU (k_metrics_partial with several members through rr_metrics_update_members_dev, rr.metrics.scores_members,
 rr.metrics.MemberAccumulator, Plan.rapid_route_members_scores): member m of a members call equals rr.metrics.scores on member m alone
 -- bit for bit wherever members x ceil(G / 256) x ceil(rows / 32) <= 2048, where both calls cut the rows into the same 32-row ranges,
 and within the project's row-split tolerance (rtol 1e-12) beyond -- for every dtype pairing, shared and per-member observations,

@@ -1,4 +1,4 @@
-"""rr.metrics.scores(..., skip_missing=True) on the GPU (k_metrics_partial_missing through rr_metrics_update_missing_dev; merge and
+"""rr.metrics.scores(..., skip_missing=True) on the GPU (k_metrics_partial<MISSING> through rr_metrics_update_missing_dev; merge and
 finish are the unmasked path's kernels): per-column scores over each column's kept pairs against numpy on those pairs (the host
 1-D path on the filtered float64 columns), by the rule of tests/test_gpu_metrics.py::check: equal NaN pattern, rtol 1e-10; 'count'
 exact.  Every shape carries the gap pattern of missing_helpers.gap_mask: 30 % at random, a gap-free column, whole chunks (at n = 7
