@@ -1,6 +1,7 @@
 """
 ctypes front-end of the CPU oracle (oracle/rr_oracle.c) and of its long-double restatement, the per-reach arbiter
-(oracle/rr_oracle_ld.c: the *_ld functions).
+(oracle/rr_oracle_ld.c: the *_ld functions), the adjoint arbiter (oracle/rr_oracle_adj.c) and the arbiter of the skill scores and their
+gradient (oracle/rr_oracle_scores.c: scores_ld, scores_grad_ld).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and bench.py's cpu_baseline leg.
 Nothing under river_route_amd/ may import this module.
@@ -35,8 +36,10 @@ _ERRORS = {
 def build(fast: bool = False, out_dir: str | None = None) -> str:
     """Compile the oracle with gcc if its shared object is missing or stale; returns the .so path."""
     name = 'librr_oracle_fast.so' if fast else 'librr_oracle.so'
-    # the parity checker holds the extended-precision arbiters too (rr_oracle_ld.c, rr_oracle_adj.c); the timed baseline is the fp64 loops alone
-    srcs = [os.path.join(_HERE, f) for f in (('rr_oracle.c',) if fast else ('rr_oracle.c', 'rr_oracle_ld.c', 'rr_oracle_adj.c'))]
+    # the parity checker holds the extended-precision arbiters too (rr_oracle_ld.c, rr_oracle_adj.c, rr_oracle_scores.c); the timed
+    # baseline is the fp64 loops alone
+    srcs = [os.path.join(_HERE, f) for f in (('rr_oracle.c',) if fast else ('rr_oracle.c', 'rr_oracle_ld.c', 'rr_oracle_adj.c',
+                                                                            'rr_oracle_scores.c'))]
     out = os.path.join(out_dir or _HERE, name)
     if os.path.exists(out) and os.path.getmtime(out) >= max(os.path.getmtime(src) for src in srcs):
         return out
@@ -68,6 +71,11 @@ def _bind(lib: C.CDLL) -> C.CDLL:
             getattr(lib, f).restype = C.c_int
     if hasattr(lib, 'orcl_rapid_adjoint'):    # the adjoint arbiter (rr_oracle_adj.c): in the parity checker only
         _bind_adjoint(lib)
+    if hasattr(lib, 'orcl_scores'):           # the scores arbiter (rr_oracle_scores.c): in the parity checker only
+        o = C.c_void_p
+        lib.orcl_scores.argtypes = [_i64, _i64, _f64p, _f64p, _i64, o, C.c_int, _f64p]
+        lib.orcl_scores_grad.argtypes = [_i64, _i64, _f64p, _f64p, _i64, o, C.c_int, _f64p, _f64p, _f64p, _f64p]
+        lib.orcl_scores.restype = lib.orcl_scores_grad.restype = C.c_int
     return lib
 
 
@@ -283,6 +291,49 @@ def uh_convolve_ld(kernel, state, lateral):
     out = np.empty((T, n))
     _check(lib().orcl_uh_convolve(T, n_ks, n, kernel, state, lateral, out))
     return out
+
+
+# ---- the scores arbiter (rr_oracle_scores.c): rr.metrics' five scores and their gradient in compensated long double ----
+
+SCORES_LD_ROWS = ('count', 'me', 'mae', 'mse', 'pearson_r', 'kge2012', 'mt', 'mp', 'kappa_t', 'kappa_p', 'beta', 'gamma', 'r_raw')
+
+
+def _scores_args(y_true, y_pred, columns):
+    t, p = _f64(y_true), _f64(y_pred)
+    if t.ndim != 2 or p.ndim != 2 or t.shape[0] != p.shape[0]:
+        raise ValueError(f'scores arbiter: (T, n) and (T, m) arrays of one length, got {t.shape} and {p.shape}')
+    cols = None if columns is None else _i32(columns)
+    if cols is not None and cols.shape != (t.shape[1],):
+        raise ValueError('scores arbiter: one column index per column of y_true')
+    return t, p, cols, (None if cols is None else cols.ctypes.data)
+
+
+def scores_ld(y_true, y_pred, columns=None, skip_missing=False) -> dict:
+    """The five scores of every column of y_true[T, n] against y_pred[T, m] (column columns[j], or j) as rr.metrics defines them, two-pass
+    in compensated long double and rounded to double once: {name: (n,)} for SCORES_LD_ROWS -- the pairs kept, the scores, both means,
+    kappa = |mean| / std of both series, KGE's beta and gamma, and the unclipped r.  float32 data: widened here (exactly)."""
+    t, p, cols, cols_p = _scores_args(y_true, y_pred, columns)
+    out = np.empty((len(SCORES_LD_ROWS), t.shape[1]))
+    rc = lib().orcl_scores(t.shape[0], t.shape[1], t, p, p.shape[1], cols_p, int(bool(skip_missing)), out)
+    if rc == -5:
+        raise ValueError('scores arbiter: a column index outside y_pred (or widths that differ without a map)')
+    _check(rc)
+    return dict(zip(SCORES_LD_ROWS, out))
+
+
+def scores_grad_ld(y_true, y_pred, G, columns=None, skip_missing=False) -> Adjoint:
+    """dL/dy_pred for G[5, n] = dL/d(me, mae, mse, pearson_r, kge2012) by DESIGN.md section 12c's closed form on the long-double
+    moments: Adjoint(grad (T, m), scale (T, m): the sum of the absolute values of the terms added into each element, bm (n,):
+    |B mt| + |P mp| of each scored column)."""
+    t, p, cols, cols_p = _scores_args(y_true, y_pred, columns)
+    G = _f64(G)
+    assert G.shape == (5, t.shape[1]), G.shape
+    r = Adjoint(grad=np.empty(p.shape), scale=np.empty(p.shape), bm=np.empty(t.shape[1]))
+    rc = lib().orcl_scores_grad(t.shape[0], t.shape[1], t, p, p.shape[1], cols_p, int(bool(skip_missing)), G, r.grad, r.scale, r.bm)
+    if rc == -5:
+        raise ValueError('scores arbiter: a column index outside y_pred (or widths that differ without a map)')
+    _check(rc)
+    return r
 
 
 # ---- host prep on the path ----

@@ -11,7 +11,9 @@ first), and device tensors come back.  `scores` returns all five scores of one p
 arrives in row blocks, its per-column state staying on the device between blocks.
 
 The device path merges per-column counts, means, M2 terms and co-moments exactly (Chan et al.) and matches the host
-path run on each column of the float64 data (float32 data: widened to float64) to rtol 1e-10.  One divergence is known:
+path run on each column of the float64 data (float32 data: widened to float64) to rtol 1e-10 -- for series whose |mean| / std stays
+below 1e7: pearson_r and kge2012 err by about 0.03 x 2^-53 x (|mean| / std of both series), me, mae and mse by roundings only (DESIGN.md
+sections 9 and 2d).  One divergence is known:
 a column that is exactly constant has M2 == 0 on the device, so its pearson_r and kge2012 are nan, where numpy's
 mean-then-subtract can leave a tiny non-zero standard deviation (1.4e-17 for 35,040 copies of 0.1) and the reference's
 KGE then returns a finite number.
